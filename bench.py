@@ -15,6 +15,14 @@ memory so that the host never stalls the device between iterations (every loss i
 the timed region).  Inputs (data, W, H) are resident in HBM when the timed region starts.  For N > 1 the T axis of
 the SAME problem is sharded over the GPUs ("scaling": "strong").  Rank 0 prints one JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line: `value` (iter/s over the K timed steps) and
+`ms_per_step`, with the figures derived from them and no instrumentation inside the timed steps.  Everything else is
+measured under --full only: the in-loop HIP event pairs and the roofline / per-kernel tables, the stand-alone kernel
+timings, the sustained run, the CPU baseline, the other formulations and configurations (the no-reuse, call-by-call and
+Gram-form loops, `other_configs`) and, for N > 1, the collectives timed alone.  --dump-outputs DIR writes what the timed
+steps computed (W and H after the last step, and its loss) as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
 Which multi-GPU form runs is decided by `route()`: WORLD_SIZE == --gpus > 1 (a launcher started one process per GPU)
 takes the per-process form; --gpus N > 1 with no launcher takes the one-process form -- no relaunch, no exec.  `comm` in
 the JSON line says which transport carried the collectives, the RCCL version and how many ranks it saw.
@@ -53,6 +61,7 @@ CONFIGS = {
     4: dict(N=2000, T=50000, K=32, L=20, l1_H=0.1, l2_H=0.2, l1_W=0.1, l2_W=0.5),
     5: dict(N=2000, T=50000, K=32, L=20, alg="hals"),
 }
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together (config 2: 23 MB in float64)
 
 
 T_PROCESS_START = time.time()
@@ -175,6 +184,24 @@ def hals_steps(rule, n, reg_kw):
         rule.update_motifs(l1W=reg_kw["l1W"], l2W=reg_kw["l2W"])
         out_.append(rule.update_feature_maps(l1H=reg_kw["l1H"], l2H=reg_kw["l2H"]))
     return out_
+
+
+def dump_outputs(dirname, arrays):
+    """arrays {name: ndarray} -> dirname/<name>.npy, at most DUMP_LIMIT_BYTES in all: float64 when that fits, else float32
+    (the device holds W and H in fp32: no value changes), else a fixed sample (seed 0, sorted) of the flattened column-major
+    elements of each array, in float32 and in proportion to its size."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # (room for the .npy headers)
+    total = sum(np.asarray(a).size for a in arrays.values())
+    dtype = np.float64 if 8 * total <= budget else np.float32
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=dtype)
+        if 4 * total > budget:
+            keep = max(1, a.size * (budget // 4) // total)
+            a = a.reshape(-1, order="F")[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def other_configs(cmf, rule, data, W0, H0, N, T, K, L, with_config3, device):
@@ -410,16 +437,27 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (kernel tables and roofline, sustained run, CPU baseline, other "
+                         "formulations and configurations); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write W, H and the loss of the last timed step as DIR/<name>.npy (float64; float32 or a seeded sample "
+                         f"when larger than {DUMP_LIMIT_BYTES >> 20} MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--T", type=int, default=0, help="override T (debugging only; invalidates the metric)")
-    ap.add_argument("--sustain", type=float, default=8.0, help="seconds of back-to-back iterations after the timed steps (0 = skip)")
+    ap.add_argument("--sustain", type=float, default=8.0, help="--full: seconds of back-to-back iterations after the timed steps (0 = skip)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the no-reuse / Gram-form / other-config side measurements (profiling runs: keeps one launch shape per kernel)")
-    ap.add_argument("--no-config3", action="store_true", help="skip config 3 (T=400000 on one GPU) in other_configs")
+                    help="--full: skip the no-reuse / Gram-form / other-config side measurements (profiling runs: keeps one launch shape per kernel)")
+    ap.add_argument("--no-config3", action="store_true", help="--full: skip config 3 (T=400000 on one GPU) in other_configs")
     ap.add_argument("--attempt-timeout", type=float, default=float(os.environ.get("CMF_BENCH_ATTEMPT_TIMEOUT", "300")),
                     help="--gpus N > 1: seconds one attempt (one form of the ladder, in its own child process) may take")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)  # set by the supervisor: this process IS the measurement
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:  # (the supervisor's children run in the repository root)
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 # ---- supervisor (multi-GPU runs): the measurement in a child process per attempt --------------------------------------
@@ -456,6 +494,10 @@ def child_command(args, tag):
         cmd.append("--no-extras")
     if args.no_config3:
         cmd.append("--no-config3")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     return cmd
 
 
@@ -900,10 +942,12 @@ def measure(args, form, progress):
                     break
             rule.set_overlap("overlap" in probe and probe["overlap"] < probe["single"])
             progress["partial"] = {"allreduce_overlap_probe_ms": {k: (1e3 * v if isinstance(v, float) else v) for k, v in probe.items()}}
-    # The timed region carries HIP event pairs (option "profile": events on the launch stream) around every fourth launch of the
+    # --full: the timed region carries HIP event pairs (option "profile": events on the launch stream) around every fourth launch of the
     # DOMINANT kernel only -- the roofline block's duration is measured live over these very steps -- because an event pair idles the
     # device a few microseconds: pairs around all four contraction kernels cost 0.5 % of the step.  The other kernels' durations (the
-    # `kernels` table) are taken the same way over a second pass of the same K steps right behind the timed one.
+    # `kernels` table) are taken the same way over a second pass of the same K steps right behind the timed one.  A plain run
+    # brackets nothing.
+    full = args.full
     prof = rule
     one_class = alg == "mult" and form == "single"
     progress["phase"] = "warm-up steps"
@@ -913,7 +957,7 @@ def measure(args, form, progress):
     # largest mean duration is the one the timed steps bracket (bit i of "profile_mask" = the i-th class name of cmf_kernel_times)
     PROF_CLASSES = ("conv", "conv_t", "conv_loss", "conv_loss_store", "hxt", "transconv", "hxt_num", "hxt_den")
     dom_class = "transconv"
-    if one_class and args.warmup > 0:
+    if full and one_class and args.warmup > 0:
         prof.set_option("profile", 1)
         timed(args.warmup, 0)
         warm = {nm: prof.kernel_times(nm) for nm in PROF_CLASSES}
@@ -924,10 +968,11 @@ def measure(args, form, progress):
     else:
         timed(args.warmup, 0)
     progress["phase"] = "timed steps"
-    prof.set_option("profile_mask", (1 << PROF_CLASSES.index(dom_class)) if one_class else 0)
-    # (HALS: the timed steps carry no event pairs at all -- one around each of an iteration's ~20 launches idles the device ~0.2 ms per
-    # iteration; the two sweeps' spans of the roofline block come from a bracketed pass of the same steps right behind the timed one)
-    prof.set_option("profile", 4 if alg == "mult" else 0)  # every 4th launch of the bracketed class
+    if full:
+        prof.set_option("profile_mask", (1 << PROF_CLASSES.index(dom_class)) if one_class else 0)
+        # (HALS: the timed steps carry no event pairs at all -- one around each of an iteration's ~20 launches idles the device ~0.2 ms per
+        # iteration; the two sweeps' spans of the roofline block come from a bracketed pass of the same steps right behind the timed one)
+        prof.set_option("profile", 4 if alg == "mult" else 0)  # every 4th launch of the bracketed class
     coll0 = None
     if sharded:
         try:  # the collectives this rank's handle issues over the timed steps (cmf_get_counter): the north star asks for ONE per iteration
@@ -946,17 +991,24 @@ def measure(args, form, progress):
         except Exception as e:  # noqa: BLE001
             coll_per_step = {"error": repr(e)}
     progress.setdefault("partial", {}).update(ms_per_step=1e3 * dt / args.steps, iters_per_s=args.steps / dt, loss_last=float(losses[-1]) if len(losses) else None)
+    if args.dump_outputs:  # what the timed steps computed, before any side measurement moves the factors on
+        progress["phase"] = "dump outputs"
+        W_last, H_last = rule.download()  # (T-sharded ranks: a collective, every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"W": W_last, "H": H_last, "loss": [losses[-1]]})
+        del W_last, H_last
     progress["phase"] = "side measurements after the timed steps"
     names = ("conv", "conv_t", "conv_loss", "conv_loss_store", "hxt", "hxt_num", "hxt_den", "transconv", "hals_h_pipeline", "hals_w_sweep")
     inloop = {}
-    for name in names:
-        kms, n = prof.kernel_times(name)
-        if n:
-            inloop[name] = (kms, n)
-    prof.set_option("profile", 0)
-    prof.set_option("profile_mask", 0)
+    if full:
+        for name in names:
+            kms, n = prof.kernel_times(name)
+            if n:
+                inloop[name] = (kms, n)
+        prof.set_option("profile", 0)
+        prof.set_option("profile_mask", 0)
     hals_spans = {}
-    if alg != "mult":
+    if full and alg != "mult":
         prof.set_option("profile", 1)
         timed(0, min(args.steps, 5))
         for name in names:
@@ -966,7 +1018,7 @@ def measure(args, form, progress):
         prof.set_option("profile", 0)
         hals_spans, inloop = inloop, {}
     dt_allpairs = None
-    if one_class:  # second pass: every contraction kernel bracketed (the dominant kernel keeps its figure from the timed steps)
+    if full and one_class:  # second pass: every contraction kernel bracketed (the dominant kernel keeps its figure from the timed steps)
         prof.set_option("profile", 4)
         dt_allpairs, _ = timed(0, args.steps)
         for name in names:
@@ -977,7 +1029,7 @@ def measure(args, form, progress):
     # Steady state: the timed region above is ~0.1 s; run back-to-back iterations for several seconds more (same call) so that
     # the figure also holds at the clock the card settles to (and the driver's GPU-busy sampling has something to see).
     sustained = None
-    if alg == "mult" and args.sustain > 0:
+    if full and alg == "mult" and args.sustain > 0:
         per = max(dt / max(args.steps, 1), 1e-4)
         n_sus = int(min(max(args.sustain / per, args.steps), 200000))
         dt_sus, _ = timed(0, n_sus)
@@ -985,7 +1037,7 @@ def measure(args, form, progress):
     # Same loop with the reference's redundant est recomputation left in (7 executed contractions
     # instead of 6): reported beside the headline so both numbers come from one run.
     dt_noreuse = None
-    extras = form == "single" and alg == "mult" and not args.no_extras
+    extras = full and form == "single" and alg == "mult" and not args.no_extras
     if extras:
         rule.set_option("reuse_est", 0)
         dt_noreuse, _ = timed(1, max(3, args.steps // 2))
@@ -1039,7 +1091,7 @@ def measure(args, form, progress):
     # tests/test_multi_gpu.py has passed on a node.
     group_extras = None
     ge_mode = os.environ.get("CMF_BENCH_GROUP_EXTRAS", "0")
-    if sharded and ge_mode != "0" and not args.no_extras:
+    if full and sharded and ge_mode != "0" and not args.no_extras:
         group_extras = {}
         keep_overlap = bool(rule.overlap)
         nrep = max(5, args.steps // 2)
@@ -1060,7 +1112,7 @@ def measure(args, form, progress):
     # step is communication
     allreduce = None
     collectives = None
-    if sharded:
+    if full and sharded:
         progress["phase"] = "collectives timed alone"
 
         def coll(name, payload, ring=True):
@@ -1165,7 +1217,7 @@ def measure(args, form, progress):
         raise FileNotFoundError("no PMC summary under profiles/")
 
     progress["phase"] = "stand-alone kernel timings"
-    if rank == 0:
+    if rank == 0 and full:
         kern = {}
         timer = rule
         Tl = T // ngpu if alg == "mult" else T
@@ -1216,8 +1268,9 @@ def measure(args, form, progress):
                            "dominant_by_second_pass": (dom_second if inloop else None)}
 
     if rank == 0 and alg == "hals":
-        out["roofline_mfma_kernel"] = out["roofline"]
-        out["roofline"] = hals_roofline(T, K, L, hals_spans, 1e3 * dt / args.steps if dt else None)
+        if full:
+            out["roofline_mfma_kernel"] = out["roofline"]
+            out["roofline"] = hals_roofline(T, K, L, hals_spans, 1e3 * dt / args.steps if dt else None)
         out["hals_pipeline_reruns"] = rule.counter("hals_pipeline_reruns")
 
     if rank == 0 and alg == "mult":
@@ -1246,7 +1299,7 @@ def measure(args, form, progress):
                 if rec_.get("ms_per_step_gram") and dt_gram:
                     rec_["speedup_before_communication_gram"] = 1e3 * dt_gram / rec_["ms_per_step_gram"]
     if rank == 0:
-        if args.cpu_seconds > 0 and ngpu == 1:
+        if full and args.cpu_seconds > 0 and ngpu == 1:
             try:
                 out["cpu_baseline"] = (cpu_baseline_hals if alg == "hals" else cpu_baseline)(data, W0, H0, args.cpu_seconds)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU line for it

@@ -206,7 +206,7 @@ def test_bench_multi_form_rehearsal_on_one_gpu(n, config, extras):
     env = dict(os.environ, CMF_BENCH_DEVICES=",".join(["0"] * n), CMF_BENCH_GROUP_EXTRAS=extras)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    args = ["--gpus", str(n), "--steps", "3", "--warmup", "1", "--sustain", "0", "--config", str(config)]
+    args = ["--gpus", str(n), "--steps", "3", "--warmup", "1", "--sustain", "0", "--config", str(config), "--full"]
     if config == 2:
         args += ["--T", "8000"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
@@ -248,7 +248,7 @@ def test_bench_ranks_form_rehearsal_on_one_gpu(transport):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--sustain", "0",
-           "--T", "8000"]
+           "--T", "8000", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -270,7 +270,7 @@ def test_bench_multi_form_rehearsal_peer_transport_and_enqueue_threads(transport
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--sustain", "0",
-                        "--T", "8000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--T", "8000", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -7,7 +7,7 @@ T=${2:-6250}
 root=$(pwd)
 out=$root/gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd $root
-B="python3 bench.py --cpu-seconds 0 --no-extras --sustain 0 --T $T --steps 20 --warmup 3"
+B="python3 bench.py --full --cpu-seconds 0 --no-extras --sustain 0 --T $T --steps 20 --warmup 3"
 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $out/${tag}_pmc_fetch -o t -- $B > /dev/null 2> $out/${tag}_pmc_fetch.err
 echo "fetch done"
 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $out/${tag}_pmc_write -o t -- $B > /dev/null 2> $out/${tag}_pmc_write.err
