@@ -436,6 +436,10 @@ int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, in
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: bad hxt LP %d", h->hxt_LP);
     }
+    for (int i = 0; i < 7; ++i)
+        if (kHxtLP[i] == h->hxt_LP) h->launches[LA_HXT + i] += 1;
+    h->launches[nsrc == 1 ? LA_HXT_NSRC1 : LA_HXT_NSRC2] += 1;
+    h->launches[p.Tl < d.Tl ? LA_HXT_TAIL : LA_HXT_NO_TAIL] += 1;
     KCHK("hxt_kernel");
     return CMF_OK;
 }
@@ -473,6 +477,9 @@ int launch_transconv(cmf_handle_s *h, int nsrc, const float *xt0, bool front_blo
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: bad transconv LT %d", h->tc_LT);
     }
+    h->launches[LA_TC + h->tc_LT / 4 - 1] += 1;
+    if (front_block) h->launches[LA_TC_FRONT] += 1;
+    if (p.W >= 64 && p.W % 32 == 0) h->launches[LA_TC_XCD] += 1; // (the plan's XCD placement: tc_plan)
     KCHK("transconv_kernel");
     return CMF_OK;
 }
@@ -488,6 +495,7 @@ int launch_slab_sum(cmf_handle_s *h, float *out, const float *in, int nslabs, si
         h->carry = CmfLossCarry{};
     }
     hipLaunchKernelGGL(slab_sum_kernel, dim3(blocks + (carry.partial ? 1 : 0)), dim3(256), 0, h->stream, out, in, nslabs, stride, n4, carry, tail);
+    h->launches[carry.partial ? LA_SLAB_SUM_CARRY : LA_SLAB_SUM] += 1;
     KCHK("slab_sum_kernel");
     return CMF_OK;
 }
@@ -1183,6 +1191,16 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
         return CMF_OK;
     }                       // H updates that ran inside the few-component C3 launch
     if (std::strcmp(name, "writeback_overlapped") == 0) { *value = h->wb ? h->wb->hooked_calls : 0; return CMF_OK; }     // ... served by the copy stream behind the H update
+    if (std::strncmp(name, "launches:", 9) == 0) { // launches of one path (kLaunchNames; a group: over its shards)
+        for (int c = 0; c < LA_NCLS; ++c)
+            if (std::strcmp(name + 9, kLaunchNames[c]) == 0) {
+                *value = h->launches[c];
+                if (h->group)
+                    for (const cmf_handle_s *s : h->group->sh) *value += (s != h) ? s->launches[c] : 0;
+                return CMF_OK;
+            }
+        return fail(CMF_ERR_ARG, "unknown launch path '%s'", name + 9);
+    }
     if (h->group) { // host cost of the pipelined iterations of a group (reading a counter resets nothing)
         cmf_group_s *g = h->group;
         if (std::strcmp(name, "allreduce_calls") == 0) { *value = g->n_allreduce; return CMF_OK; } // collectives this handle has issued since it was made

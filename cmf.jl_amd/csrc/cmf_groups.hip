@@ -631,6 +631,7 @@ static void build_exchange_halos(cmf_group_s *g, StepList &st)
             const CmfDims &d = s->d;
             hipLaunchKernelGGL(halo_pack3_kernel, dim3(8), dim3(256), 0, s->stream, s->H, g->halo3_send[i], d.PADL, d.Tl, rows, d.K32, 0, 1);
             KCHK("halo_pack3_kernel");
+            s->launches[LA_HALO_PACK3] += 1;
             return CMF_OK;
         });
         step_allgather(g, st, "cmf:all-gather of the H halos (wide)", g->halo3_send, g->halo3_all, (size_t)(3 * g->HC));
@@ -640,6 +641,7 @@ static void build_exchange_halos(cmf_group_s *g, StepList &st)
             hipLaunchKernelGGL(halo_unpack3_kernel, dim3(8), dim3(256), 0, s->stream, s->H, s->Ht, g->halo3_all[i], d.PADL, d.Tl, rows, d.K32, d.TP,
                                g->rank[i], g->nranks);
             KCHK("halo_unpack3_kernel");
+            s->launches[LA_HALO_UNPACK3] += 1;
             return CMF_OK;
         });
         return;
@@ -649,6 +651,7 @@ static void build_exchange_halos(cmf_group_s *g, StepList &st)
         const CmfDims &d = s->d;
         hipLaunchKernelGGL(halo_pack2_kernel, dim3(8), dim3(256), 0, s->stream, s->H, g->halo_send[i], d.PADL, d.PADL + d.Tl - rows, rows, d.K32);
         KCHK("halo_pack2_kernel");
+        s->launches[LA_HALO_PACK2] += 1;
         return CMF_OK;
     });
     step_allgather(g, st, "cmf:all-gather of the H halos", g->halo_send, g->halo_all, (size_t)(2 * g->HC));
@@ -658,6 +661,7 @@ static void build_exchange_halos(cmf_group_s *g, StepList &st)
         hipLaunchKernelGGL(halo_unpack2_kernel, dim3(8), dim3(256), 0, s->stream, s->H, s->Ht, s->halo[2], s->halo[3],
                            d.PADL - rows, d.PADL + d.Tl, rows, d.K32, d.TP);
         KCHK("halo_unpack2_kernel");
+        s->launches[LA_HALO_UNPACK2] += 1;
         return CMF_OK;
     });
 }
@@ -792,6 +796,7 @@ static void build_update_motifs(cmf_group_s *g, StepList &st, double l1W, double
             hipLaunchKernelGGL(halo_unpack3_kernel, dim3(8), dim3(256), 0, s->stream, s->H, s->Ht, g->red[i] + toff + (size_t)g->tail, d.PADL, d.Tl, rows,
                                d.K32, d.TP, g->rank[i], g->nranks);
             KCHK("halo_unpack3_kernel");
+            s->launches[LA_HALO_UNPACK3] += 1;
             return CMF_OK;
         });
         g->halos_current = true;
@@ -826,6 +831,7 @@ static void build_update_feature_maps(cmf_group_s *g, StepList &st, double l1H, 
             hipLaunchKernelGGL(halo_pack3_kernel, dim3(16), dim3(256), 0, s->stream, s->H, g->red[i] + toff + (size_t)g->tail, d.PADL, d.Tl, rows, d.K32,
                                g->rank[i], g->nranks);
             KCHK("halo_pack3_kernel");
+            s->launches[LA_HALO_PACK3] += 1;
             return CMF_OK;
         });
         g->halos_current = false;

@@ -132,6 +132,39 @@ struct RoctxRange {
 // ------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------
+// Launch paths of the contraction kernels (cmf_get_counter "launches:<name>"): a per-handle count per path, incremented on the
+// host at the launch site -- no device work, no change to any plan.  Instances and forms are counted separately (a launch of
+// hxt_kernel<5> with two sources and tail rows adds one to each of "hxt_kernel<5>", "hxt_kernel:nsrc2" and "hxt_kernel:tail"), so
+// that a test can reach every name with a handful of shapes.  tests/test_exact_parity.py expects exactly this list.
+enum { LA_CONV = 0, LA_CONV2, LA_CONV3_WHOLE, LA_CONV3_WHOLE_P4, LA_CONV3_WHOLE_P16, LA_CONV3_P4, LA_CONV3_P16,
+       LA_CONV_SMALL, /* + 6: NKP 1, 2, 3, 4, 6, 8 */ LA_CONV_SMALL_Q = LA_CONV_SMALL + 6, LA_CONV_SMALL_PRE,
+       LA_HXT, /* + 7: kHxtLP */ LA_HXT_NSRC1 = LA_HXT + 7, LA_HXT_NSRC2, LA_HXT_TAIL, LA_HXT_NO_TAIL,
+       LA_TC, /* + 8: LT 4 .. 32 */ LA_TC_FRONT = LA_TC + 8, LA_TC_XCD,
+       LA_HXT_SMALL, /* + 10: MBW 1 .. 10 */ LA_HXT_SMALL_RV = LA_HXT_SMALL + 10, /* + 3 */
+       LA_GFOLD = LA_HXT_SMALL_RV + 3, /* + 6: MBW 1 .. 6 */ LA_GFOLD_RV = LA_GFOLD + 6, /* + 3 */ LA_GFOLD_SPLIT = LA_GFOLD_RV + 3, LA_GFOLD_FUSED_H,
+       LA_GRAM_W, LA_GRAM_CORR, LA_GRAM_TAPS, LA_GRAM_H_MFMA, LA_GRAM_H,
+       LA_SLAB_SUM, LA_SLAB_SUM_CARRY, LA_SLAB_SUM_SMALL, LA_SLAB_SUM_SMALL_CARRY,
+       LA_HALO_PACK2, LA_HALO_UNPACK2, LA_HALO_PACK3, LA_HALO_UNPACK3, LA_NCLS };
+static const char *const kLaunchNames[] = {
+    "conv_kernel", "conv2_kernel", "conv3_kernel:whole", "conv3_kernel:whole+4", "conv3_kernel:whole+16", "conv3_kernel:pieces4", "conv3_kernel:pieces16",
+    "conv_small_kernel<1>", "conv_small_kernel<2>", "conv_small_kernel<3>", "conv_small_kernel<4>", "conv_small_kernel<6>", "conv_small_kernel<8>",
+    "conv_small_kernel:quarter", "conv_small_kernel:pre",
+    "hxt_kernel<1>", "hxt_kernel<2>", "hxt_kernel<3>", "hxt_kernel<4>", "hxt_kernel<5>", "hxt_kernel<6>", "hxt_kernel<8>",
+    "hxt_kernel:nsrc1", "hxt_kernel:nsrc2", "hxt_kernel:tail", "hxt_kernel:no_tail",
+    "transconv_kernel<4>", "transconv_kernel<8>", "transconv_kernel<12>", "transconv_kernel<16>", "transconv_kernel<20>", "transconv_kernel<24>",
+    "transconv_kernel<28>", "transconv_kernel<32>", "transconv_kernel:front_block", "transconv_kernel:xcd",
+    "hxt_small_kernel<1>", "hxt_small_kernel<2>", "hxt_small_kernel<3>", "hxt_small_kernel<4>", "hxt_small_kernel<5>", "hxt_small_kernel<6>",
+    "hxt_small_kernel<7>", "hxt_small_kernel<8>", "hxt_small_kernel<9>", "hxt_small_kernel<10>",
+    "hxt_small_kernel<1,RV>", "hxt_small_kernel<2,RV>", "hxt_small_kernel<3,RV>",
+    "g_gemm_fold_small_kernel<1>", "g_gemm_fold_small_kernel<2>", "g_gemm_fold_small_kernel<3>", "g_gemm_fold_small_kernel<4>",
+    "g_gemm_fold_small_kernel<5>", "g_gemm_fold_small_kernel<6>",
+    "g_gemm_fold_small_kernel<1,RV>", "g_gemm_fold_small_kernel<2,RV>", "g_gemm_fold_small_kernel<3,RV>",
+    "g_gemm_fold_small_kernel:split", "g_gemm_fold_small_kernel:fused_h",
+    "gram_w_kernel", "gram_lag_corr", "gram_w_taps", "gram_h_mfma_kernel", "gram_h_kernel",
+    "slab_sum_kernel", "slab_sum_kernel:carry", "slab_sum_small_kernel", "slab_sum_small_kernel:carry",
+    "halo_pack2_kernel", "halo_unpack2_kernel", "halo_pack3_kernel", "halo_unpack3_kernel"};
+static_assert(sizeof(kLaunchNames) / sizeof(kLaunchNames[0]) == LA_NCLS, "one name per launch path");
+
 struct cmf_handle_s {
     int device = 0;
     CmfDims d{};
@@ -242,6 +275,7 @@ struct cmf_handle_s {
     bool prof = false;
     int prof_every = 1;          // bracket every n-th launch of a class (option value n)
     int prof_seen[32] = {0};
+    int64_t launches[LA_NCLS] = {0}; // cmf_get_counter "launches:<name>" (kLaunchNames)
     struct ProfRec { hipEvent_t a, b; int cls; };
     unsigned prof_mask = 0; // option "profile_mask"
     std::vector<ProfRec> prof_recs;
@@ -611,6 +645,9 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
             if (nkp <= 1) CASE(1); else if (nkp == 2) CASE(2); else if (nkp == 3) CASE(3); else if (nkp == 4) CASE(4);
             else if (nkp <= 6) CASE(6); else CASE(8);
 #undef CASE
+            h->launches[LA_CONV_SMALL + (nkp <= 4 ? std::max(nkp, 1) - 1 : nkp <= 6 ? 4 : 5)] += 1;
+            if (cutq > 0) h->launches[LA_CONV_SMALL_Q] += 1;
+            if (pre) h->launches[LA_CONV_SMALL_PRE] += 1;
             h->conv_partials = (int)grid.x;
             KCHK("conv_small_kernel");
             return CMF_OK;
@@ -624,12 +661,18 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         const int pieces = (split && cut < h->n_cu && h->conv_split != 4) ? 16 : 4;
         grid = dim3(n_full + pieces * (tiles3 - n_full));
         hipLaunchKernelGGL((conv3_kernel<MODE>), grid, dim3(64), 0, h->stream, p, gx3, n_full, pieces);
+        h->launches[n_full == tiles3 ? LA_CONV3_WHOLE : n_full > 0 ? (pieces == 4 ? LA_CONV3_WHOLE_P4 : LA_CONV3_WHOLE_P16)
+                                                         : (pieces == 4 ? LA_CONV3_P4 : LA_CONV3_P16)] += 1;
     } else if (d.K % 32 == 0) {
         // the 128 x 128 kernel exists for the epilogues that only store or only sum (est, est', loss): with a data tile
         // read AND a store in the epilogue (mode 3 and the residual modes) it needs more than the 168 registers three
         // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
         if constexpr (MODE <= 2) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
-    } else hipLaunchKernelGGL((conv_kernel<MODE, 0>), grid, block, 0, h->stream, p);
+        if constexpr (MODE <= 2) h->launches[LA_CONV2] += 1;
+    } else {
+        hipLaunchKernelGGL((conv_kernel<MODE, 0>), grid, block, 0, h->stream, p);
+        h->launches[LA_CONV] += 1;
+    }
     h->conv_partials = (int)(grid.x * grid.y);
     KCHK("conv_kernel");
     return CMF_OK;

@@ -136,6 +136,7 @@ static int launch_gram_w(cmf_handle_s *h, const float *HH, float *out)
 #undef CASE
     }
     KCHK("gram_w_kernel");
+    h->launches[LA_GRAM_W] += 1;
     return CMF_OK;
 }
 
@@ -158,6 +159,7 @@ static int compute_hh(cmf_handle_s *h, float *out = nullptr)
     hipLaunchKernelGGL(hals_hh_kernel, dim3(1024), dim3(256), 0, h->stream, h->hals_C, h->H, out ? out : h->hals_HH, d.Tl, d.L, d.K, d.K32,
                        h->hals_NpC, h->hals_NpH, d.PADL, shard ? 1 : 0, (h->t_offset + d.Tl == h->T_global) ? 1 : 0);
     KCHK("hals_hh_kernel");
+    h->launches[LA_GRAM_CORR] += 1;
     return CMF_OK;
 }
 
@@ -504,6 +506,7 @@ int gram_tables(cmf_handle_s *h) // PW -> GW, GE (the lag-Gram taps of W; shared
     hipLaunchKernelGGL(hals_gw_kernel, dim3(1024), dim3(256), 0, h->stream, h->hals_PW, h->hals_GW, h->hals_GE, d.L, d.K32, h->hals_ne, d.Tl, h->hals_t_edge0,
                        h->hals_GWt, 2 * d.L); // (+ the taps as [k'][e][k], E = 2L - 1 padded to an even count, for gram_h_mfma_kernel)
     KCHK("hals_gw_kernel");
+    h->launches[LA_GRAM_TAPS] += 1;
     return CMF_OK;
 }
 
@@ -534,6 +537,7 @@ int gram_denom_h(cmf_handle_s *h, float *out)
         hipLaunchKernelGGL(gram_h_mfma_kernel, dim3(edge.n_main + n_edge), dim3(256), lds_m, h->stream, h->Ht, h->hals_GWt, out, d.K, d.L, d.K32, d.TP, d.PADL,
                            Ep, fw, ntile, edge);
         KCHK("gram_h_mfma_kernel");
+        h->launches[LA_GRAM_H_MFMA] += 1;
         if (ride) return CMF_OK;
     }
     const int block0 = t_first / 64, nblock = (d.Tl + 63) / 64 - block0; // (a half block in front of it is simply formed twice)
@@ -541,6 +545,7 @@ int gram_denom_h(cmf_handle_s *h, float *out)
         hipLaunchKernelGGL(gram_h_kernel, dim3(nblock, d.K32 / 4), dim3(256), lds, h->stream, h->Ht, h->hals_GW, h->hals_GE, out,
                            d.Tl, d.K, d.L, d.K32, d.TP, d.PADL, h->hals_ne, h->hals_t_edge0, block0);
         KCHK("gram_h_kernel");
+        h->launches[LA_GRAM_H] += 1;
     }
     return CMF_OK;
 }

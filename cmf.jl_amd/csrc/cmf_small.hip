@@ -22,6 +22,7 @@ int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int ns
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: bad m block count %d", h->sk_MBW);
     }
+    h->launches[h->sk_RV ? LA_HXT_SMALL_RV + std::min(h->sk_MBW, 3) - 1 : LA_HXT_SMALL + h->sk_MBW - 1] += 1;
     KCHK("hxt_small_kernel");
     if (slabs_only) return CMF_OK; // (the caller's next launch sums the slabs itself: w_update_small_kernel)
     CmfLossCarry carry{};
@@ -32,6 +33,7 @@ int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int ns
     const size_t n4 = (size_t)nsrc * d.L * d.K32 * d.Np / 4;
     hipLaunchKernelGGL(slab_sum_small_kernel, dim3((unsigned)std::min<size_t>(2048, (n4 + 255) / 256)), dim3(256), 0, h->stream, out, h->sk_slabs,
                        h->sk_ngroups, nsrc, d.L, d.K, d.K32, d.Np, h->sk_JP, carry);
+    h->launches[carry.partial ? LA_SLAB_SUM_SMALL_CARRY : LA_SLAB_SUM_SMALL] += 1;
     KCHK("slab_sum_small_kernel");
     return CMF_OK;
 }
@@ -79,6 +81,9 @@ int launch_transconv_small(cmf_handle_s *h, int nsrc, const float *xt0, bool upd
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: bad m block count %d", h->sk3_MBW);
     }
+    h->launches[h->sk3_RV ? LA_GFOLD_RV + std::min(h->sk3_MBW, 3) - 1 : LA_GFOLD + h->sk3_MBW - 1] += 1;
+    if (h->sk3_NS > 1) h->launches[LA_GFOLD_SPLIT] += 1;
+    if (update_h) h->launches[LA_GFOLD_FUSED_H] += 1;
     KCHK("g_gemm_fold_small_kernel");
     return CMF_OK;
 }

@@ -187,7 +187,19 @@ int cmf_rccl_version(int *version, char *path, int64_t path_len);
  * the MU rule that ran inside the few-component contraction launch (option "small_k_fuse").  Group handles: "enqueue_ns" /
  * "enqueue_iters" = nanoseconds the calling thread spent enqueueing (or posting to the enqueue workers) the pipelined
  * iterations of cmf_iterate, and how many iterations that covers; "worker_ns" = time the busiest enqueue worker spent
- * inside its jobs (0 without workers). */
+ * inside its jobs (0 without workers).  "launches:<path>" (a group: over its shards): launches of one kernel path, counted on the
+ * host at the launch site (observability for tests; no device work).  Instances and forms count separately, so one launch adds to
+ * several names:  conv_kernel (K % 32 != 0), conv2_kernel, conv3_kernel:whole, conv3_kernel:whole+4, conv3_kernel:whole+16,
+ * conv3_kernel:pieces4, conv3_kernel:pieces16 (whole 64 x 64 tiles only / with the grid's tail cut into quarter or sixteenth
+ * pieces / pieces only);  conv_small_kernel<NKP> (NKP 1, 2, 3, 4, 6, 8), conv_small_kernel:quarter, conv_small_kernel:pre;
+ * hxt_kernel<LP> (LP 1, 2, 3, 4, 5, 6, 8), hxt_kernel:nsrc1, hxt_kernel:nsrc2, hxt_kernel:tail, hxt_kernel:no_tail (rows past
+ * the last whole ring rotation left to the slab sum, or none);  transconv_kernel<LT> (LT 4, 8, ..., 32),
+ * transconv_kernel:front_block, transconv_kernel:xcd (the plan's XCD placement);  hxt_small_kernel<MBW> (1 .. 10),
+ * hxt_small_kernel<MBW,RV> (1 .. 3: with VALU rows), g_gemm_fold_small_kernel<MBW> (1 .. 6), g_gemm_fold_small_kernel<MBW,RV>
+ * (1 .. 3), g_gemm_fold_small_kernel:split (the reduction over n in more than one piece), g_gemm_fold_small_kernel:fused_h;
+ * gram_w_kernel, gram_lag_corr, gram_w_taps, gram_h_mfma_kernel, gram_h_kernel;  slab_sum_kernel, slab_sum_kernel:carry,
+ * slab_sum_small_kernel, slab_sum_small_kernel:carry (with a deferred loss reduction riding on it);  halo_pack2_kernel,
+ * halo_unpack2_kernel, halo_pack3_kernel, halo_unpack3_kernel.  An unknown path is CMF_ERR_ARG. */
 int cmf_get_counter(cmf_handle h, const char *name, int64_t *value);
 
 /* Run all work of this handle on an existing HIP stream (hipStream_t passed
