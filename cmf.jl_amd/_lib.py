@@ -34,6 +34,7 @@ SYMBOLS = [
     "cmf_update_motifs", "cmf_update_feature_maps", "cmf_compute_loss", "cmf_iterate", "cmf_fit", "cmf_converged",
     "cmf_hals_update_motifs", "cmf_hals_update_feature_maps",
     "cmf_pgd_reset", "cmf_set_mask", "cmf_pgd_set_loss", "cmf_pgd_update_motifs", "cmf_pgd_update_feature_maps", "cmf_pgd_get_steps",
+    "cmf_admm_prepare", "cmf_admm_update_motifs", "cmf_admm_update_feature_maps",
     "cmf_tensor_conv", "cmf_tensor_transconv", "cmf_init_rand", "cmf_gen_synthetic",
     "cmf_time_kernel", "cmf_kernel_times",
 ]
@@ -122,6 +123,9 @@ def load():
     sig("cmf_pgd_update_motifs", [vp, dbl, dbl, cint])
     sig("cmf_pgd_update_feature_maps", [vp, dbl, dbl, cint, pd])
     sig("cmf_pgd_get_steps", [vp, pd, pd])
+    sig("cmf_admm_prepare", [vp, pd])
+    sig("cmf_admm_update_motifs", [vp, pd, pd, dbl, i64, dbl, cint, pi64])
+    sig("cmf_admm_update_feature_maps", [vp, pd, pd, dbl, i64, dbl, dbl, cint, pd, pi64])
     sig("cmf_tensor_conv", [cint, i64, i64, i64, i64, pd, pd, pd])
     sig("cmf_tensor_transconv", [cint, i64, i64, i64, i64, pd, pd, pd])
     sig("cmf_init_rand", [cint, i64, i64, i64, i64, u64, pd, pd, pd])

@@ -303,7 +303,12 @@ struct cmf_handle_s {
     bool dev_stamps = false;              // set by cmf_fit around its pipelined batch: time_hist from HIP timing events on the stream
     CmfLossCarry carry{};                 // a loss reduction waiting for the next W phase's slab sum (cmf_iterate only)
     CmfWriteback *wb = nullptr;           // cmf_arm_writeback: the factors written into the caller's arrays behind a rule call
+    struct AdmmState *admm = nullptr;     // the ADMM rule's fp64 state (cmf_admm_prepare; cmf_admm.hip)
 };
+
+// cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)
+void admm_free(cmf_handle_s *h);
+int admm_counter(const cmf_handle_s *h, const char *name, int64_t *value);
 
 #define HALS_PMAX 4 // puller workgroups per row of the persistent H pipeline (4 -> 7 measured the same span: profiles/r04_hals_pullers_sweep.txt)
 

@@ -571,6 +571,107 @@ class PGDUpdate(MultUpdate):
 HIPPGDUpdate = PGDUpdate
 
 
+class ADMMUpdate(AbstractCFUpdate):
+    """ADMMUpdate on MI355X: drop-in for src/algs/admm.jl, computed in fp64 end to end.
+
+    ``ADMMUpdate(data, W, H)`` mirrors admm.jl:13-21: it uploads ``data`` in fp64 and keeps its norm (cmf_admm_prepare).  Unlike
+    the other rules nothing of W or H stays on the device between calls: each call reads exactly the factor the reference reads
+    (``update_motifs`` reads H, ``update_feature_maps`` reads W) from the caller's array and overwrites the other one in place,
+    as the reference does.  The inner ADMM loops restart from zero on every call (admm.jl:36-48, :152-163).
+
+    After a call, ``last_W_iters`` / ``last_H_iters`` hold its inner iteration count and ``last_W_reverts`` /
+    ``last_H_reverts`` its reverts (cmf_get_counter "admm_W_reverts" / "admm_H_reverts").  One GPU only.
+    """
+
+    last_W_iters = last_H_iters = last_W_reverts = last_H_reverts = 0
+    MAX_T = 65535 * 64  # columns one contraction launch covers (cmf_admm_prepare refuses more)
+
+    def __init__(self, data, W, H, device=None, devices=None):
+        if devices is not None:
+            raise NotImplementedError("ADMMUpdate runs on one GPU: devices=[...] (T sharding) is not available for the ADMM rule")
+        lib = _lib.load()
+        self._lib = lib
+        self._h = ctypes.c_void_p()
+        data = farr(data)
+        if data.ndim != 2:
+            raise ValueError("data must be a matrix (N x T)")
+        W = farr(W)
+        if W.ndim != 3:
+            raise ValueError("W must be a K x N x L tensor")
+        K, N, L = W.shape
+        if data.shape[0] != N:
+            raise ValueError(f"DimensionMismatch: data has {data.shape[0]} rows, W has N={N}")
+        T = data.shape[1]
+        farr(H, (K, T))
+        if T > self.MAX_T:  # (cmf_create would cut such a recording into a T-sharded group, which the ADMM rule cannot run on)
+            raise NotImplementedError(f"ADMMUpdate runs on one handle of at most {self.MAX_T} columns (T = {T})")
+        self.N, self.T, self.K, self.L = N, T, K, L
+        self.device = _dev(device)
+        check(lib.cmf_create(ctypes.byref(self._h), self.device, N, T, K, L, ptr(data)))
+        try:
+            check(lib.cmf_admm_prepare(self._h, ptr(data)))
+        except Exception:
+            self.close()
+            raise
+        self.data_norm = float(np.linalg.norm(data))  # admm.jl:17
+
+    @staticmethod
+    def _out(a, shape):
+        """The caller's array if the library can write it in place, else a Fortran float64 copy (copied back after the call)."""
+        if not isinstance(a, np.ndarray) or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"expected an array of shape {tuple(shape)}")
+        if a.dtype == np.float64 and a.flags.f_contiguous and a.flags.writeable:
+            return a
+        return np.asfortranarray(a, dtype=np.float64).copy(order="F")
+
+    def update_motifs(self, data, W, H, rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=True, **kwargs):
+        """update_motifs!(rule::ADMMUpdate, data, W, H; rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=true): admm.jl:24-121.
+        Reads H, overwrites W."""
+        Hin = farr(H, (self.K, self.T))
+        Wout = self._out(W, (self.K, self.N, self.L))
+        iters = ctypes.c_int64()
+        check(self._lib.cmf_admm_update_motifs(self._h, ptr(Hin), ptr(Wout), float(rhow), int(admm_W_maxiter), float(admm_tol),
+                                               1 if nonnegW else 0, ctypes.byref(iters)))
+        if Wout is not W:
+            W[...] = Wout
+        self.last_W_iters, self.last_W_reverts = iters.value, self.counter("admm_W_reverts")
+
+    def update_feature_maps(self, data, W, H, rhoh=10, admm_H_maxiter=30, l1H=0, admm_tol=1e-4, nonnegH=True, **kwargs):
+        """update_feature_maps!(rule::ADMMUpdate, data, W, H; rhoh=10, admm_H_maxiter=30, l1H=0, admm_tol=1e-4, nonnegH=true)
+        -> loss: admm.jl:124-226.  Reads W, overwrites H."""
+        Win = farr(W, (self.K, self.N, self.L))
+        Hout = self._out(H, (self.K, self.T))
+        loss, iters = ctypes.c_double(), ctypes.c_int64()
+        check(self._lib.cmf_admm_update_feature_maps(self._h, ptr(Win), ptr(Hout), float(rhoh), int(admm_H_maxiter), float(l1H),
+                                                     float(admm_tol), 1 if nonnegH else 0, ctypes.byref(loss), ctypes.byref(iters)))
+        if Hout is not H:
+            H[...] = Hout
+        self.last_H_iters, self.last_H_reverts = iters.value, self.counter("admm_H_reverts")
+        return loss.value
+
+    def counter(self, name):
+        v = ctypes.c_int64()
+        check(self._lib.cmf_get_counter(self._h, name.encode(), ctypes.byref(v)))
+        return v.value
+
+    def set_option(self, name, value):
+        raise NotImplementedError(f"ADMMUpdate has no library options (got {name!r}): cmf_set_option selects paths of the other rules")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.cmf_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+HIPADMMUpdate = ADMMUpdate
+
+
 def _resolve_alg(alg):
     """alg may be a rule type (HEAD, model.jl:60) or a README-style symbol (README.md:30-33)."""
     if isinstance(alg, str):
@@ -581,8 +682,10 @@ def _resolve_alg(alg):
             return HALSUpdate
         if name == "pgd":
             return PGDUpdate
-        if name in ("anls", "admm", "sep"):
-            raise NotImplementedError(f"alg=:{name} is outside the MI355X hot path built here (:mult, :hals, :pgd)")
+        if name == "admm":
+            return ADMMUpdate
+        if name in ("anls", "sep"):
+            raise NotImplementedError(f"alg=:{name} is outside the MI355X hot path built here (:mult, :hals, :pgd, :admm)")
         raise ValueError(f"unknown algorithm {alg!r}")
     if isinstance(alg, type) and issubclass(alg, AbstractCFUpdate):
         return alg
@@ -653,7 +756,8 @@ def fit(alg, data, L, K, W_init, H_init, verbose=False, **kwargs):
 _REG_ALIASES = {"l1_W": "l1W", "l2_W": "l2W", "l1_H": "l1H", "l2_H": "l2H"}  # README.md:44-52 -> mult.jl:23,42
 _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_mode", "tol", "verbose",
              "l1W", "l2W", "l1H", "l2H", "device", "devices", "options",
-             "loss_func", "constrW", "constrH", "penaltiesW", "penaltiesH"}  # PGDUpdate (pgd.jl:158-202)
+             "loss_func", "constrW", "constrH", "penaltiesW", "penaltiesH",  # PGDUpdate (pgd.jl:158-202)
+             "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH"}  # ADMMUpdate (admm.jl:24-27,124-127)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -702,12 +806,14 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     W_init = kw.get("W_init", W_init)  # :72-73
     H_init = kw.get("H_init", H_init)
 
+    if devices is not None and rule_type is ADMMUpdate:
+        raise NotImplementedError("devices=[...] (T sharding) is not available for alg=:admm: the ADMM rule runs on one GPU")
     if devices is not None and rule_type not in (MultUpdate, PGDUpdate):
         raise NotImplementedError("devices=[...] (T sharding) is available for alg=:mult and :pgd; HALS sweeps H sequentially along T")
     if devices is not None:
         rule = rule_type(data, W_init, H_init, devices=devices)
     else:
-        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, MultUpdate)
+        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, (MultUpdate, ADMMUpdate))
                 else rule_type(data, W_init, H_init))
     try:
         for name, value in (options or {}).items():

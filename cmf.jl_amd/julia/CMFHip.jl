@@ -318,6 +318,61 @@ const ALGORITHMS = Dict{Symbol,Any}(
 )
 
 """
+    HIPADMMUpdate(data, W, H; device=LOCAL_RANK or 0)
+
+Drop-in for `ADMMUpdate(data, W, H)` (src/algs/admm.jl:13-21), computed in fp64 on one GPU.  Not in `ALGORITHMS`: select
+it by type, as the reference does (`fit_cnmf(data; alg=HIPADMMUpdate)`, model.jl:60).  Each call reads the factor the
+reference reads (`update_motifs!` H, `update_feature_maps!` W) and overwrites the other one in place; `W_iters` / `H_iters`
+hold the inner iteration counts of the last calls.
+"""
+mutable struct HIPADMMUpdate <: AbstractCFUpdate
+    handle::Ptr{Cvoid}
+    W_iters::Int64
+    H_iters::Int64
+end
+function HIPADMMUpdate(data, W, H; device::Integer=parse(Int, get(ENV, "LOCAL_RANK", "0")))
+    K, N, L = size(W)
+    T = size(data, 2)
+    size(data, 1) == N || throw(DimensionMismatch("data has $(size(data,1)) rows, W has N=$N"))
+    size(H) == (K, T) || throw(DimensionMismatch("H must be $K x $T"))
+    d = Matrix{Float64}(data)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:cmf_create, LIBCMF), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64, Int64, Ptr{Float64}),
+                h, device, N, T, K, L, d))
+    rule = HIPADMMUpdate(h[], 0, 0)
+    finalizer(r -> (r.handle != C_NULL && ccall((:cmf_destroy, LIBCMF), Cint, (Ptr{Cvoid},), r.handle); r.handle = C_NULL), rule)
+    check(ccall((:cmf_admm_prepare, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), rule.handle, d))
+    return rule
+end
+
+# update_motifs!(rule::ADMMUpdate, data, W, H; rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=true)  -- src/algs/admm.jl:24-121
+function update_motifs!(rule::HIPADMMUpdate, data, W, H; rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=true, kwargs...)
+    Hc = Matrix{Float64}(H)
+    Wc = W isa Array{Float64,3} ? W : Array{Float64,3}(W)
+    iters = Ref{Int64}(0)
+    check(ccall((:cmf_admm_update_motifs, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Float64, Cint, Ref{Int64}),
+                rule.handle, Hc, Wc, rhow, admm_W_maxiter, admm_tol, nonnegW ? 1 : 0, iters))
+    Wc === W || (W .= Wc)
+    rule.W_iters = iters[]
+    return W
+end
+
+# update_feature_maps!(rule::ADMMUpdate, data, W, H; rhoh=10, admm_H_maxiter=30, l1H=0, admm_tol=1e-4, nonnegH=true) -> loss
+# -- src/algs/admm.jl:124-226
+function update_feature_maps!(rule::HIPADMMUpdate, data, W, H; rhoh=10, admm_H_maxiter=30, l1H=0, admm_tol=1e-4, nonnegH=true,
+                              kwargs...)
+    Wc = Array{Float64,3}(W)
+    Hc = H isa Matrix{Float64} ? H : Matrix{Float64}(H)
+    loss, iters = Ref{Float64}(0.0), Ref{Int64}(0)
+    check(ccall((:cmf_admm_update_feature_maps, LIBCMF), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Float64, Float64, Cint, Ref{Float64}, Ref{Int64}),
+                rule.handle, Wc, Hc, rhoh, admm_H_maxiter, l1H, admm_tol, nonnegH ? 1 : 0, loss, iters))
+    Hc === H || (H .= Hc)
+    rule.H_iters = iters[]
+    return loss[]
+end
+
+"""
     iterate!(rule, n; l1W=0, l2W=0, l1H=0, l2H=0, eval_mode=false) -> losses
 
 `n` x (`update_motifs!`; `update_feature_maps!`) back to back (alternating.jl:51-54) in one ccall (`cmf_iterate`): the

@@ -67,7 +67,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_admm.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -407,6 +407,33 @@ int cmf_pgd_set_loss(cmf_handle h, int loss_kind);
 int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int constraint);
 int cmf_pgd_update_feature_maps(cmf_handle h, double pen_sq, double pen_abs, int constraint, double *loss);
 int cmf_pgd_get_steps(cmf_handle h, double *stepW, double *stepH);
+
+/* ---- ADMM rule ----------------------------------------------------------------------------------------------------------
+ * The fourth rule of the reference (src/CMF.jl:4), computed in fp64 end to end: data, factors, auxiliaries, contractions, the
+ * Gram matrices, their factorisations and the FFT ("The ADMM rule", says why and how).  The entries take the caller's
+ * arrays in and out -- the rule reads exactly what it is handed and overwrites the other factor in place, as the reference does --
+ * and keep clear of cmf_set_factors / cmf_arm_writeback, whose device copies are fp32.  Single-GPU handles only: a handle that
+ * fronts a T-sharded group gets CMF_ERR_UNSUPPORTED.  cmf_get_counter "admm_W_reverts" / "admm_H_reverts" give the reverts
+ * (admm.jl:101-105, :205-209) of the last call of each kind.
+ *
+ * ADMMUpdate(data, W, H) (src/algs/admm.jl:13-21): uploads `data` (N x T, fp64) and keeps norm(data); allocates the rule's fp64
+ * state on the handle's device.  The random U of the constructor is zeroed before every use (admm.jl:46-48) and is not kept. */
+int cmf_admm_prepare(cmf_handle h, const double *data);
+/* update_motifs!(rule::ADMMUpdate, data, W, H; rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=true)  src/algs/admm.jl:24-121.
+ * Reads H (K x T) only and overwrites W (K x N x L) with the fold of Z3 (admm.jl:114-120).  G = Hstk*Hstk' + 2I (admm.jl:53) is
+ * factorised once per call; the inner loop (admm.jl:61-108) starts from zero auxiliaries and duals, updates the duals before the
+ * loss, and reverts Z3 / breaks on the loss history of the call.  *iters (may be NULL) receives the inner iterations run.
+ * L*K <= 8192. */
+int cmf_admm_update_motifs(cmf_handle h, const double *H, double *W, double rhow, int64_t maxiter, double tol, int nonnegW,
+                           int64_t *iters);
+/* update_feature_maps!(rule::ADMMUpdate, data, W, H; rhoh=10, admm_H_maxiter=30, l1H=0, admm_tol=1e-4, nonnegH=true) -> loss
+ * src/algs/admm.jl:124-226.  Reads W only and overwrites H with Z3 (admm.jl:219); *loss = norm(conv(W, H) - data) / norm(data)
+ * (admm.jl:225).  The linear solve uses rho = 1 whatever rhoh is (precompute_solveH(W, 1, T), admm.jl:167, 180-182); the Z1 step
+ * uses the circular convolution (tesnor_circconv!, common.jl:36-50), the loss the linear one; the revert / break check comes
+ * before the dual update (admm.jl:203-216).  Needs T >= L (CMF_ERR_ARG: the reference indexes wh[:, :, 1:L], admm.jl:233) and
+ * K <= 64 (CMF_ERR_UNSUPPORTED).  *iters (may be NULL) receives the inner iterations run. */
+int cmf_admm_update_feature_maps(cmf_handle h, const double *W, double *H, double rhoh, int64_t maxiter, double l1H, double tol,
+                                 int nonnegH, double *loss, int64_t *iters);
 
 /* converged(loss_hist, patience, tol): src/model.jl:91-107 (host arithmetic). */
 int cmf_converged(const double *loss_hist, int64_t len, int64_t patience, double tol);
