@@ -1,11 +1,11 @@
-"""cmf.jl_amd -- MI355X (gfx950) implementation of CMF.jl's update rules (MU, HALS, PGD, ADMM).
+"""cmf.jl_amd -- MI355X (gfx950) implementation of CMF.jl's update rules (MU, HALS, PGD, ADMM, ANLS).
 
 The directory name is not a Python identifier; import it through the shim at the
 repo root:  ``import cmf_jl_amd as cmf``.
 """
 from ._lib import CMFError, LIB_PATH, SYMBOLS, load as load_library  # noqa: F401
 from .host import (  # noqa: F401
-    EPSILON, ADMMUpdate, AbsoluteLoss, AbsolutePenalty, AbstractCFUpdate, AlternatingOptimizer, CNMF_results, HALSUpdate, HIPADMMUpdate, HIPHALSUpdate,
+    EPSILON, ADMMUpdate, ANLSUpdate, AbsoluteLoss, AbsolutePenalty, AbstractCFUpdate, AlternatingOptimizer, CNMF_results, HALSUpdate, HIPADMMUpdate, HIPANLSUpdate, HIPHALSUpdate,
     HIPMultUpdate, HIPPGDUpdate, MaskedLoss, MultUpdate, NonnegConstraint, PGDUpdate, SquareLoss, SquarePenalty, UnitNormConstraint,
     compute_loss, converged, evaluate_convergence, evaluate_mse, evaluate_test, fit, fit_cnmf, gen_synthetic,
     init_rand, load_model, parameter_sweep, rccl_version, save_model, tensor_conv, tensor_transconv,

@@ -13,6 +13,7 @@
 //   admm_w_cols_kernel   W side steps 4-6 on the stacked columns (norm rule w[n] >= 1, projection, duals U2 / U3)
 //   admm_h_aux_kernel    H side steps 3-4 (soft threshold, projection); admm_h_dual_kernel the duals Q2 / Q3
 //   admm_sum_kernel      the loss partials of a contraction, summed in a fixed order
+// The kernels are static: cmf_anls.h includes this header too, for the contraction kernel and its loaders.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -122,7 +123,7 @@ struct EpiZ1H { // est[n, t] = acc (kept for the dual update); Z1 = c1*((est+Q1)
 
 // A_MFAST / B_PFAST: which index of the loader is contiguous in memory, so that a wave's tile loads run along it
 template <class AL, class BL, class EP, bool A_MFAST, bool B_PFAST>
-__global__ __launch_bounds__(256) void admm_gemm_kernel(AL A, BL B, EP E, int64_t M, int64_t P, int64_t R, double *partial)
+static __global__ __launch_bounds__(256) void admm_gemm_kernel(AL A, BL B, EP E, int64_t M, int64_t P, int64_t R, double *partial)
 {
     __shared__ double As[TR][TM + 1];
     __shared__ double Bs[TR][TP + 1];
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256) void admm_gemm_kernel(AL A, BL B, EP E, int64_
 }
 
 // sum of n partials into out[0], one workgroup, fixed order (deterministic)
-__global__ __launch_bounds__(256) void admm_sum_kernel(const double *partial, int64_t n, double *out)
+static __global__ __launch_bounds__(256) void admm_sum_kernel(const double *partial, int64_t n, double *out)
 {
     __shared__ double red[256];
     double s = 0.0;
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void admm_sum_kernel(const double *partial, in
 
 // ---- W side: Cholesky of the LK x LK Gram and the triangular solves ------------------------------------------------------------
 // In place on G (row-major, lower triangle used); writes the factor's transpose to Lt for the backward solve.
-__global__ __launch_bounds__(1024) void admm_chol_kernel(double *G, double *Lt, int n)
+static __global__ __launch_bounds__(1024) void admm_chol_kernel(double *G, double *Lt, int n)
 {
     const int tid = threadIdx.x;
     for (int j = 0; j < n; ++j) {
@@ -228,7 +229,7 @@ __device__ inline double wave_sum(double v)
 }
 
 // X[:, n] = (L L')^{-1} X[:, n] for the columns of X ([i][n], row stride N): one wave per column, the column in LDS (LK doubles)
-__global__ __launch_bounds__(64) void admm_trsm_kernel(const double *Lf, const double *Lt, double *X, int n, int64_t N)
+static __global__ __launch_bounds__(64) void admm_trsm_kernel(const double *Lf, const double *Lt, double *X, int n, int64_t N)
 {
     extern __shared__ double y[];
     const int64_t col = blockIdx.x;
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(64) void admm_trsm_kernel(const double *Lf, const d
 
 // W side steps 4-6 (admm.jl:72-91, U1 is in the estT epilogue) on the stacked columns, one thread per column n:
 // V2 = Wstk + U2, w = |V2|^2, Z2 = V2 / sqrt(w) where w >= 1 (else kept), Z3 = max(0, Wstk + U3) into Z3n, U2 += Wstk - Z2, U3 += Wstk - Z3
-__global__ __launch_bounds__(256) void admm_w_cols_kernel(const double *Wstk, double *Z2, double *U2, double *Z3n, double *U3, int LK, int64_t N, int nonneg)
+static __global__ __launch_bounds__(256) void admm_w_cols_kernel(const double *Wstk, double *Z2, double *U2, double *Z3n, double *U3, int LK, int64_t N, int nonneg)
 {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256) void admm_w_cols_kernel(const double *Wstk, do
 
 // ---- H side ---------------------------------------------------------------------------------------------------------------------
 // A[d + L-1][k][k'] = sum_n sum_{l - l' = d} W[k, n, l] W[k', n, l'] (k >= k' only: the Grams are Hermitian)
-__global__ __launch_bounds__(256) void admm_lag_gram_kernel(const double *W, double *A, int K, int64_t N, int L)
+static __global__ __launch_bounds__(256) void admm_lag_gram_kernel(const double *W, double *A, int K, int64_t N, int L)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t nd = 2 * L - 1;
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void admm_lag_gram_kernel(const double *W, dou
 }
 
 // Gram_f (lower triangle) and its Cholesky for f = 0..F-1, in place in Lf[(i*K + j)*F + f] (complex as double2)
-__global__ __launch_bounds__(64) void admm_freq_chol_kernel(const double *A, double2 *Lf, int K, int L, int64_t T, int64_t F)
+static __global__ __launch_bounds__(64) void admm_freq_chol_kernel(const double *A, double2 *Lf, int K, int L, int64_t T, int64_t F)
 {
     const int64_t f = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (f >= F) return;
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(64) void admm_freq_chol_kernel(const double *A, dou
 }
 
 // Y[k][f] <- Gram_f^{-1} Y[k][f] for f = 0..F-1 (Y row-major K x T complex), and Y[k][T-f] = conj(Y[k][f])
-__global__ __launch_bounds__(64) void admm_freq_solve_kernel(const double2 *Lf, double2 *Y, int K, int64_t T, int64_t F)
+static __global__ __launch_bounds__(64) void admm_freq_solve_kernel(const double2 *Lf, double2 *Y, int K, int64_t T, int64_t F)
 {
     const int64_t f = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (f >= F) return;
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(64) void admm_freq_solve_kernel(const double2 *Lf, 
 }
 
 // H side steps 3-4 (admm.jl:189-197): Z2 = sign(H+Q2) max(0, |H+Q2| - lam), Z3 = max(0, H+Q3) into Z3n
-__global__ __launch_bounds__(256) void admm_h_aux_kernel(const double *H, const double *Q2, const double *Q3, double *Z2, double *Z3n, int64_t n, double lam, int nonneg)
+static __global__ __launch_bounds__(256) void admm_h_aux_kernel(const double *H, const double *Q2, const double *Q3, double *Z2, double *Z3n, int64_t n, double lam, int nonneg)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(256) void admm_h_aux_kernel(const double *H, const 
 }
 
 // admm.jl:214-216: Q1 += est - Z1 (n1 elements), Q2 += H - Z2, Q3 += H - Z3 (n2 elements)
-__global__ __launch_bounds__(256) void admm_h_dual_kernel(double *Q1, const double *est, const double *Z1, int64_t n1, double *Q2, double *Q3,
+static __global__ __launch_bounds__(256) void admm_h_dual_kernel(double *Q1, const double *est, const double *Z1, int64_t n1, double *Q2, double *Q3,
                                                           const double *H, const double *Z2, const double *Z3, int64_t n2)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(256) void admm_h_dual_kernel(double *Q1, const doub
 
 // ---- FFT along T: Bluestein over a radix-2 Stockham FFT of length M (a power of two >= 2T-1) -------------------------------------
 // chirp w[m] = exp(-pi i m^2 / T), the angle from m^2 mod 2T in integers; b[m] = conj(w[|m|]) wrapped into length M
-__global__ __launch_bounds__(256) void admm_chirp_kernel(double2 *w, double2 *b, int64_t T, int64_t M)
+static __global__ __launch_bounds__(256) void admm_chirp_kernel(double2 *w, double2 *b, int64_t T, int64_t M)
 {
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(256) void admm_chirp_kernel(double2 *w, double2 *b,
 
 // buf[row][m] = x[row][m] * w[m] for m < T, 0 up to M.  REAL: x is real (row stride T); else complex, conjugated when CONJ
 template <bool REAL, bool CONJ>
-__global__ __launch_bounds__(256) void admm_fft_pre_kernel(const void *x, const double2 *w, double2 *buf, int64_t T, int64_t M)
+static __global__ __launch_bounds__(256) void admm_fft_pre_kernel(const void *x, const double2 *w, double2 *buf, int64_t T, int64_t M)
 {
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
     if (m >= M) return;
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(256) void admm_fft_pre_kernel(const void *x, const 
 }
 
 // one radix-2 Stockham stage (natural order in and out after log2(M) stages); sign -1 forward, +1 inverse (unnormalised)
-__global__ __launch_bounds__(256) void admm_fft_stage_kernel(const double2 *in, double2 *out, int64_t M, int64_t Ns, double sign)
+static __global__ __launch_bounds__(256) void admm_fft_stage_kernel(const double2 *in, double2 *out, int64_t M, int64_t Ns, double sign)
 {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
     const int64_t half = M >> 1;
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(256) void admm_fft_stage_kernel(const double2 *in, 
 }
 
 // buf[row][m] *= bh[m]
-__global__ __launch_bounds__(256) void admm_fft_mul_kernel(double2 *buf, const double2 *bh, int64_t M)
+static __global__ __launch_bounds__(256) void admm_fft_mul_kernel(double2 *buf, const double2 *bh, int64_t M)
 {
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
     if (m >= M) return;
@@ -458,7 +459,7 @@ __global__ __launch_bounds__(256) void admm_fft_mul_kernel(double2 *buf, const d
 
 // X[row][t] = w[t] * conv[row][t] / M.  REAL: write Re(X) * scale into a real row (the inverse transform's real part)
 template <bool REAL>
-__global__ __launch_bounds__(256) void admm_fft_post_kernel(const double2 *buf, const double2 *w, void *X, int64_t T, int64_t M, double scale)
+static __global__ __launch_bounds__(256) void admm_fft_post_kernel(const double2 *buf, const double2 *w, void *X, int64_t T, int64_t M, double scale)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
     if (t >= T) return;

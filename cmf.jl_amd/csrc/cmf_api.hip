@@ -202,6 +202,7 @@ static void destroy_impl(cmf_handle_s *h)
     if (!h->root_only) (void)hipSetDevice(h->device);
     wb_free(h);
     admm_free(h);
+    anls_free(h);
     if (h->root_only) { delete h; return; }
     (void)hipSetDevice(h->device);
     auto mine = [&](const void *q) { // not a piece of the arena
@@ -1186,6 +1187,7 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
     if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
     if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
+    if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
     if (std::strcmp(name, "small_k_fused_h_updates") == 0) { // (a group: over its shards)
         *value = h->sk_fused_h;
         if (h->group)
@@ -1253,6 +1255,12 @@ int cmf_option_names(char *buf, int64_t len)
 int cmf_set_option(cmf_handle h, const char *name, int value)
 {
     if (!h || !name) return fail(CMF_ERR_ARG, "NULL argument");
+    if (std::strcmp(name, "anls_backup_only") == 0) { // the ANLS rule's only option (not a path of the rules cmf_option_names lists): plain principal pivoting
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "anls_backup_only: the ANLS rule runs on single-GPU handles only");
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "anls_backup_only must be 0 or 1");
+        h->anls_backup_only = value;
+        return CMF_OK;
+    }
     if (h->group) {
         cmf_group_s *g = h->group;
         CMFTRY(group_join(g));

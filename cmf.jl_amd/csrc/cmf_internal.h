@@ -304,11 +304,16 @@ struct cmf_handle_s {
     CmfLossCarry carry{};                 // a loss reduction waiting for the next W phase's slab sum (cmf_iterate only)
     CmfWriteback *wb = nullptr;           // cmf_arm_writeback: the factors written into the caller's arrays behind a rule call
     struct AdmmState *admm = nullptr;     // the ADMM rule's fp64 state (cmf_admm_prepare; cmf_admm.hip)
+    struct AnlsState *anls = nullptr;     // the ANLS rule's fp64 state (cmf_anls_prepare; cmf_anls.hip)
+    int anls_backup_only = 0;             // cmf_set_option "anls_backup_only": every exchange of the ANLS solver is a backup-rule exchange
 };
 
 // cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)
 void admm_free(cmf_handle_s *h);
 int admm_counter(const cmf_handle_s *h, const char *name, int64_t *value);
+// cmf_anls.hip: the same for the ANLS state and the counters "anls_W_exchanges" / "anls_H_exchanges" / "anls_backup" / "anls_capped"
+void anls_free(cmf_handle_s *h);
+int anls_counter(const cmf_handle_s *h, const char *name, int64_t *value);
 
 #define HALS_PMAX 4 // puller workgroups per row of the persistent H pipeline (4 -> 7 measured the same span: profiles/r04_hals_pullers_sweep.txt)
 

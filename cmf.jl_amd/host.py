@@ -672,6 +672,112 @@ class ADMMUpdate(AbstractCFUpdate):
 HIPADMMUpdate = ADMMUpdate
 
 
+class ANLSUpdate(AbstractCFUpdate):
+    """ANLSUpdate on MI355X: drop-in for src/algs/anls.jl (alternating non-negative least squares), computed in fp64 end to end.
+
+    ``ANLSUpdate(data, W, H)`` mirrors anls.jl:10-14: it uploads ``data`` in fp64 and keeps its norm (cmf_anls_prepare).  Nothing
+    of W or H stays on the device between calls: ``update_motifs`` reads H from the caller's array and overwrites W with the exact
+    minimiser over W >= 0; ``update_feature_maps`` reads W and H and overwrites H column by column (``variant=":basic"``) or in L
+    phases of independent columns (``variant=":block"``), as the reference does.  Select it by type (``alg=ANLSUpdate``, what
+    HEAD's fit_cnmf takes, model.jl:60); the name ``":anls"`` is not mapped.
+
+    After a call, ``last_W_exchanges`` / ``last_H_exchanges`` hold the pivoting rounds of the NNLS solver summed over the call's
+    problems (cmf_get_counter "anls_W_exchanges" / "anls_H_exchanges").  One GPU only; K*L <= 128 and K <= 64.
+    """
+
+    last_W_exchanges = last_H_exchanges = 0
+    MAX_T = ADMMUpdate.MAX_T  # columns one contraction launch covers (cmf_anls_prepare refuses more)
+    _VARIANTS = {"basic": 0, "block": 1}
+
+    def __init__(self, data, W, H, device=None, devices=None):
+        if devices is not None:
+            raise NotImplementedError("ANLSUpdate runs on one GPU: devices=[...] (T sharding) is not available for the ANLS rule")
+        lib = _lib.load()
+        self._lib = lib
+        self._h = ctypes.c_void_p()
+        data = farr(data)
+        if data.ndim != 2:
+            raise ValueError("data must be a matrix (N x T)")
+        W = farr(W)
+        if W.ndim != 3:
+            raise ValueError("W must be a K x N x L tensor")
+        K, N, L = W.shape
+        if data.shape[0] != N:
+            raise ValueError(f"DimensionMismatch: data has {data.shape[0]} rows, W has N={N}")
+        T = data.shape[1]
+        farr(H, (K, T))
+        if T > self.MAX_T:  # (cmf_create would cut such a recording into a T-sharded group, which the ANLS rule cannot run on)
+            raise NotImplementedError(f"ANLSUpdate runs on one handle of at most {self.MAX_T} columns (T = {T})")
+        self.N, self.T, self.K, self.L = N, T, K, L
+        self.device = _dev(device)
+        check(lib.cmf_create(ctypes.byref(self._h), self.device, N, T, K, L, ptr(data)))
+        try:
+            check(lib.cmf_anls_prepare(self._h, ptr(data)))
+        except Exception:
+            self.close()
+            raise
+        self.data_norm = float(np.linalg.norm(data))  # anls.jl:12
+
+    @classmethod
+    def _variant(cls, variant):
+        name = variant.lstrip(":") if isinstance(variant, str) else variant
+        if name not in cls._VARIANTS:
+            raise ValueError(f"variant must be ':basic' or ':block', got {variant!r}")
+        return cls._VARIANTS[name]
+
+    def update_motifs(self, data, W, H, variant=":basic", **kwargs):
+        """update_motifs!(rule::ANLSUpdate, data, W, H; kwargs...): anls.jl:22-24, :47-57.  Reads H, overwrites W.  (`variant`
+        belongs to update_feature_maps; fit hands every keyword to both calls.)"""
+        Hin = farr(H, (self.K, self.T))
+        Wout = ADMMUpdate._out(W, (self.K, self.N, self.L))
+        try:
+            check(self._lib.cmf_anls_update_motifs(self._h, ptr(Hin), ptr(Wout)))
+        finally:
+            self.last_W_exchanges = self.counter("anls_W_exchanges")
+        if Wout is not W:
+            W[...] = Wout
+
+    def update_feature_maps(self, data, W, H, variant=":basic", **kwargs):
+        """update_feature_maps!(rule::ANLSUpdate, data, W, H; variant=:basic) -> loss: anls.jl:26-36, :63-137.  Reads W and H,
+        overwrites H."""
+        code = self._variant(variant)
+        Win = farr(W, (self.K, self.N, self.L))
+        Hout = ADMMUpdate._out(H, (self.K, self.T))
+        loss = ctypes.c_double()
+        try:
+            check(self._lib.cmf_anls_update_feature_maps(self._h, ptr(Win), ptr(Hout), code, ctypes.byref(loss)))
+        finally:
+            self.last_H_exchanges = self.counter("anls_H_exchanges")
+        if Hout is not H:
+            H[...] = Hout
+        return loss.value
+
+    def counter(self, name):
+        v = ctypes.c_int64()
+        check(self._lib.cmf_get_counter(self._h, name.encode(), ctypes.byref(v)))
+        return v.value
+
+    def set_option(self, name, value):
+        if name != "anls_backup_only":
+            raise NotImplementedError(f"ANLSUpdate has one library option, 'anls_backup_only' (got {name!r}): the other names of "
+                                      "cmf_set_option select paths of the other rules")
+        check(self._lib.cmf_set_option(self._h, name.encode(), int(value)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.cmf_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+HIPANLSUpdate = ANLSUpdate
+
+
 def _resolve_alg(alg):
     """alg may be a rule type (HEAD, model.jl:60) or a README-style symbol (README.md:30-33)."""
     if isinstance(alg, str):
@@ -684,8 +790,10 @@ def _resolve_alg(alg):
             return PGDUpdate
         if name == "admm":
             return ADMMUpdate
-        if name in ("anls", "sep"):
-            raise NotImplementedError(f"alg=:{name} is outside the MI355X hot path built here (:mult, :hals, :pgd, :admm)")
+        if name == "anls":
+            raise NotImplementedError("alg=:anls is not mapped as a name: select the ANLS rule by type, alg=ANLSUpdate (model.jl:60)")
+        if name == "sep":
+            raise NotImplementedError(f"alg=:{name} is outside the MI355X hot path built here (:mult, :hals, :pgd, :admm, ANLSUpdate)")
         raise ValueError(f"unknown algorithm {alg!r}")
     if isinstance(alg, type) and issubclass(alg, AbstractCFUpdate):
         return alg
@@ -757,7 +865,8 @@ _REG_ALIASES = {"l1_W": "l1W", "l2_W": "l2W", "l1_H": "l1H", "l2_H": "l2H"}  # R
 _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_mode", "tol", "verbose",
              "l1W", "l2W", "l1H", "l2H", "device", "devices", "options",
              "loss_func", "constrW", "constrH", "penaltiesW", "penaltiesH",  # PGDUpdate (pgd.jl:158-202)
-             "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH"}  # ADMMUpdate (admm.jl:24-27,124-127)
+             "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH",  # ADMMUpdate (admm.jl:24-27,124-127)
+             "variant"}  # ANLSUpdate (anls.jl:26)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -808,12 +917,14 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
 
     if devices is not None and rule_type is ADMMUpdate:
         raise NotImplementedError("devices=[...] (T sharding) is not available for alg=:admm: the ADMM rule runs on one GPU")
+    if devices is not None and rule_type is ANLSUpdate:
+        raise NotImplementedError("devices=[...] (T sharding) is not available for alg=ANLSUpdate: the ANLS rule runs on one GPU")
     if devices is not None and rule_type not in (MultUpdate, PGDUpdate):
         raise NotImplementedError("devices=[...] (T sharding) is available for alg=:mult and :pgd; HALS sweeps H sequentially along T")
     if devices is not None:
         rule = rule_type(data, W_init, H_init, devices=devices)
     else:
-        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, (MultUpdate, ADMMUpdate))
+        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, (MultUpdate, ADMMUpdate, ANLSUpdate))
                 else rule_type(data, W_init, H_init))
     try:
         for name, value in (options or {}).items():

@@ -373,6 +373,53 @@ function update_feature_maps!(rule::HIPADMMUpdate, data, W, H; rhoh=10, admm_H_m
 end
 
 """
+    HIPANLSUpdate(data, W, H; device=LOCAL_RANK or 0)
+
+Drop-in for `ANLSUpdate(data, W, H)` (src/algs/anls.jl:10-14), computed in fp64 on one GPU, on the K x N x L layout of W.  Not in
+`ALGORITHMS`: select it by type (`fit_cnmf(data; alg=HIPANLSUpdate, variant=:block)`, model.jl:60).  `update_motifs!` reads H and
+overwrites W with the exact minimiser over W >= 0; `update_feature_maps!` overwrites H column by column (`variant=:basic`) or in
+L phases of independent columns (`variant=:block`).  K*L <= 128, K <= 64.
+"""
+mutable struct HIPANLSUpdate <: AbstractCFUpdate
+    handle::Ptr{Cvoid}
+end
+function HIPANLSUpdate(data, W, H; device::Integer=parse(Int, get(ENV, "LOCAL_RANK", "0")))
+    K, N, L = size(W)
+    T = size(data, 2)
+    size(data, 1) == N || throw(DimensionMismatch("data has $(size(data,1)) rows, W has N=$N"))
+    size(H) == (K, T) || throw(DimensionMismatch("H must be $K x $T"))
+    d = Matrix{Float64}(data)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:cmf_create, LIBCMF), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64, Int64, Ptr{Float64}),
+                h, device, N, T, K, L, d))
+    rule = HIPANLSUpdate(h[])
+    finalizer(r -> (r.handle != C_NULL && ccall((:cmf_destroy, LIBCMF), Cint, (Ptr{Cvoid},), r.handle); r.handle = C_NULL), rule)
+    check(ccall((:cmf_anls_prepare, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), rule.handle, d))
+    return rule
+end
+
+# update_motifs!(rule::ANLSUpdate, data, W, H; kwargs...)  -- src/algs/anls.jl:22-24, :47-57
+function update_motifs!(rule::HIPANLSUpdate, data, W, H; kwargs...)
+    Hc = Matrix{Float64}(H)
+    Wc = W isa Array{Float64,3} ? W : Array{Float64,3}(W)
+    check(ccall((:cmf_anls_update_motifs, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), rule.handle, Hc, Wc))
+    Wc === W || (W .= Wc)
+    return W
+end
+
+# update_feature_maps!(rule::ANLSUpdate, data, W, H; variant=:basic, kwargs...) -> loss  -- src/algs/anls.jl:26-36, :63-137
+function update_feature_maps!(rule::HIPANLSUpdate, data, W, H; variant=:basic, kwargs...)
+    variant in (:basic, :block) || throw(ArgumentError("variant must be :basic or :block, got $variant"))
+    Wc = Array{Float64,3}(W)
+    Hc = H isa Matrix{Float64} ? H : Matrix{Float64}(H)
+    loss = Ref{Float64}(0.0)
+    check(ccall((:cmf_anls_update_feature_maps, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Float64}),
+                rule.handle, Wc, Hc, variant == :block ? 1 : 0, loss))
+    Hc === H || (H .= Hc)
+    return loss[]
+end
+
+"""
     iterate!(rule, n; l1W=0, l2W=0, l1H=0, l2H=0, eval_mode=false) -> losses
 
 `n` x (`update_motifs!`; `update_feature_maps!`) back to back (alternating.jl:51-54) in one ccall (`cmf_iterate`): the

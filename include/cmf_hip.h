@@ -67,7 +67,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_admm.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_admm.h, cmf_anls.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -434,6 +434,43 @@ int cmf_admm_update_motifs(cmf_handle h, const double *H, double *W, double rhow
  * K <= 64 (CMF_ERR_UNSUPPORTED).  *iters (may be NULL) receives the inner iterations run. */
 int cmf_admm_update_feature_maps(cmf_handle h, const double *W, double *H, double rhoh, int64_t maxiter, double l1H, double tol,
                                  int nonnegH, double *loss, int64_t *iters);
+
+/* ---- ANLS rule ----------------------------------------------------------------------------------------------------------
+ * Alternating non-negative least squares (src/algs/anls.jl), computed in fp64 end to end, restated on the K x N x L layout of W
+ * (anls.jl is written for the old L x N x K one): every half step is the exact minimiser of its block.  The NNLS solver is block
+ * principal pivoting on the normal equations with tol = 1e-5 (NNLS_TOL, anls.jl:18), which stands for nonneg_lsq(...; alg=:pivot)
+ * of the reference; DESIGN.md, "The ANLS rule", says what is assumed about that package.  Like the ADMM entries these take the
+ * caller's arrays in and out -- each call reads the factor the reference reads and overwrites the other in place -- keep nothing
+ * of the factors on the device between calls, and stay clear of cmf_set_factors / cmf_arm_writeback.  Single-GPU handles only: a
+ * handle that fronts a T-sharded group gets CMF_ERR_UNSUPPORTED.
+ *
+ * A problem whose passive-set Gram is not positive definite (rank-deficient or non-finite input), or that reaches the cap on
+ * pivoting rounds (5 n + 10 for n unknowns; 50 n + 50 under "anls_backup_only"), ends the call with CMF_ERR_UNSUPPORTED and a
+ * message; the caller's output factor is then untouched.  An all-zero stacked row of H or component of W is no such case: its
+ * unknowns stay zero.
+ *
+ * cmf_set_option(h, "anls_backup_only", 1): every exchange of every problem moves only the infeasible index of largest number
+ * (the solver's backup rule, i.e. plain principal pivoting): the same answer in more rounds.  It is the rule's only option and
+ * exists so that a test can walk the backup path; it selects no path of the other rules and cmf_option_names does not list it.
+ * cmf_get_counter: "anls_W_exchanges" / "anls_H_exchanges" = pivoting rounds summed over the problems of the last call of that
+ * kind; "anls_backup" = problems of the last call that took the backup rule; "anls_capped" = problems of the last call that hit
+ * the cap.
+ *
+ * ANLSUpdate(data, W, H) (src/algs/anls.jl:10-14): uploads `data` (N x T, fp64) and keeps norm(data); allocates the rule's fp64
+ * state on the handle's device.  (The residual the constructor forms is recomputed by every update_feature_maps!, anls.jl:27.) */
+int cmf_anls_prepare(cmf_handle h, const double *data);
+/* update_motifs!(rule::ANLSUpdate, data, W, H)  src/algs/anls.jl:22-24, :47-57.  Reads H (K x T) only and overwrites W (K x N x L)
+ * with argmin_{W >= 0} |data - conv(W, H)|: N independent problems of K*L unknowns on G = Hstk*Hstk', C = Hstk*data', one
+ * workgroup each, the passive-set Gram factorised in LDS.  K*L <= 128 (CMF_ERR_UNSUPPORTED beyond: nothing runs through global
+ * scratch). */
+int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W);
+/* update_feature_maps!(rule::ANLSUpdate, data, W, H; variant=:basic) -> loss  src/algs/anls.jl:26-36, :63-137.  Reads W and H,
+ * overwrites H; *loss (may be NULL) = norm(conv(W, H) - data) / norm(data) of the new H (anls.jl:35).  variant 0 (:basic,
+ * anls.jl:63-94): the columns t = 1..T in order, each the exact minimiser over H[:, t] >= 0 given the others -- one workgroup
+ * walks T.  variant 1 (:block, anls.jl:101-137): L phases of columns l, l+L, ... <= T-L+1 solved side by side, then the last L-1
+ * columns in order; needs T >= L (CMF_ERR_ARG: the reference indexes T-L+2:T).  Any other variant is CMF_ERR_ARG.  K <= 64 and
+ * (L-1)*K <= 6144 (CMF_ERR_UNSUPPORTED). */
+int cmf_anls_update_feature_maps(cmf_handle h, const double *W, double *H, int variant, double *loss);
 
 /* converged(loss_hist, patience, tol): src/model.jl:91-107 (host arithmetic). */
 int cmf_converged(const double *loss_hist, int64_t len, int64_t patience, double tol);
