@@ -1,9 +1,6 @@
 #pragma once
 // cmf_admm.h -- gfx950 kernels of the ADMM rule (src/algs/admm.jl), all in fp64 ("The ADMM rule").
 //
-//   admm_gemm_kernel     the contractions: C[m, p] = sum_r A(m, r) B(r, p) for element loaders A, B that address the factors in
-//                        place (the stacked Hstk of common.jl:133-142, the lagged / circularly wrapped H and data columns), with a
-//                        fused element-wise epilogue (Z / dual updates, squared residuals of the loss).  64 x 64 tiles, 4 x 4 per thread.
 //   admm_chol_kernel     the LK x LK Cholesky of G = Hstk*Hstk' + 2I (one workgroup, right-looking, in place; once per W call)
 //   admm_trsm_kernel     G \ rhs against N right-hand sides: one wave per column, the column in LDS, no explicit inverse
 //   admm_lag_gram_kernel the 2L-1 lag matrices A(d) of the H solve
@@ -12,41 +9,18 @@
 //   admm_fft_*           Bluestein over a radix-2 Stockham FFT of power-of-two length: one path for every T
 //   admm_w_cols_kernel   W side steps 4-6 on the stacked columns (norm rule w[n] >= 1, projection, duals U2 / U3)
 //   admm_h_aux_kernel    H side steps 3-4 (soft threshold, projection); admm_h_dual_kernel the duals Q2 / Q3
-//   admm_sum_kernel      the loss partials of a contraction, summed in a fixed order
-// The kernels are static: cmf_anls.h includes this header too, for the contraction kernel and its loaders.
+// The contractions are fp64_gemm_kernel of cmf_fp64.h, with its loaders and epilogues and the ones below (the differences of
+// two arrays, the circularly wrapped H and data columns, the Z / dual updates).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "cmf_fp64.h"
 
 namespace admm {
 
-constexpr int TM = 64, TP = 64, TR = 16;
-
-// ---- element loaders (A: m x r, B: r x p) --------------------------------------------------------------------------------------
-// Hstk[i, t] = H[k, t - l] (i = l*K + k, zero for t < l); H is row-major [k][t] on the device
-struct HstkRT { // A(i, t): m = stacked row, r = time
-    const double *H; int K, T;
-    __device__ double operator()(int64_t i, int64_t t) const { int l = (int)(i / K), k = (int)(i % K); return t >= l ? H[(int64_t)k * T + t - l] : 0.0; }
-};
-struct HstkTR { // A(t, i) or B(t, j) with the stacked row as the second index
-    const double *H; int K, T;
-    __device__ double operator()(int64_t t, int64_t i) const { int l = (int)(i / K), k = (int)(i % K); return t >= l ? H[(int64_t)k * T + t - l] : 0.0; }
-};
-struct RowMajor { // M[r][p] with row stride ld
-    const double *X; int64_t ld;
-    __device__ double operator()(int64_t r, int64_t p) const { return X[r * ld + p]; }
-};
+// ---- element loaders for fp64_gemm_kernel (A: m x r, B: r x p) -------------------------------------------------------------------
 struct RowMajorDiff { // X[r][p] - Y[r][p]
     const double *X, *Y; int64_t ld;
     __device__ double operator()(int64_t r, int64_t p) const { return X[r * ld + p] - Y[r * ld + p]; }
-};
-// W in Julia's layout W[k + K*(n + N*l)]
-struct WkR { // A(k, r) with r = n + N*l
-    const double *W; int K;
-    __device__ double operator()(int64_t k, int64_t r) const { return W[k + (int64_t)K * r]; }
-};
-struct WnR { // A(n, r) with r = k + K*l
-    const double *W; int K, N;
-    __device__ double operator()(int64_t n, int64_t r) const { int l = (int)(r / K), k = (int)(r % K); return W[k + (int64_t)K * (n + (int64_t)N * l)]; }
 };
 // B(r, s) = X[n, (s + l) mod T] - Y[n, ...] with r = n + N*l, X / Y in data's layout [t][n]
 struct ShiftColsDiff {
@@ -72,10 +46,6 @@ struct LagH {
 };
 
 // ---- epilogues: called once per output element; the return value is added to the loss partial ---------------------------------
-struct EpiStore { // C[m][p] (row stride ld) = acc + (diag ? add_diag : 0)
-    double *C; int64_t ld; double add_diag;
-    __device__ double operator()(int64_t m, int64_t p, double acc) const { C[m * ld + p] = acc + (m == p ? add_diag : 0.0); return 0.0; }
-};
 struct EpiRhsW { // rhs[i][n] = acc + Z2 - U2 + Z3 - U3   (admm.jl:63-65)
     double *out; const double *Z2, *U2, *Z3, *U3; int64_t ld;
     __device__ double operator()(int64_t i, int64_t n, double acc) const {
@@ -99,10 +69,6 @@ struct EpiLossT { // (data'[t][n] - acc)^2   (admm.jl:93-96)
     const double *data; int64_t N;
     __device__ double operator()(int64_t t, int64_t n, double acc) const { double r = data[t * N + n] - acc; return r * r; }
 };
-struct EpiLossN { // (acc - data[n, t])^2   (admm.jl:199-200, 225)
-    const double *data; int64_t N;
-    __device__ double operator()(int64_t n, int64_t t, double acc) const { double r = acc - data[t * N + n]; return r * r; }
-};
 struct EpiRhsH { // y[k][s] = acc + (Z2 - Q2) + (Z3 - Q3): the real input of the forward FFT (admm.jl:180-182, by linearity)
     double *y; const double *Z2, *Q2, *Z3, *Q3; int64_t T;
     __device__ double operator()(int64_t k, int64_t s, double acc) const {
@@ -120,76 +86,6 @@ struct EpiZ1H { // est[n, t] = acc (kept for the dual update); Z1 = c1*((est+Q1)
         return 0.0;
     }
 };
-
-// A_MFAST / B_PFAST: which index of the loader is contiguous in memory, so that a wave's tile loads run along it
-template <class AL, class BL, class EP, bool A_MFAST, bool B_PFAST>
-static __global__ __launch_bounds__(256) void admm_gemm_kernel(AL A, BL B, EP E, int64_t M, int64_t P, int64_t R, double *partial)
-{
-    __shared__ double As[TR][TM + 1];
-    __shared__ double Bs[TR][TP + 1];
-    __shared__ double red[256];
-    const int tid = threadIdx.x, tm = tid % 16, tp = tid / 16;
-    const int64_t m0 = (int64_t)blockIdx.x * TM, p0 = (int64_t)blockIdx.y * TP;
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-    for (int64_t r0 = 0; r0 < R; r0 += TR) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = tid + 256 * q;
-            const int mm = A_MFAST ? idx % TM : idx / TR, ra = A_MFAST ? idx / TM : idx % TR;
-            As[ra][mm] = (m0 + mm < M && r0 + ra < R) ? A(m0 + mm, r0 + ra) : 0.0;
-            const int pp = B_PFAST ? idx % TP : idx / TR, rb = B_PFAST ? idx / TP : idx % TR;
-            Bs[rb][pp] = (p0 + pp < P && r0 + rb < R) ? B(r0 + rb, p0 + pp) : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int rr = 0; rr < TR; ++rr) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { av[q] = As[rr][tm + 16 * q]; bv[q] = Bs[rr][tp + 16 * q]; }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = fma(av[a], bv[b], acc[a][b]);
-        }
-        __syncthreads();
-    }
-    double part = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int64_t m = m0 + tm + 16 * a, p = p0 + tp + 16 * b;
-            if (m < M && p < P) part += E(m, p, acc[a][b]);
-        }
-    if (partial) {
-        red[tid] = part;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        if (tid == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-    }
-}
-
-// sum of n partials into out[0], one workgroup, fixed order (deterministic)
-static __global__ __launch_bounds__(256) void admm_sum_kernel(const double *partial, int64_t n, double *out)
-{
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
 
 // ---- W side: Cholesky of the LK x LK Gram and the triangular solves ------------------------------------------------------------
 // In place on G (row-major, lower triangle used); writes the factor's transpose to Lt for the backward solve.

@@ -1,68 +1,38 @@
 // cmf_admm.hip -- the ADMM rule (src/algs/admm.jl) on one device, in fp64 end to end: cmf_admm_prepare,
-// cmf_admm_update_motifs, cmf_admm_update_feature_maps (include/cmf_hip.h).  The kernels are in cmf_admm.h; the rewritings that
-// keep the K x N x T tensor `wh` and the T Gram products of the reference out of the computation are in DESIGN.md, "The ADMM rule".
+// cmf_admm_update_motifs, cmf_admm_update_feature_maps (include/cmf_hip.h).  The kernels are in cmf_admm.h, the contraction and
+// the part of the state that the ANLS rule has too in cmf_fp64.h; the rewritings that keep the K x N x T tensor `wh` and the T
+// Gram products of the reference out of the computation are in DESIGN.md, "The ADMM rule".
 #include "cmf_internal.h"
 #include "cmf_admm.h"
 
+using namespace fp64;
 using namespace admm;
 
-struct AdmmState {
-    int64_t N = 0, T = 0, K = 0, L = 0, LK = 0;
+static const char RULE[] = "ADMM";
+
+struct AdmmState : Fp64State { // Hd: K x T row-major, the H the W call reads
     int64_t F = 0;  // frequencies solved: 0..T/2 (the spectrum of real rows is Hermitian)
     int64_t M = 1;  // Bluestein length: a power of two >= 2T-1
-    double datanorm = 0.0;
-    double *data = nullptr;                          // N x T, data[n + N*t] (= data' row-major)
     double *Z1 = nullptr, *D1 = nullptr, *est = nullptr; // N x T: Z1, its dual (U1' / Q1), est (H side)
-    double *Hd = nullptr;                            // K x T row-major: the H the W call reads
     double *G = nullptr, *Gt = nullptr;              // LK x LK: Cholesky factor of Hstk*Hstk' + 2I and its transpose
     double *Wstk = nullptr, *Z2w = nullptr, *Z3w[2] = {nullptr, nullptr}, *U2 = nullptr, *U3 = nullptr; // LK x N, [i][n]
-    double *Wd = nullptr;                            // K x N x L, Julia's layout: the W the H call reads
     double *Hh = nullptr, *Z2h = nullptr, *Z3h[2] = {nullptr, nullptr}, *Q2 = nullptr, *Q3 = nullptr, *yr = nullptr; // K x T row-major
     double2 *Y = nullptr;                            // K x T complex
     double2 *fa = nullptr, *fb = nullptr;            // K x M complex: Bluestein work
     double2 *chirp = nullptr, *bh = nullptr;         // T, M
     double *Alag = nullptr;                          // (2L-1) x K x K
     double2 *Lf = nullptr;                           // K x K x F: the per-frequency factors
-    double *partial = nullptr, *dsum = nullptr, *hsum = nullptr;
-    int64_t npartial = 0;
+    double *hsum = nullptr;                          // pinned: the loss sum read back
     int64_t w_reverts = 0, h_reverts = 0;            // of the last call of each kind
-    std::vector<void *> owned;
 };
 
 void admm_free(cmf_handle_s *h)
 {
     if (!h || !h->admm) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->admm->owned) (void)hipFree(p);
+    fp64_release(h, h->admm);
     if (h->admm->hsum) (void)hipHostFree(h->admm->hsum);
     delete h->admm;
     h->admm = nullptr;
-}
-
-template <typename T>
-static int aalloc(AdmmState *s, T **p, size_t n)
-{
-    HIPCHK(hipMalloc(p, std::max<size_t>(n, 1) * sizeof(T)));
-    s->owned.push_back(*p);
-    return CMF_OK;
-}
-
-static int64_t blocks(int64_t n, int64_t b) { return (n + b - 1) / b; }
-
-template <bool AMF, bool BPF, class AL, class BL, class EP>
-static int gemm(AdmmState *s, hipStream_t st, AL a, BL b, EP e, int64_t M, int64_t P, int64_t R, bool loss)
-{
-    const dim3 grid((unsigned)blocks(M, TM), (unsigned)blocks(P, TP));
-    if (grid.y > 65535) return fail(CMF_ERR_UNSUPPORTED, "ADMM: a contraction of %lld columns is beyond one launch", (long long)P);
-    if (loss && (int64_t)grid.x * grid.y > s->npartial) return fail(CMF_ERR_STATE, "internal: ADMM loss partial buffer too small");
-    hipLaunchKernelGGL((admm_gemm_kernel<AL, BL, EP, AMF, BPF>), grid, dim3(256), 0, st, a, b, e, M, P, R, loss ? s->partial : nullptr);
-    KCHK("admm_gemm_kernel");
-    if (loss) {
-        hipLaunchKernelGGL(admm_sum_kernel, dim3(1), dim3(256), 0, st, s->partial, (int64_t)grid.x * grid.y, s->dsum);
-        KCHK("admm_sum_kernel");
-    }
-    return CMF_OK;
 }
 
 // the sum the last loss contraction left in dsum, as norm / datanorm
@@ -109,8 +79,7 @@ static int dft_rows(AdmmState *s, hipStream_t st, const void *x, void *out, doub
 static int admm_state(cmf_handle h, AdmmState **out)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the ADMM rule runs on a single-GPU handle only (this one fronts a T-sharded group)");
+    CMFTRY(fp64_single_gpu(h, RULE, false));
     if (!h->admm) return fail(CMF_ERR_STATE, "call cmf_admm_prepare before the ADMM rule entries");
     *out = h->admm;
     HIPCHK(hipSetDevice(h->device));
@@ -120,9 +89,7 @@ static int admm_state(cmf_handle h, AdmmState **out)
 int cmf_admm_prepare(cmf_handle h, const double *data)
 {
     if (!h || !data) return fail(CMF_ERR_ARG, "NULL argument");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the ADMM rule runs on a single-GPU handle of at most %lld columns only (this one fronts a T-sharded "
-                                         "group: cmf_create_multi / cmf_create_shard, or cmf_create of a longer recording)", (long long)65535 * TP);
+    CMFTRY(fp64_single_gpu(h, RULE, true));
     const int64_t N = h->d.N, T = h->d.Tl, K = h->d.K, L = h->d.L;
     if (L * K > 8192) return fail(CMF_ERR_UNSUPPORTED, "ADMM: L*K = %lld > 8192 (the stacked solve keeps a column of L*K in LDS)", (long long)(L * K));
     if (T > (int64_t)65535 * TP) return fail(CMF_ERR_UNSUPPORTED, "ADMM: T = %lld > %lld", (long long)T, (long long)65535 * TP);
@@ -131,37 +98,28 @@ int cmf_admm_prepare(cmf_handle h, const double *data)
     auto *s = new AdmmState();
     h->admm = s;
     auto bail = [&](int rc) { admm_free(h); return rc; };
-    s->N = N; s->T = T; s->K = K; s->L = L; s->LK = L * K;
+    int rc = fp64_prepare_common(h, s, data);
+    if (rc != CMF_OK) return bail(rc);
     s->F = T / 2 + 1;
     while (s->M < 2 * T - 1) s->M <<= 1;
     const size_t NT = (size_t)N * T, KT = (size_t)K * T, LKN = (size_t)s->LK * N;
-    s->npartial = blocks(T, 64) * blocks(N, 64);
-    int rc = CMF_OK;
-    for (double **p : {&s->data, &s->Z1, &s->D1, &s->est})
-        if (rc == CMF_OK) rc = aalloc(s, p, NT);
+    for (double **p : {&s->Z1, &s->D1, &s->est})
+        if (rc == CMF_OK) rc = fp64_alloc(s, p, NT);
     for (double **p : {&s->Wstk, &s->Z2w, &s->Z3w[0], &s->Z3w[1], &s->U2, &s->U3})
-        if (rc == CMF_OK) rc = aalloc(s, p, LKN);
-    for (double **p : {&s->Hd, &s->Hh, &s->Z2h, &s->Z3h[0], &s->Z3h[1], &s->Q2, &s->Q3, &s->yr})
-        if (rc == CMF_OK) rc = aalloc(s, p, KT);
-    if (rc == CMF_OK) rc = aalloc(s, &s->G, (size_t)s->LK * s->LK);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Gt, (size_t)s->LK * s->LK);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Wd, (size_t)K * N * L);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Y, KT);
-    if (rc == CMF_OK) rc = aalloc(s, &s->fa, (size_t)K * s->M);
-    if (rc == CMF_OK) rc = aalloc(s, &s->fb, (size_t)K * s->M);
-    if (rc == CMF_OK) rc = aalloc(s, &s->chirp, (size_t)T);
-    if (rc == CMF_OK) rc = aalloc(s, &s->bh, (size_t)s->M);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Alag, (size_t)(2 * L - 1) * K * K);
-    if (rc == CMF_OK && K <= 64) rc = aalloc(s, &s->Lf, (size_t)K * K * s->F);
-    if (rc == CMF_OK) rc = aalloc(s, &s->partial, (size_t)s->npartial);
-    if (rc == CMF_OK) rc = aalloc(s, &s->dsum, 1);
+        if (rc == CMF_OK) rc = fp64_alloc(s, p, LKN);
+    for (double **p : {&s->Hh, &s->Z2h, &s->Z3h[0], &s->Z3h[1], &s->Q2, &s->Q3, &s->yr})
+        if (rc == CMF_OK) rc = fp64_alloc(s, p, KT);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->G, (size_t)s->LK * s->LK);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->Gt, (size_t)s->LK * s->LK);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->Y, KT);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->fa, (size_t)K * s->M);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->fb, (size_t)K * s->M);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->chirp, (size_t)T);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->bh, (size_t)s->M);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->Alag, (size_t)(2 * L - 1) * K * K);
+    if (rc == CMF_OK && K <= 64) rc = fp64_alloc(s, &s->Lf, (size_t)K * K * s->F);
     if (rc != CMF_OK) return bail(rc);
     if (hipHostMalloc(&s->hsum, sizeof(double)) != hipSuccess) return bail(fail(CMF_ERR_HIP, "hipHostMalloc failed"));
-    // data (admm.jl:13-21: the constructor keeps norm(data))
-    double ss = 0.0;
-    for (size_t i = 0; i < NT; ++i) ss += data[i] * data[i];
-    s->datanorm = std::sqrt(ss);
-    if (hipMemcpy(s->data, data, NT * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(CMF_ERR_HIP, "data upload failed"));
     // Bluestein chirp and the transform of its conjugate (depend on T only)
     hipStream_t st = h->stream;
     hipLaunchKernelGGL(admm_chirp_kernel, dim3((unsigned)blocks(s->M, 256)), dim3(256), 0, st, s->chirp, s->bh, T, s->M);
@@ -205,18 +163,15 @@ int cmf_admm_update_motifs(cmf_handle h, const double *H, double *W, double rhow
     if (maxiter < 0) return fail(CMF_ERR_ARG, "admm_W_maxiter < 0");
     const int64_t N = s->N, T = s->T, K = s->K, L = s->L, LK = s->LK;
     hipStream_t st = h->stream;
-    // H (K x T, Julia's layout) -> [k][t]
-    std::vector<double> Hr((size_t)K * T);
-    for (int64_t t = 0; t < T; ++t)
-        for (int64_t k = 0; k < K; ++k) Hr[(size_t)k * T + t] = H[k + K * t];
-    HIPCHK(hipMemcpyAsync(s->Hd, Hr.data(), Hr.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    std::vector<double> Hr;
+    CMFTRY(fp64_upload_H_rows(s, st, H, Hr));
     const size_t NT = (size_t)N * T, LKN = (size_t)LK * N;
     for (double *p : {s->Z1, s->D1}) HIPCHK(hipMemsetAsync(p, 0, NT * sizeof(double), st)); // admm.jl:36-48: everything starts at zero
     for (double *p : {s->Wstk, s->Z2w, s->Z3w[0], s->Z3w[1], s->U2, s->U3}) HIPCHK(hipMemsetAsync(p, 0, LKN * sizeof(double), st));
     // G = Hstk*Hstk' + 2I, factorised once per call (:51-53)
     const HstkRT hs{s->Hd, (int)K, (int)T};
     const HstkTR hst{s->Hd, (int)K, (int)T};
-    CMFTRY((gemm<false, false>(s, st, hs, hst, EpiStore{s->G, LK, 2.0}, LK, LK, T, false)));
+    CMFTRY((fp64_gemm<false, false>(s, st, RULE, hs, hst, EpiStore{s->G, LK, 2.0}, LK, LK, T, false)));
     hipLaunchKernelGGL(admm_chol_kernel, dim3(1), dim3(1024), 0, st, s->G, s->Gt, (int)LK);
     KCHK("admm_chol_kernel");
     const double c1 = 1.0 / (1.0 + 1.0 / rhow), c2 = 1.0 / rhow;
@@ -226,18 +181,18 @@ int cmf_admm_update_motifs(cmf_handle h, const double *H, double *W, double rhow
     while (it < maxiter) {
         ++it;
         // 1. Wstk = G \ (Hstk*(Z1-U1) + Z2-U2 + Z3-U3)   (:63-65)
-        CMFTRY((gemm<false, true>(s, st, hs, RowMajorDiff{s->Z1, s->D1, N}, EpiRhsW{s->Wstk, s->Z2w, s->U2, s->Z3w[cur], s->U3, N}, LK, N, T, false)));
+        CMFTRY((fp64_gemm<false, true>(s, st, RULE, hs, RowMajorDiff{s->Z1, s->D1, N}, EpiRhsW{s->Wstk, s->Z2w, s->U2, s->Z3w[cur], s->U3, N}, LK, N, T, false)));
         hipLaunchKernelGGL(admm_trsm_kernel, dim3((unsigned)N), dim3(64), LK * sizeof(double), st, s->G, s->Gt, s->Wstk, (int)LK, N);
         KCHK("admm_trsm_kernel");
         // 2-3. estT = Hstk'*Wstk; Z1 = c1*((estT+U1) + c2*data'); U1 += estT - Z1   (:68-69, 89)
-        CMFTRY((gemm<true, true>(s, st, hst, RowMajor{s->Wstk, N}, EpiZ1W{s->Z1, s->D1, s->data, N, c1, c2}, T, N, LK, false)));
+        CMFTRY((fp64_gemm<true, true>(s, st, RULE, hst, RowMajor{s->Wstk, N}, EpiZ1W{s->Z1, s->D1, s->data, N, c1, c2}, T, N, LK, false)));
         // 4-6. column norms with the w[n] >= 1 rule, Z3 = max(0, Wstk+U3) into Z3_last's buffer, U2, U3   (:72-91)
         hipLaunchKernelGGL(admm_w_cols_kernel, dim3((unsigned)blocks(N, 256)), dim3(256), 0, st, s->Wstk, s->Z2w, s->U2, s->Z3w[cur ^ 1], s->U3,
                            (int)LK, N, nonnegW ? 1 : 0);
         KCHK("admm_w_cols_kernel");
         cur ^= 1;
         // 7. loss = norm(data' - Hstk'*Z3) / norm(data)   (:93-96)
-        CMFTRY((gemm<true, true>(s, st, hst, RowMajor{s->Z3w[cur], N}, EpiLossT{s->data, N}, T, N, LK, true)));
+        CMFTRY((fp64_gemm<true, true>(s, st, RULE, hst, RowMajor{s->Z3w[cur], N}, EpiLossT{s->data, N}, T, N, LK, true)));
         double loss = 0.0;
         CMFTRY(read_loss(s, st, &loss));
         bool revert = false;
@@ -249,9 +204,7 @@ int cmf_admm_update_motifs(cmf_handle h, const double *H, double *W, double rhow
     std::vector<double> Z((size_t)LK * N);
     HIPCHK(hipMemcpyAsync(Z.data(), s->Z3w[cur], Z.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int64_t l = 0; l < L; ++l)
-        for (int64_t n = 0; n < N; ++n)
-            for (int64_t k = 0; k < K; ++k) W[k + K * (n + N * l)] = Z[(size_t)(l * K + k) * N + n];
+    fp64_fold_W(Z.data(), W, K, N, L);
     s->w_reverts = reverts;
     if (iters) *iters = it;
     return CMF_OK;
@@ -287,21 +240,21 @@ int cmf_admm_update_feature_maps(cmf_handle h, const double *W, double *H, doubl
     while (it < maxiter) {
         ++it;
         // 1. H = real(ifft(Gram_f \ fft(circtransconv(W, Z1-Q1) + Z2-Q2 + Z3-Q3)))   (:180-182, fastsolveH! :249-272 with rho = 1)
-        CMFTRY((gemm<true, false>(s, st, wk, ShiftColsDiff{s->Z1, s->D1, (int)N, (int)T},
+        CMFTRY((fp64_gemm<true, false>(s, st, RULE, wk, ShiftColsDiff{s->Z1, s->D1, (int)N, (int)T},
                                   EpiRhsH{s->yr, s->Z2h, s->Q2, s->Z3h[cur], s->Q3, T}, K, T, N * L, false)));
         CMFTRY(dft_rows<false>(s, st, s->yr, s->Y, 1.0));
         hipLaunchKernelGGL(admm_freq_solve_kernel, dim3((unsigned)blocks(s->F, 64)), dim3(64), 0, st, s->Lf, s->Y, (int)K, T, s->F);
         KCHK("admm_freq_solve_kernel");
         CMFTRY(dft_rows<true>(s, st, s->Y, s->Hh, 1.0 / (double)T));
         // 2. est = circular conv(W, H); Z1 = c1*((est+Q1) + c2*data)   (:185-186)
-        CMFTRY((gemm<false, true>(s, st, wn, LagH<true>{s->Hh, (int)K, (int)T}, EpiZ1H{s->est, s->Z1, s->D1, s->data, N, c1, c2}, N, T, K * L, false)));
+        CMFTRY((fp64_gemm<false, true>(s, st, RULE, wn, LagH<true>{s->Hh, (int)K, (int)T}, EpiZ1H{s->est, s->Z1, s->D1, s->data, N, c1, c2}, N, T, K * L, false)));
         // 3-4. Z2 = shrink(H+Q2), Z3 = max(0, H+Q3) into Z3_last's buffer   (:189-197)
         hipLaunchKernelGGL(admm_h_aux_kernel, dim3((unsigned)blocks(KT, 256)), dim3(256), 0, st, s->Hh, s->Q2, s->Q3, s->Z2h, s->Z3h[cur ^ 1], (int64_t)KT,
                            lam, nonnegH ? 1 : 0);
         KCHK("admm_h_aux_kernel");
         cur ^= 1;
         // 5. loss of the linear conv(W, Z3), then revert / break BEFORE the dual update   (:199-211)
-        CMFTRY((gemm<false, true>(s, st, wn, LagH<false>{s->Z3h[cur], (int)K, (int)T}, EpiLossN{s->data, N}, N, T, K * L, true)));
+        CMFTRY((fp64_gemm<false, true>(s, st, RULE, wn, LagH<false>{s->Z3h[cur], (int)K, (int)T}, EpiLossN{s->data, N}, N, T, K * L, true)));
         double l = 0.0;
         CMFTRY(read_loss(s, st, &l));
         bool revert = false;
@@ -314,7 +267,7 @@ int cmf_admm_update_feature_maps(cmf_handle h, const double *W, double *H, doubl
         KCHK("admm_h_dual_kernel");
     }
     // H .= Z3 (:219); the call returns norm(conv(W, H) - data) / norm(data) (:225)
-    CMFTRY((gemm<false, true>(s, st, wn, LagH<false>{s->Z3h[cur], (int)K, (int)T}, EpiLossN{s->data, N}, N, T, K * L, true)));
+    CMFTRY((fp64_gemm<false, true>(s, st, RULE, wn, LagH<false>{s->Z3h[cur], (int)K, (int)T}, EpiLossN{s->data, N}, N, T, K * L, true)));
     double l = 0.0;
     CMFTRY(read_loss(s, st, &l));
     std::vector<double> Hr(KT);

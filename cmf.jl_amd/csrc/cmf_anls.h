@@ -18,12 +18,11 @@
 //                        A one-wave workgroup needs no hardware barrier: __syncthreads() is an LDS fence there.
 //   anls_h_block_kernel  block H step: one wave per column of a phase l, l+L, l+2L, ... (their windows are disjoint).
 //   anls_lag_gram_kernel A_Lt(e) for Lt = 1..L: the full lag-Grams (Lt = L) and the truncated ones of the last L-1 columns
-//   anls_sum_kernel      the loss partials of a contraction, summed in a fixed order
-// The contractions (G, C = Hstk*data', B = transconv(W, data), the loss of conv(W, H)) are admm_gemm_kernel of cmf_admm.h
-// with the loaders below.
+// The contractions (G, C = Hstk*data', B = transconv(W, data), the loss of conv(W, H)) are fp64_gemm_kernel of cmf_fp64.h
+// with its loaders and the ones below.
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "cmf_admm.h"
+#include "cmf_fp64.h"
 
 namespace anls {
 
@@ -36,7 +35,7 @@ enum { ST_ROUNDS = 0, ST_BACKUP = 1, ST_CAPPED = 2, ST_BADPIVOT = 3, ST_N = 4 };
 
 __host__ __device__ inline int anls_round_cap(int n, int backup_only) { return backup_only ? 50 * n + 50 : 5 * n + 10; }
 
-// ---- loaders / epilogues for admm_gemm_kernel ---------------------------------------------------------------------------------
+// ---- loaders / epilogues for fp64_gemm_kernel ---------------------------------------------------------------------------------
 // B(r, s) = data[n, s + l] (r = n + N*l), zero past the end: the linear transconv of the H step; data is [t][n]
 struct ShiftColsLin {
     const double *X; int N; int64_t T;
@@ -58,20 +57,6 @@ struct EpiStoreT { // C[p][m] (row stride ld) = acc
     double *C; int64_t ld;
     __device__ double operator()(int64_t m, int64_t p, double acc) const { C[p * ld + m] = acc; return 0.0; }
 };
-
-static __global__ __launch_bounds__(256) void anls_sum_kernel(const double *partial, int64_t n, double *out)
-{
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
 
 // A[((Lt-1)*(2L-1) + e + L-1)*K*K + k*K + k'] = sum_{l < Lt, 0 <= l-e < L} sum_n W[k, n, l] W[k', n, l-e]; one thread per (e, k, k')
 // walks l upwards and leaves the running sum behind after every l.  W in Julia's layout W[k + K*(n + N*l)].

@@ -1,36 +1,29 @@
 // cmf_anls.hip -- the ANLS rule (src/algs/anls.jl) on one device, in fp64 end to end: cmf_anls_prepare, cmf_anls_update_motifs,
-// cmf_anls_update_feature_maps (include/cmf_hip.h).  The kernels are in cmf_anls.h; the Gram form of the two steps and what is
-// assumed about the reference's NNLS package are in DESIGN.md, "The ANLS rule".
+// cmf_anls_update_feature_maps (include/cmf_hip.h).  The kernels are in cmf_anls.h, the contraction and the part of the state
+// that the ADMM rule has too in cmf_fp64.h; the Gram form of the two steps and what is assumed about the reference's NNLS
+// package are in DESIGN.md, "The ANLS rule".
 #include "cmf_internal.h"
 #include "cmf_anls.h"
 
+using namespace fp64;
 using namespace anls;
 
+static const char RULE[] = "ANLS";
 constexpr double ANLS_TOL = 1e-5; // NNLS_TOL, anls.jl:18
 
-struct AnlsState {
-    int64_t N = 0, T = 0, K = 0, L = 0, LK = 0;
-    double datanorm = 0.0;
-    double *data = nullptr;             // N x T, data[n + N*t]
-    double *Hd = nullptr;               // K x T: [k][t] in the W call (the stacked loaders), Julia's [t][k] in the H call
-    double *Wd = nullptr;               // K x N x L, Julia's layout
+struct AnlsState : Fp64State { // Hd: [k][t] in the W call (the stacked loaders), Julia's [t][k] in the H call
     double *G = nullptr, *C = nullptr, *X = nullptr; // W step: LK x LK, LK x N [i][n] twice
     double *Bt = nullptr;               // H step: transconv(W, data) as [t][k]
     double *Alag = nullptr;             // L x (2L-1) x K x K (anls_lag_gram_kernel)
-    double *partial = nullptr, *dsum = nullptr;
     unsigned long long *st = nullptr;   // ST_N counters of the running call
-    int64_t npartial = 0;
     struct Host { unsigned long long st[ST_N]; double sum; } *host = nullptr; // pinned
     int64_t w_exchanges = 0, h_exchanges = 0, backup = 0, capped = 0; // of the last call (exchanges: of the last call of each kind)
-    std::vector<void *> owned;
 };
 
 void anls_free(cmf_handle_s *h)
 {
     if (!h || !h->anls) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->anls->owned) (void)hipFree(p);
+    fp64_release(h, h->anls);
     if (h->anls->host) (void)hipHostFree(h->anls->host);
     delete h->anls;
     h->anls = nullptr;
@@ -46,36 +39,10 @@ int anls_counter(const cmf_handle_s *h, const char *name, int64_t *value)
     return 0;
 }
 
-template <typename T>
-static int aalloc(AnlsState *s, T **p, size_t n)
-{
-    HIPCHK(hipMalloc(p, std::max<size_t>(n, 1) * sizeof(T)));
-    s->owned.push_back(*p);
-    return CMF_OK;
-}
-
-static int64_t blocks(int64_t n, int64_t b) { return (n + b - 1) / b; }
-
-template <bool AMF, bool BPF, class AL, class BL, class EP>
-static int gemm(AnlsState *s, hipStream_t st, AL a, BL b, EP e, int64_t M, int64_t P, int64_t R, bool loss)
-{
-    const dim3 grid((unsigned)blocks(M, admm::TM), (unsigned)blocks(P, admm::TP));
-    if (grid.y > 65535) return fail(CMF_ERR_UNSUPPORTED, "ANLS: a contraction of %lld columns is beyond one launch", (long long)P);
-    if (loss && (int64_t)grid.x * grid.y > s->npartial) return fail(CMF_ERR_STATE, "internal: ANLS loss partial buffer too small");
-    hipLaunchKernelGGL((admm::admm_gemm_kernel<AL, BL, EP, AMF, BPF>), grid, dim3(256), 0, st, a, b, e, M, P, R, loss ? s->partial : nullptr);
-    KCHK("admm_gemm_kernel");
-    if (loss) {
-        hipLaunchKernelGGL(anls_sum_kernel, dim3(1), dim3(256), 0, st, s->partial, (int64_t)grid.x * grid.y, s->dsum);
-        KCHK("anls_sum_kernel");
-    }
-    return CMF_OK;
-}
-
 static int anls_state(cmf_handle h, AnlsState **out)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the ANLS rule runs on a single-GPU handle only (this one fronts a T-sharded group)");
+    CMFTRY(fp64_single_gpu(h, RULE, false));
     if (!h->anls) return fail(CMF_ERR_STATE, "call cmf_anls_prepare before the ANLS rule entries");
     *out = h->anls;
     HIPCHK(hipSetDevice(h->device));
@@ -85,37 +52,25 @@ static int anls_state(cmf_handle h, AnlsState **out)
 int cmf_anls_prepare(cmf_handle h, const double *data)
 {
     if (!h || !data) return fail(CMF_ERR_ARG, "NULL argument");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the ANLS rule runs on a single-GPU handle of at most %lld columns only (this one fronts a T-sharded "
-                                         "group: cmf_create_multi / cmf_create_shard, or cmf_create of a longer recording)", (long long)65535 * admm::TP);
+    CMFTRY(fp64_single_gpu(h, RULE, true));
     const int64_t N = h->d.N, T = h->d.Tl, K = h->d.K, L = h->d.L;
-    if (T > (int64_t)65535 * admm::TP) return fail(CMF_ERR_UNSUPPORTED, "ANLS: T = %lld > %lld", (long long)T, (long long)65535 * admm::TP);
+    if (T > (int64_t)65535 * TP) return fail(CMF_ERR_UNSUPPORTED, "ANLS: T = %lld > %lld", (long long)T, (long long)65535 * TP);
     if (L > (1 << 20) || K > (1 << 20)) return fail(CMF_ERR_UNSUPPORTED, "ANLS: K = %lld, L = %lld", (long long)K, (long long)L);
     HIPCHK(hipSetDevice(h->device));
     anls_free(h);
     auto *s = new AnlsState();
     h->anls = s;
     auto bail = [&](int rc) { anls_free(h); return rc; };
-    s->N = N; s->T = T; s->K = K; s->L = L; s->LK = L * K;
+    int rc = fp64_prepare_common(h, s, data);
     const bool w_ok = s->LK <= WMAX, h_ok = K <= KMAX; // the entries refuse what is beyond; the state of the other one is still made
-    s->npartial = blocks(T, 64) * blocks(N, 64);
-    int rc = aalloc(s, &s->data, (size_t)N * T);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Hd, (size_t)K * T);
-    if (rc == CMF_OK) rc = aalloc(s, &s->Wd, (size_t)K * N * L);
-    if (rc == CMF_OK && w_ok) rc = aalloc(s, &s->G, (size_t)s->LK * s->LK);
-    if (rc == CMF_OK && w_ok) rc = aalloc(s, &s->C, (size_t)s->LK * N);
-    if (rc == CMF_OK && w_ok) rc = aalloc(s, &s->X, (size_t)s->LK * N);
-    if (rc == CMF_OK && h_ok) rc = aalloc(s, &s->Bt, (size_t)K * T);
-    if (rc == CMF_OK && h_ok) rc = aalloc(s, &s->Alag, (size_t)L * (2 * L - 1) * K * K);
-    if (rc == CMF_OK) rc = aalloc(s, &s->partial, (size_t)s->npartial);
-    if (rc == CMF_OK) rc = aalloc(s, &s->dsum, 1);
-    if (rc == CMF_OK) rc = aalloc(s, &s->st, ST_N);
+    if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->G, (size_t)s->LK * s->LK);
+    if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->C, (size_t)s->LK * N);
+    if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->X, (size_t)s->LK * N);
+    if (rc == CMF_OK && h_ok) rc = fp64_alloc(s, &s->Bt, (size_t)K * T);
+    if (rc == CMF_OK && h_ok) rc = fp64_alloc(s, &s->Alag, (size_t)L * (2 * L - 1) * K * K);
+    if (rc == CMF_OK) rc = fp64_alloc(s, &s->st, ST_N);
     if (rc != CMF_OK) return bail(rc);
     if (hipHostMalloc(&s->host, sizeof(AnlsState::Host)) != hipSuccess) return bail(fail(CMF_ERR_HIP, "hipHostMalloc failed"));
-    double ss = 0.0; // anls.jl:10-14: the constructor keeps norm(data)
-    for (size_t i = 0; i < (size_t)N * T; ++i) ss += data[i] * data[i];
-    s->datanorm = std::sqrt(ss);
-    if (hipMemcpy(s->data, data, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(CMF_ERR_HIP, "data upload failed"));
     return CMF_OK;
 }
 
@@ -145,25 +100,21 @@ int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W)
     if (LK > WMAX)
         return fail(CMF_ERR_UNSUPPORTED, "ANLS: update_motifs! solves K*L <= %d unknowns per unit in LDS (K*L = %lld)", WMAX, (long long)LK);
     hipStream_t st = h->stream;
-    std::vector<double> Hr((size_t)K * T); // H (K x T, Julia's layout) -> [k][t]
-    for (int64_t t = 0; t < T; ++t)
-        for (int64_t k = 0; k < K; ++k) Hr[(size_t)k * T + t] = H[k + K * t];
-    HIPCHK(hipMemcpyAsync(s->Hd, Hr.data(), Hr.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    std::vector<double> Hr;
+    CMFTRY(fp64_upload_H_rows(s, st, H, Hr));
     HIPCHK(hipMemsetAsync(s->st, 0, ST_N * sizeof(unsigned long long), st));
     // G = Hstk*Hstk', C = Hstk*data' (anls.jl:49-52: t(H_unfold), t(data) as the solver's normal equations)
-    const admm::HstkRT hs{s->Hd, (int)K, (int)T};
-    const admm::HstkTR hst{s->Hd, (int)K, (int)T};
-    CMFTRY((gemm<false, false>(s, st, hs, hst, admm::EpiStore{s->G, LK, 0.0}, LK, LK, T, false)));
-    CMFTRY((gemm<false, true>(s, st, hs, admm::RowMajor{s->data, N}, admm::EpiStore{s->C, N, 0.0}, LK, N, T, false)));
+    const HstkRT hs{s->Hd, (int)K, (int)T};
+    const HstkTR hst{s->Hd, (int)K, (int)T};
+    CMFTRY((fp64_gemm<false, false>(s, st, RULE, hs, hst, EpiStore{s->G, LK, 0.0}, LK, LK, T, false)));
+    CMFTRY((fp64_gemm<false, true>(s, st, RULE, hs, RowMajor{s->data, N}, EpiStore{s->C, N, 0.0}, LK, N, T, false)));
     const int bo = h->anls_backup_only;
     hipLaunchKernelGGL(anls_nnls_w_kernel, dim3((unsigned)N), dim3(256), 0, st, s->G, s->C, s->X, (int)LK, N, ANLS_TOL, anls_round_cap((int)LK, bo), bo, s->st);
     KCHK("anls_nnls_w_kernel");
     std::vector<double> Xh((size_t)LK * N);
     HIPCHK(hipMemcpyAsync(Xh.data(), s->X, Xh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     CMFTRY(finish(s, st, "update_motifs!", &s->w_exchanges));
-    for (int64_t l = 0; l < L; ++l) // fold_W (anls.jl:56, :150-157): W[k, n, l] = X[l*K + k, n]
-        for (int64_t n = 0; n < N; ++n)
-            for (int64_t k = 0; k < K; ++k) W[k + K * (n + N * l)] = Xh[(size_t)(l * K + k) * N + n];
+    fp64_fold_W(Xh.data(), W, K, N, L);
     return CMF_OK;
 }
 
@@ -203,7 +154,7 @@ int cmf_anls_update_feature_maps(cmf_handle h, const double *W, double *H, int v
     HIPCHK(hipMemcpyAsync(s->Hd, H, KT * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(s->st, 0, ST_N * sizeof(unsigned long long), st));
     // B = transconv(W, data) and the lag-Grams stand for the residual windows of anls.jl:27, :76-82
-    CMFTRY((gemm<true, false>(s, st, admm::WkR{s->Wd, (int)K}, ShiftColsLin{s->data, (int)N, T}, EpiStoreT{s->Bt, K}, K, T, N * L, false)));
+    CMFTRY((fp64_gemm<true, false>(s, st, RULE, WkR{s->Wd, (int)K}, ShiftColsLin{s->data, (int)N, T}, EpiStoreT{s->Bt, K}, K, T, N * L, false)));
     const int64_t per = (2 * L - 1) * K * K;
     hipLaunchKernelGGL(anls_lag_gram_kernel, dim3((unsigned)blocks(per, 256)), dim3(256), 0, st, s->Wd, s->Alag, (int)K, N, (int)L);
     KCHK("anls_lag_gram_kernel");
@@ -222,7 +173,7 @@ int cmf_anls_update_feature_maps(cmf_handle h, const double *W, double *H, int v
         CMFTRY(sweep(h, s, 0, T)); // anls.jl:63-94
     }
     // anls.jl:35: norm(resids) / data_norm, the residual formed once from the new H
-    CMFTRY((gemm<false, false>(s, st, admm::WnR{s->Wd, (int)K, (int)N}, LagHT{s->Hd, (int)K}, admm::EpiLossN{s->data, N}, N, T, K * L, true)));
+    CMFTRY((fp64_gemm<false, false>(s, st, RULE, WnR{s->Wd, (int)K, (int)N}, LagHT{s->Hd, (int)K}, EpiLossN{s->data, N}, N, T, K * L, true)));
     HIPCHK(hipMemcpyAsync(&s->host->sum, s->dsum, sizeof(double), hipMemcpyDeviceToHost, st));
     std::vector<double> Hn(KT);
     HIPCHK(hipMemcpyAsync(Hn.data(), s->Hd, KT * sizeof(double), hipMemcpyDeviceToHost, st));

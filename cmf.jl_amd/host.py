@@ -571,24 +571,15 @@ class PGDUpdate(MultUpdate):
 HIPPGDUpdate = PGDUpdate
 
 
-class ADMMUpdate(AbstractCFUpdate):
-    """ADMMUpdate on MI355X: drop-in for src/algs/admm.jl, computed in fp64 end to end.
+class _Fp64Rule(AbstractCFUpdate):
+    """What the fp64 rules share: one single-GPU handle prepared with the data (``_PREPARE``), the caller's arrays written in
+    place, the counters of the last call.  ``_NAME`` / ``_RULE`` are the words the messages name the rule by."""
 
-    ``ADMMUpdate(data, W, H)`` mirrors admm.jl:13-21: it uploads ``data`` in fp64 and keeps its norm (cmf_admm_prepare).  Unlike
-    the other rules nothing of W or H stays on the device between calls: each call reads exactly the factor the reference reads
-    (``update_motifs`` reads H, ``update_feature_maps`` reads W) from the caller's array and overwrites the other one in place,
-    as the reference does.  The inner ADMM loops restart from zero on every call (admm.jl:36-48, :152-163).
-
-    After a call, ``last_W_iters`` / ``last_H_iters`` hold its inner iteration count and ``last_W_reverts`` /
-    ``last_H_reverts`` its reverts (cmf_get_counter "admm_W_reverts" / "admm_H_reverts").  One GPU only.
-    """
-
-    last_W_iters = last_H_iters = last_W_reverts = last_H_reverts = 0
-    MAX_T = 65535 * 64  # columns one contraction launch covers (cmf_admm_prepare refuses more)
+    MAX_T = 65535 * 64  # columns one contraction launch covers (cmf_admm_prepare / cmf_anls_prepare refuse more)
 
     def __init__(self, data, W, H, device=None, devices=None):
         if devices is not None:
-            raise NotImplementedError("ADMMUpdate runs on one GPU: devices=[...] (T sharding) is not available for the ADMM rule")
+            raise NotImplementedError(f"{self._NAME} runs on one GPU: devices=[...] (T sharding) is not available for the {self._RULE} rule")
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -603,17 +594,17 @@ class ADMMUpdate(AbstractCFUpdate):
             raise ValueError(f"DimensionMismatch: data has {data.shape[0]} rows, W has N={N}")
         T = data.shape[1]
         farr(H, (K, T))
-        if T > self.MAX_T:  # (cmf_create would cut such a recording into a T-sharded group, which the ADMM rule cannot run on)
-            raise NotImplementedError(f"ADMMUpdate runs on one handle of at most {self.MAX_T} columns (T = {T})")
+        if T > self.MAX_T:  # (cmf_create would cut such a recording into a T-sharded group, which these rules cannot run on)
+            raise NotImplementedError(f"{self._NAME} runs on one handle of at most {self.MAX_T} columns (T = {T})")
         self.N, self.T, self.K, self.L = N, T, K, L
         self.device = _dev(device)
         check(lib.cmf_create(ctypes.byref(self._h), self.device, N, T, K, L, ptr(data)))
         try:
-            check(lib.cmf_admm_prepare(self._h, ptr(data)))
+            check(getattr(lib, self._PREPARE)(self._h, ptr(data)))
         except Exception:
             self.close()
             raise
-        self.data_norm = float(np.linalg.norm(data))  # admm.jl:17
+        self.data_norm = float(np.linalg.norm(data))  # admm.jl:17, anls.jl:12
 
     @staticmethod
     def _out(a, shape):
@@ -623,6 +614,38 @@ class ADMMUpdate(AbstractCFUpdate):
         if a.dtype == np.float64 and a.flags.f_contiguous and a.flags.writeable:
             return a
         return np.asfortranarray(a, dtype=np.float64).copy(order="F")
+
+    def counter(self, name):
+        v = ctypes.c_int64()
+        check(self._lib.cmf_get_counter(self._h, name.encode(), ctypes.byref(v)))
+        return v.value
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.cmf_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ADMMUpdate(_Fp64Rule):
+    """ADMMUpdate on MI355X: drop-in for src/algs/admm.jl, computed in fp64 end to end.
+
+    ``ADMMUpdate(data, W, H)`` mirrors admm.jl:13-21: it uploads ``data`` in fp64 and keeps its norm (cmf_admm_prepare).  Unlike
+    the other rules nothing of W or H stays on the device between calls: each call reads exactly the factor the reference reads
+    (``update_motifs`` reads H, ``update_feature_maps`` reads W) from the caller's array and overwrites the other one in place,
+    as the reference does.  The inner ADMM loops restart from zero on every call (admm.jl:36-48, :152-163).
+
+    After a call, ``last_W_iters`` / ``last_H_iters`` hold its inner iteration count and ``last_W_reverts`` /
+    ``last_H_reverts`` its reverts (cmf_get_counter "admm_W_reverts" / "admm_H_reverts").  One GPU only.
+    """
+
+    last_W_iters = last_H_iters = last_W_reverts = last_H_reverts = 0
+    _NAME, _RULE, _PREPARE = "ADMMUpdate", "ADMM", "cmf_admm_prepare"
 
     def update_motifs(self, data, W, H, rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=True, **kwargs):
         """update_motifs!(rule::ADMMUpdate, data, W, H; rhow=10, admm_W_maxiter=30, admm_tol=1e-4, nonnegW=true): admm.jl:24-121.
@@ -649,30 +672,14 @@ class ADMMUpdate(AbstractCFUpdate):
         self.last_H_iters, self.last_H_reverts = iters.value, self.counter("admm_H_reverts")
         return loss.value
 
-    def counter(self, name):
-        v = ctypes.c_int64()
-        check(self._lib.cmf_get_counter(self._h, name.encode(), ctypes.byref(v)))
-        return v.value
-
     def set_option(self, name, value):
         raise NotImplementedError(f"ADMMUpdate has no library options (got {name!r}): cmf_set_option selects paths of the other rules")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.cmf_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 HIPADMMUpdate = ADMMUpdate
 
 
-class ANLSUpdate(AbstractCFUpdate):
+class ANLSUpdate(_Fp64Rule):
     """ANLSUpdate on MI355X: drop-in for src/algs/anls.jl (alternating non-negative least squares), computed in fp64 end to end.
 
     ``ANLSUpdate(data, W, H)`` mirrors anls.jl:10-14: it uploads ``data`` in fp64 and keeps its norm (cmf_anls_prepare).  Nothing
@@ -686,37 +693,8 @@ class ANLSUpdate(AbstractCFUpdate):
     """
 
     last_W_exchanges = last_H_exchanges = 0
-    MAX_T = ADMMUpdate.MAX_T  # columns one contraction launch covers (cmf_anls_prepare refuses more)
+    _NAME, _RULE, _PREPARE = "ANLSUpdate", "ANLS", "cmf_anls_prepare"
     _VARIANTS = {"basic": 0, "block": 1}
-
-    def __init__(self, data, W, H, device=None, devices=None):
-        if devices is not None:
-            raise NotImplementedError("ANLSUpdate runs on one GPU: devices=[...] (T sharding) is not available for the ANLS rule")
-        lib = _lib.load()
-        self._lib = lib
-        self._h = ctypes.c_void_p()
-        data = farr(data)
-        if data.ndim != 2:
-            raise ValueError("data must be a matrix (N x T)")
-        W = farr(W)
-        if W.ndim != 3:
-            raise ValueError("W must be a K x N x L tensor")
-        K, N, L = W.shape
-        if data.shape[0] != N:
-            raise ValueError(f"DimensionMismatch: data has {data.shape[0]} rows, W has N={N}")
-        T = data.shape[1]
-        farr(H, (K, T))
-        if T > self.MAX_T:  # (cmf_create would cut such a recording into a T-sharded group, which the ANLS rule cannot run on)
-            raise NotImplementedError(f"ANLSUpdate runs on one handle of at most {self.MAX_T} columns (T = {T})")
-        self.N, self.T, self.K, self.L = N, T, K, L
-        self.device = _dev(device)
-        check(lib.cmf_create(ctypes.byref(self._h), self.device, N, T, K, L, ptr(data)))
-        try:
-            check(lib.cmf_anls_prepare(self._h, ptr(data)))
-        except Exception:
-            self.close()
-            raise
-        self.data_norm = float(np.linalg.norm(data))  # anls.jl:12
 
     @classmethod
     def _variant(cls, variant):
@@ -729,7 +707,7 @@ class ANLSUpdate(AbstractCFUpdate):
         """update_motifs!(rule::ANLSUpdate, data, W, H; kwargs...): anls.jl:22-24, :47-57.  Reads H, overwrites W.  (`variant`
         belongs to update_feature_maps; fit hands every keyword to both calls.)"""
         Hin = farr(H, (self.K, self.T))
-        Wout = ADMMUpdate._out(W, (self.K, self.N, self.L))
+        Wout = self._out(W, (self.K, self.N, self.L))
         try:
             check(self._lib.cmf_anls_update_motifs(self._h, ptr(Hin), ptr(Wout)))
         finally:
@@ -742,7 +720,7 @@ class ANLSUpdate(AbstractCFUpdate):
         overwrites H."""
         code = self._variant(variant)
         Win = farr(W, (self.K, self.N, self.L))
-        Hout = ADMMUpdate._out(H, (self.K, self.T))
+        Hout = self._out(H, (self.K, self.T))
         loss = ctypes.c_double()
         try:
             check(self._lib.cmf_anls_update_feature_maps(self._h, ptr(Win), ptr(Hout), code, ctypes.byref(loss)))
@@ -752,27 +730,11 @@ class ANLSUpdate(AbstractCFUpdate):
             H[...] = Hout
         return loss.value
 
-    def counter(self, name):
-        v = ctypes.c_int64()
-        check(self._lib.cmf_get_counter(self._h, name.encode(), ctypes.byref(v)))
-        return v.value
-
     def set_option(self, name, value):
         if name != "anls_backup_only":
             raise NotImplementedError(f"ANLSUpdate has one library option, 'anls_backup_only' (got {name!r}): the other names of "
                                       "cmf_set_option select paths of the other rules")
         check(self._lib.cmf_set_option(self._h, name.encode(), int(value)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.cmf_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 HIPANLSUpdate = ANLSUpdate
@@ -924,7 +886,7 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     if devices is not None:
         rule = rule_type(data, W_init, H_init, devices=devices)
     else:
-        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, (MultUpdate, ADMMUpdate, ANLSUpdate))
+        rule = (rule_type(data, W_init, H_init, device=device) if issubclass(rule_type, (MultUpdate, _Fp64Rule))
                 else rule_type(data, W_init, H_init))
     try:
         for name, value in (options or {}).items():

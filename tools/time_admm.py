@@ -31,11 +31,11 @@ def kernel_table(path):
     rows = []
     for r in csv.DictReader(open(path)):
         name = r["Name"]
-        if "admm" not in name:
+        if "admm" not in name and "fp64" not in name:
             continue
-        m = re.search(r"admm_gemm_kernel<admm::(\w+)(?:<[^>]*>)?, admm::(\w+)(?:<[^>]*>)?, admm::(\w+)", name)
+        m = re.search(r"fp64_gemm_kernel<\w+::(\w+)(?:<[^>]*>)?, \w+::(\w+)(?:<[^>]*>)?, \w+::(\w+)", name)
         short = (f"contraction {m.group(1)} x {m.group(2)} -> {m.group(3)}" + (" (circ)" if "LagH<true>" in name else "") if m
-                 else re.sub(r"\(.*", "", name).replace("void ", "").replace("admm::", ""))
+                 else re.sub(r"\(.*", "", name).replace("void ", "").replace("admm::", "").replace("fp64::", ""))
         rows.append((short, int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
     tot = sum(r[2] for r in rows)
     con = sum(r[2] for r in rows if r[0].startswith("contraction"))

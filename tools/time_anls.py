@@ -30,11 +30,11 @@ def kernel_table(path):
     rows = []
     for r in csv.DictReader(open(path)):
         name = r["Name"]
-        if "anls" not in name and "admm_gemm_kernel" not in name:  # (the contractions of the W step carry loaders of cmf_admm.h only)
+        if "anls" not in name and "fp64" not in name:
             continue
-        m = re.search(r"admm_gemm_kernel<(?:\w+::)(\w+)(?:<[^>]*>)?, (?:\w+::)(\w+)(?:<[^>]*>)?, (?:\w+::)(\w+)", name)
+        m = re.search(r"fp64_gemm_kernel<\w+::(\w+)(?:<[^>]*>)?, \w+::(\w+)(?:<[^>]*>)?, \w+::(\w+)", name)
         short = (f"contraction {m.group(1)} x {m.group(2)} -> {m.group(3)}" if m
-                 else re.sub(r"\(.*", "", name).replace("void ", "").replace("anls::", ""))
+                 else re.sub(r"\(.*", "", name).replace("void ", "").replace("anls::", "").replace("fp64::", ""))
         rows.append((short, int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
     tot = sum(r[2] for r in rows)
     print(f"{'kernel':<62} {'calls':>6} {'total ms':>9} {'avg ms':>8} {'share':>6}")
