@@ -1,4 +1,4 @@
-"""cmf.jl_amd -- MI355X (gfx950) implementation of CMF.jl's update rules (MU, HALS, PGD, ADMM, ANLS).
+"""cmf.jl_amd -- MI355X (gfx950) implementation of CMF.jl's update rules (MU, HALS, PGD, ADMM, ANLS) and its separable fit.
 
 The directory name is not a Python identifier; import it through the shim at the
 repo root:  ``import cmf_jl_amd as cmf``.
@@ -9,6 +9,7 @@ from .host import (  # noqa: F401
     HIPMultUpdate, HIPPGDUpdate, MaskedLoss, MultUpdate, NonnegConstraint, PGDUpdate, SquareLoss, SquarePenalty, UnitNormConstraint,
     compute_loss, converged, evaluate_convergence, evaluate_mse, evaluate_test, fit, fit_cnmf, gen_synthetic,
     init_rand, load_model, parameter_sweep, rccl_version, save_model, tensor_conv, tensor_transconv,
+    Separable, cos_score, gen_sep_data, is_separable, permute_factors, row_normalize, separable_fit,
 )
 
 __version__ = "0.1.0"

@@ -36,6 +36,7 @@ SYMBOLS = [
     "cmf_pgd_reset", "cmf_set_mask", "cmf_pgd_set_loss", "cmf_pgd_update_motifs", "cmf_pgd_update_feature_maps", "cmf_pgd_get_steps",
     "cmf_admm_prepare", "cmf_admm_update_motifs", "cmf_admm_update_feature_maps",
     "cmf_anls_prepare", "cmf_anls_update_motifs", "cmf_anls_update_feature_maps",
+    "cmf_sep_prepare", "cmf_sep_gram", "cmf_sep_spa", "cmf_sep_nnls", "cmf_sep_shift_table", "cmf_sep_construct",
     "cmf_tensor_conv", "cmf_tensor_transconv", "cmf_init_rand", "cmf_gen_synthetic",
     "cmf_time_kernel", "cmf_kernel_times",
 ]
@@ -130,6 +131,12 @@ def load():
     sig("cmf_anls_prepare", [vp, pd])
     sig("cmf_anls_update_motifs", [vp, pd, pd])
     sig("cmf_anls_update_feature_maps", [vp, pd, pd, cint, pd])
+    sig("cmf_sep_prepare", [vp, pd])
+    sig("cmf_sep_gram", [vp, dbl, pd])
+    sig("cmf_sep_spa", [vp, i64, dbl, cint, pd, pi64])
+    sig("cmf_sep_nnls", [vp, pi64, i64, pd, pd])
+    sig("cmf_sep_shift_table", [vp, pd, i64, i64, pd, pd])
+    sig("cmf_sep_construct", [vp, pd, pd, pi64, pd, pd])
     sig("cmf_tensor_conv", [cint, i64, i64, i64, i64, pd, pd, pd])
     sig("cmf_tensor_transconv", [cint, i64, i64, i64, i64, pd, pd, pd])
     sig("cmf_init_rand", [cint, i64, i64, i64, i64, u64, pd, pd, pd])

@@ -203,6 +203,7 @@ static void destroy_impl(cmf_handle_s *h)
     wb_free(h);
     admm_free(h);
     anls_free(h);
+    sep_free(h);
     if (h->root_only) { delete h; return; }
     (void)hipSetDevice(h->device);
     auto mine = [&](const void *q) { // not a piece of the arena
@@ -1187,6 +1188,7 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
     if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
     if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
+    if (sep_counter(h, name, value)) return CMF_OK;                                                      // pivoting rounds of the last NNLS step of the separable fit
     if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
     if (std::strcmp(name, "small_k_fused_h_updates") == 0) { // (a group: over its shards)
         *value = h->sk_fused_h;

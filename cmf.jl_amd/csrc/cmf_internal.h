@@ -305,6 +305,7 @@ struct cmf_handle_s {
     CmfWriteback *wb = nullptr;           // cmf_arm_writeback: the factors written into the caller's arrays behind a rule call
     struct AdmmState *admm = nullptr;     // the ADMM rule's fp64 state (cmf_admm_prepare; cmf_admm.hip)
     struct AnlsState *anls = nullptr;     // the ANLS rule's fp64 state (cmf_anls_prepare; cmf_anls.hip)
+    struct SepState *sep = nullptr;       // the separable fit's fp64 state (cmf_sep_prepare; cmf_sep.hip)
     int anls_backup_only = 0;             // cmf_set_option "anls_backup_only": every exchange of the ANLS solver is a backup-rule exchange
 };
 
@@ -314,6 +315,9 @@ int admm_counter(const cmf_handle_s *h, const char *name, int64_t *value);
 // cmf_anls.hip: the same for the ANLS state and the counters "anls_W_exchanges" / "anls_H_exchanges" / "anls_backup" / "anls_capped"
 void anls_free(cmf_handle_s *h);
 int anls_counter(const cmf_handle_s *h, const char *name, int64_t *value);
+// cmf_sep.hip: the same for the state of the separable fit and the counter "sep_nnls_exchanges"
+void sep_free(cmf_handle_s *h);
+int sep_counter(const cmf_handle_s *h, const char *name, int64_t *value);
 
 #define HALS_PMAX 4 // puller workgroups per row of the persistent H pipeline (4 -> 7 measured the same span: profiles/r04_hals_pullers_sweep.txt)
 

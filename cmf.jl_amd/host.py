@@ -14,9 +14,11 @@ the reference checkout.
     MultUpdate: ctor, update_motifs!, update_feature_maps!                        src/algs/mult.jl:1-58
     tensor_conv / tensor_transconv / compute_loss                                 src/common.jl:17-81
     gen_synthetic                                                                 README.md:14, datasets/synthetic.jl:29-61
+    separable_fit (alg=:sep), gen_sep_data, cos_score, permute_factors, ...       src/algs/separable.jl:14-56, :422-483, datasets/sep.jl:4-39
 
 Arrays use Julia's index order: ``data[n, t]`` (N,T), ``W[k, n, l]`` (K,N,L), ``H[k, t]`` (K,T).
-All arithmetic runs on the GPU through libcmf_hip.so; nothing here computes on the CPU.
+The arithmetic on the data runs on the GPU through libcmf_hip.so; the host decides only on small tables (the grouping of the
+separable fit, R x R numbers).
 """
 from __future__ import annotations
 
@@ -740,6 +742,254 @@ class ANLSUpdate(_Fp64Rule):
 HIPANLSUpdate = ANLSUpdate
 
 
+# --------------------------------------------------------------------------------------
+# the separable fit (src/algs/separable.jl)
+# --------------------------------------------------------------------------------------
+_SQRT_EPS = EPSILON ** 0.5
+
+
+def _diagscale(c):
+    """The diagonal of diagscale (separable.jl:389-391)."""
+    return c + (c < EPSILON)
+
+
+def row_normalize(H):
+    """row_normalize(H): separable.jl:422-424."""
+    H = np.asarray(H, dtype=np.float64)
+    return H * (1.0 / _diagscale(np.abs(H).sum(axis=1)))[:, None]
+
+
+def cos_score(trueH, estH):
+    """cos_score(trueH, estH): separable.jl:432-441."""
+    trueH, estH = np.asarray(trueH, dtype=np.float64), np.asarray(estH, dtype=np.float64)
+    return float(np.mean([trueH[k] @ estH[k] / (np.linalg.norm(trueH[k]) * np.linalg.norm(estH[k])) for k in range(trueH.shape[0])]))
+
+
+def permute_factors(trueH, estH):
+    """permute_factors(trueH, estH): separable.jl:444-449 -- the permutation p that maximises cos_score(estH[p], trueH)."""
+    import itertools
+
+    estH = np.asarray(estH)
+    perms = list(itertools.permutations(range(np.asarray(trueH).shape[0])))
+    return list(perms[int(np.argmax([cos_score(estH[list(p)], trueH) for p in perms]))])
+
+
+def is_separable(H, L):
+    """is_separable(H, L): separable.jl:452-483 -- does the block form of H contain a scaled permuted identity?"""
+    H = np.asarray(H)
+    K, T = H.shape
+    G = np.zeros((K * L, T))
+    for l in range(L):
+        G[l * K:(l + 1) * K, l:] = H[:, :T - l]
+    nz = G != 0
+    return bool(nz[:, nz.sum(axis=0) == 1].any(axis=1).all())
+
+
+def gen_sep_data(N, T, K, L, H_sparsity=0.75, seed=None, device=None):
+    """gen_sep_data(N, T, K, L; H_sparsity=0.75) -> (data, W, H): datasets/sep.jl:4-39, on the K x N x L layout, drawn from
+    ``numpy.random.default_rng(seed)``; data = tensor_conv(W, H) on the GPU."""
+    rng = np.random.default_rng(seed)
+    if T < 3 * K * L:
+        raise ValueError("T too small")  # sep.jl:13-16
+    W = 0.5 + rng.random((K, N, L))
+    H = rng.random((K, T)) * (rng.random((K, T)) > H_sparsity)
+    hL = L // 2
+    free = np.ones(T - L, dtype=bool)
+    for k in range(K):
+        for down, up in ((-L, hL), (-hL, L)):  # left and right side of the sequence (sep.jl:23)
+            t = int(rng.choice(np.flatnonzero(free)))
+            t1, t2 = max(0, t + down), min(T - 1, t + up)
+            H[:, t1:t2 + 1] = 0.0
+            H[k, t] = 0.5 + rng.random()
+            free[t1:min(t2, T - L - 1) + 1] = False
+    W, H = np.asfortranarray(W), np.asfortranarray(H)
+    return tensor_conv(W, H, device=device), W, H
+
+
+def _cos_ab(P, head, a, b):
+    """cosL(G[a], G[b], l, "a") and (..., "b") for l = 0..L-1 from the shift table (separable.jl:374-385)."""
+    return P[a, b, :] / (head[a, :] * head[b, 0]), P[b, a, :] / (head[a, 0] * head[b, :])
+
+
+def _find_groups(dmat, K, L):
+    """find_groups: separable.jl:191-211 (pop! takes the last ungrouped row, findmax the first maximum)."""
+    groups = [[] for _ in range(K)]
+    ungrouped = list(range(K * L))
+    for k in range(K):
+        groups[k].append(ungrouped.pop())
+        while len(groups[k]) < L:
+            sims = dmat[np.ix_(groups[k], ungrouped)].sum(axis=0)
+            groups[k].append(ungrouped.pop(int(np.argmax(sims))))
+    return groups
+
+
+def _find_groups_spectral(simat, K, L):
+    """find_groups_spectral: separable.jl:214-270 with binarize=false."""
+    R = K * L
+    simat = np.maximum(0.0, simat - simat.sum() / R ** 2)
+    _, V = np.linalg.eigh(simat)
+    free = np.ones(R, dtype=bool)
+    groups = []
+    for k in range(K):
+        v = V[:, R - 1 - k]
+        if abs(v.max()) < abs(v.min()):
+            v = -v  # reorient (:242-244)
+        rows = np.flatnonzero(free)
+        priority = rows[np.argsort(-v[rows], kind="stable")]
+        groups.append([int(r) for r in priority[:L]])
+        free[priority[:L]] = False
+    return groups
+
+
+def _arg_shift_max(left, right):
+    """arg_shift_max: separable.jl:112-131 (strict >, "a" before "b")."""
+    arg, best = 0, 0.0
+    for l in range(len(left)):
+        if left[l] > best:
+            best, arg = left[l], l
+        if right[l] > best:
+            best, arg = right[l], -l
+    return arg
+
+
+def _sort_group(group, P, head):
+    """sort_group: separable.jl:96-109, the cosines from the shift table; a stable sort by descending weight."""
+    weight = [sum(_arg_shift_max(*_cos_ab(P, head, a, b)) for b in group) for a in group]
+    return [group[i] for i in np.argsort(-np.asarray(weight, dtype=np.float64), kind="stable")]
+
+
+class Separable(_Fp64Rule):
+    """The stages of the separable fit (src/algs/separable.jl) on one MI355X, in fp64: ``Separable(data, K, L)`` uploads the data
+    (cmf_sep_prepare); ``spa``, ``nnls``, ``shift_table`` and ``construct`` are the four device stages (cmf_sep_*), ``cluster``
+    the decisions on R x R numbers between them (numpy).  ``separable_fit`` runs them in the reference's order."""
+
+    _NAME, _RULE, _PREPARE = "Separable", "separable", "cmf_sep_prepare"
+    _PRE = {None: 0, "svd": 1, "svdcond": 2}
+
+    def __init__(self, data, K, L, device=None):
+        data = farr(data)
+        if data.ndim != 2:
+            raise ValueError("data must be a matrix (N x T)")
+        N, T = data.shape
+        super().__init__(data, np.zeros((K, N, L), order="F"), np.zeros((K, T), order="F"), device=device)
+        self.R = K * L
+
+    @classmethod
+    def _pre(cls, pre):
+        name = pre.lstrip(":") if isinstance(pre, str) else pre
+        if name not in cls._PRE:
+            raise ValueError(f"pre must be None, ':svd' or ':svdcond', got {pre!r}")
+        return name
+
+    def projection(self, R, thresh, pre):
+        """The R x N matrix that pre_svd / pre_svdcond (separable.jl:323-333) multiply X by, from the eigen-decomposition of
+        X X' (cmf_sep_gram): U' for :svd (= Diagonal(S) * Vt), S^-1 U' for :svdcond (= Vt).  SPA is invariant under the sign of a
+        singular vector (a row of the projected matrix changes sign; norms, inner products and the projector do not); the sign
+        is fixed -- the entry of largest magnitude positive -- only so that two runs give the same matrix."""
+        XXt = np.zeros((self.N, self.N), order="F")
+        check(self._lib.cmf_sep_gram(self._h, float(thresh), ptr(XXt)))
+        lam, U = np.linalg.eigh(XXt)
+        lam, U = lam[::-1][:R], U[:, ::-1][:, :R]
+        sgn = np.sign(U[np.abs(U).argmax(axis=0), np.arange(R)])
+        U = U * np.where(sgn == 0, 1.0, sgn)[None, :]
+        if pre == "svd":
+            return np.ascontiguousarray(U.T)
+        if not (lam > 0).all():
+            raise ValueError("pre=:svdcond needs R positive singular values")
+        return np.ascontiguousarray(U.T / np.sqrt(lam)[:, None])
+
+    def spa(self, R=None, thresh=0, pre=None):
+        """SPA(data, R; thresh, pre) -> sorted vertices (0-based): separable.jl:280-319."""
+        R = self.R if R is None else int(R)
+        pre = self._pre(pre)
+        if not 1 <= R <= min(self.N, self.T):
+            raise ValueError(f"SPA needs 1 <= R <= min(N, T) (R = {R}, N = {self.N}, T = {self.T})")
+        proj = None if pre is None else self.projection(R, thresh, pre)
+        vertices = np.zeros(R, dtype=np.int64)
+        check(self._lib.cmf_sep_spa(self._h, R, float(thresh), self._PRE[pre], None if proj is None else ptr(proj),
+                                    vertices.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return [int(v) for v in vertices]
+
+    def nnls(self, vertices):
+        """V = data[:, vertices]; G = nonneg_lsq(V, data); renormalize!(V, G) -> (V, G): separable.jl:23-27."""
+        v = np.ascontiguousarray(vertices, dtype=np.int64)
+        V = np.zeros((self.N, len(v)), order="F")
+        G = np.zeros((len(v), self.T), order="F")
+        try:
+            check(self._lib.cmf_sep_nnls(self._h, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(v), ptr(V), ptr(G)))
+        finally:
+            self.last_nnls_exchanges = self.counter("sep_nnls_exchanges")
+        return V, G
+
+    def shift_table(self, G, L=None):
+        """(P, head) with P[a, b, l] = sum_t G[a, t] G[b, t+l] and head[a, l] = |G[a, :T-l]|: what shift_cos / cosL
+        (separable.jl:364-385) are made of."""
+        L = self.L if L is None else int(L)
+        G = farr(G)
+        R = G.shape[0]
+        if G.shape != (R, self.T):
+            raise ValueError(f"expected G of shape (R, {self.T}), got {G.shape}")
+        P = np.zeros((R, R, L), order="F")
+        head = np.zeros((R, L), order="F")
+        check(self._lib.cmf_sep_shift_table(self._h, ptr(G), R, L, ptr(P), ptr(head)))
+        return P, head
+
+    def cluster(self, P, head, spectral=False):
+        """shift_cluster and sort_group (separable.jl:140-172, :96-109) from the shift table -> K sorted groups of L rows."""
+        R = P.shape[0]
+        dmat = np.zeros((R, R))
+        for r in range(R):  # :144-150, shift_cos (:364-370)
+            for p in range(r, R):
+                left, right = _cos_ab(P, head, r, p)
+                dmat[r, p] = dmat[p, r] = max(0.0, left.max(), right.max())
+        groups = (_find_groups_spectral if spectral else _find_groups)(dmat, self.K, self.L)
+        return [_sort_group(g, P, head) for g in groups]
+
+    def construct(self, V, G, groups):
+        """construct_WH(V, G, groups): separable.jl:59-87 -> (W, H)."""
+        g = np.asfortranarray(np.asarray(groups, dtype=np.int64).reshape(self.K, self.L))
+        W = np.zeros((self.K, self.N, self.L), order="F")
+        H = np.zeros((self.K, self.T), order="F")
+        check(self._lib.cmf_sep_construct(self._h, ptr(farr(V, (self.N, self.R))), ptr(farr(G, (self.R, self.T))),
+                                          g.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(W), ptr(H)))
+        return W, H
+
+
+def separable_fit(data, K, L, thresh=0, verbose=False, refit_H=False, refit_W=False, refit_H_itr=10, spectral=False, pre=None,
+                  device=None, stages=None, **kwargs):
+    """Separable.fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false,
+    pre=nothing) -> (W, H): separable.jl:14-56.  ``verbose`` is accepted and plots nothing.  ``refit_W`` is
+    ANLSUpdate.update_motifs (fp64), ``refit_H`` is ``refit_H_itr`` H sweeps of the HALS rule with l1H = l2H = 0 (fp32, like
+    that rule).  ``stages`` (a dict) receives vertices, V, G, P, head and groups.  One GPU; K*L <= 128."""
+    data = farr(data)
+    rule = Separable(data, K, L, device=device)
+    try:
+        vertices = rule.spa(thresh=thresh, pre=pre)  # step 1 (:22-23)
+        V, G = rule.nnls(vertices)  # step 2 (:26-27)
+        P, head = rule.shift_table(G)
+        groups = rule.cluster(P, head, spectral=spectral)  # steps 3 and 4 (:30-35)
+        W, H = rule.construct(V, G, groups)  # :38
+    finally:
+        rule.close()
+    if stages is not None:
+        stages.update(vertices=vertices, V=V, G=G, P=P, head=head, groups=groups)
+    if refit_W:  # :41-43
+        anls = ANLSUpdate(data, W, H, device=device)
+        try:
+            anls.update_motifs(data, W, H)
+        finally:
+            anls.close()
+    if refit_H:  # :46-52
+        hals = HALSUpdate(data, W, H, device=device)
+        try:
+            for _ in range(int(refit_H_itr)):
+                hals.update_feature_maps()
+            hals.download(None, H)
+        finally:
+            hals.close()
+    return W, H
+
+
 def _resolve_alg(alg):
     """alg may be a rule type (HEAD, model.jl:60) or a README-style symbol (README.md:30-33)."""
     if isinstance(alg, str):
@@ -755,7 +1005,7 @@ def _resolve_alg(alg):
         if name == "anls":
             raise NotImplementedError("alg=:anls is not mapped as a name: select the ANLS rule by type, alg=ANLSUpdate (model.jl:60)")
         if name == "sep":
-            raise NotImplementedError(f"alg=:{name} is outside the MI355X hot path built here (:mult, :hals, :pgd, :admm, ANLSUpdate)")
+            return Separable
         raise ValueError(f"unknown algorithm {alg!r}")
     if isinstance(alg, type) and issubclass(alg, AbstractCFUpdate):
         return alg
@@ -828,7 +1078,8 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "l1W", "l2W", "l1H", "l2H", "device", "devices", "options",
              "loss_func", "constrW", "constrH", "penaltiesW", "penaltiesH",  # PGDUpdate (pgd.jl:158-202)
              "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH",  # ADMMUpdate (admm.jl:24-27,124-127)
-             "variant"}  # ANLSUpdate (anls.jl:26)
+             "variant",  # ANLSUpdate (anls.jl:26)
+             "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre"}  # alg=:sep (separable.jl:14-18)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -870,6 +1121,16 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     options = kw.pop("options", None)  # {name: value} for cmf_set_option on the rule (include/cmf_hip.h lists them)
     rule_type = _resolve_alg(alg)
     data = farr(data)
+    if rule_type is Separable:
+        # The separable fit has no iteration and HEAD has no mapping for it (model.jl:3-8 is commented out): the result holds
+        # the loss of the fit and the wall time it took; max_itr, max_time, W_init and H_init do not apply.
+        if devices is not None:
+            raise NotImplementedError("devices=[...] (T sharding) is not available for alg=:sep: the separable fit runs on one GPU")
+        sep_kw = {k: kw[k] for k in ("thresh", "verbose", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre") if k in kw}
+        t0 = time.time()
+        W, H = separable_fit(data, K, L, device=device, **sep_kw)
+        dur = time.time() - t0
+        return CNMF_results(data, W, H, np.asarray([dur]), np.asarray([compute_loss(data, W, H, device=device)]))
 
     seed = kw.get("seed", None)  # :64-67
     # Initialize (:70) -- always runs, like the reference (it consumes the RNG even when inits are given)

@@ -485,4 +485,114 @@ function gen_synthetic(; N=100, T=500, K=3, L=20, alpha=0.1, p_h=0.5, sigma=0.2,
     return data
 end
 
+"""
+    HIPSeparable.fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false,
+                     pre=nothing, device=LOCAL_RANK or 0) -> W, H
+
+Drop-in for `Separable.fit` (src/algs/separable.jl:14-56) in fp64 on one GPU, on the K x N x L layout of W.  The four device stages
+are `cmf_sep_spa`, `cmf_sep_nnls`, `cmf_sep_shift_table` and `cmf_sep_construct`; the grouping and sorting of the K*L rows
+(separable.jl:96-131, :191-270) run here on the shift table.  K*L <= 128.  Row and column numbers are 0-based on the C side.
+"""
+module HIPSeparable
+
+using LinearAlgebra
+import ..CMFHip: LIBCMF, check, HIPANLSUpdate, HIPHALSUpdate, update_motifs!, update_feature_maps!
+
+cos_ab(P, head, a, b) = (P[a, b, :] ./ (head[a, :] .* head[b, 1]), P[b, a, :] ./ (head[a, 1] .* head[b, :]))
+
+function find_groups(dmat, K, L)  # separable.jl:191-211
+    groups = [Int[] for k in 1:K]
+    ungrouped = collect(1:L*K)
+    for k in 1:K
+        push!(groups[k], pop!(ungrouped))
+        while length(groups[k]) < L
+            _, i = findmax(vec(sum(dmat[groups[k], ungrouped], dims=1)))
+            push!(groups[k], ungrouped[i])
+            deleteat!(ungrouped, i)
+        end
+    end
+    return groups
+end
+
+function find_groups_spectral(simat, K, L)  # separable.jl:214-270, binarize=false
+    R = K * L
+    F = eigen(Symmetric(max.(0, simat .- (sum(simat) / R^2))))
+    V = F.vectors
+    free = trues(R)
+    groups = Vector{Int}[]
+    for k in 0:K-1
+        v = V[:, R-k]
+        abs(maximum(v)) < abs(minimum(v)) && (v = -v)
+        priority = sort(findall(free), by=j -> v[j], rev=true)
+        push!(groups, priority[1:L])
+        free[priority[1:L]] .= false
+    end
+    return groups
+end
+
+function arg_shift_max(left, right)  # separable.jl:112-131
+    arg, best = 0, 0.0
+    for l in 0:length(left)-1
+        left[l+1] > best && ((best, arg) = (left[l+1], l))
+        right[l+1] > best && ((best, arg) = (right[l+1], -l))
+    end
+    return arg
+end
+
+function sort_group(group, P, head)  # separable.jl:96-109
+    weight = [sum(arg_shift_max(cos_ab(P, head, a, b)...) for b in group) for a in group]
+    return group[sort(collect(1:length(group)), by=j -> -weight[j])]
+end
+
+function projection(handle, N, R, thresh, pre)  # pre_svd / pre_svdcond (separable.jl:323-333) from eigen(X X')
+    XXt = zeros(N, N)
+    check(ccall((:cmf_sep_gram, LIBCMF), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), handle, thresh, XXt))
+    F = eigen(Symmetric(XXt))
+    U = F.vectors[:, end:-1:end-R+1]
+    S = sqrt.(F.values[end:-1:end-R+1])
+    return pre == :svd ? U : U ./ S'   # N x R: column r is row r of the matrix SPA multiplies X by (any sign: SPA does not see it)
+end
+
+function fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false, pre=nothing,
+             device::Integer=parse(Int, get(ENV, "LOCAL_RANK", "0")), kwargs...)
+    pre in (nothing, :svd, :svdcond) || throw(ArgumentError("pre must be nothing, :svd or :svdcond"))
+    d = Matrix{Float64}(data)
+    N, T = size(d)
+    R = K * L
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:cmf_create, LIBCMF), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64, Int64, Ptr{Float64}), h, device, N, T, K, L, d))
+    W, H = zeros(K, N, L), zeros(K, T)
+    try
+        check(ccall((:cmf_sep_prepare, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], d))
+        proj = pre === nothing ? Ptr{Float64}(C_NULL) : projection(h[], N, R, Float64(thresh), pre)
+        vertices = zeros(Int64, R)
+        check(ccall((:cmf_sep_spa, LIBCMF), Cint, (Ptr{Cvoid}, Int64, Float64, Cint, Ptr{Float64}, Ptr{Int64}),
+                    h[], R, thresh, pre === nothing ? 0 : (pre == :svd ? 1 : 2), proj, vertices))
+        V, G = zeros(N, R), zeros(R, T)
+        check(ccall((:cmf_sep_nnls, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}), h[], vertices, R, V, G))
+        P, head = zeros(R, R, L), zeros(R, L)
+        check(ccall((:cmf_sep_shift_table, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                    h[], G, R, L, P, head))
+        dmat = [max(0.0, maximum(cos_ab(P, head, r, p)[1]), maximum(cos_ab(P, head, r, p)[2])) for r in 1:R, p in 1:R]
+        dmat = [r <= p ? dmat[r, p] : dmat[p, r] for r in 1:R, p in 1:R]  # separable.jl:144-150 fills from the upper triangle
+        groups = spectral ? find_groups_spectral(dmat, K, L) : find_groups(dmat, K, L)
+        groups = [sort_group(g, P, head) for g in groups]
+        g0 = Int64[groups[k][l] - 1 for k in 1:K, l in 1:L]
+        check(ccall((:cmf_sep_construct, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                    h[], V, G, g0, W, H))
+    finally
+        ccall((:cmf_destroy, LIBCMF), Cint, (Ptr{Cvoid},), h[])
+    end
+    refit_W && update_motifs!(HIPANLSUpdate(d, W, H; device=device), d, W, H)   # separable.jl:41-43
+    if refit_H                                                                    # separable.jl:46-52
+        rule = HIPHALSUpdate(d, W, H; device=device)
+        for itr in 1:refit_H_itr
+            update_feature_maps!(rule, d, W, H; l1H=0, l2H=0)
+        end
+    end
+    return W, H
+end
+
+end # module HIPSeparable
+
 end # module

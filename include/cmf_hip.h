@@ -67,7 +67,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_sep.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -471,6 +471,40 @@ int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W);
  * columns in order; needs T >= L (CMF_ERR_ARG: the reference indexes T-L+2:T).  Any other variant is CMF_ERR_ARG.  K <= 64 and
  * (L-1)*K <= 6144 (CMF_ERR_UNSUPPORTED). */
 int cmf_anls_update_feature_maps(cmf_handle h, const double *W, double *H, int variant, double *loss);
+
+/* ---- separable fit ---------------------------------------------------------------------------------------------------------
+ * The "LCS" fit of src/algs/separable.jl (Separable.fit, separable.jl:14-56): successive projection, one NNLS, shift clustering.
+ * It has no iteration; it is what the reference's notebooks start the other rules from.  Computed in fp64 end to end, restated on
+ * the K x N x L layout of W (W[k, n, l] = V[n, groups[k][l]]); DESIGN.md 6d has the rewritings.  One entry per stage, so that a
+ * caller (or a test) can run and inspect them one at a time; the decisions on R x R numbers between them (find_groups,
+ * find_groups_spectral, sort_group, separable.jl:96-131, :191-270) and the eigen-decomposition behind `pre` are the host
+ * language's.  Indices are 0-based.  Arrays are Julia's (column-major).  Single-GPU handles only, and the handle's K, L give
+ * R = K*L where an entry does not take it.  cmf_get_counter: "sep_nnls_exchanges" = pivoting rounds of the last cmf_sep_nnls,
+ * summed over its T problems.
+ *
+ * Uploads `data` (N x T, fp64) and allocates the state of the fit on the handle's device (separable.jl:19). */
+int cmf_sep_prepare(cmf_handle h, const double *data);
+/* X X' (N x N) of the matrix SPA works on -- the columns of data scaled to l1-norm 1, the ones with col1 < thresh zeroed
+ * (separable.jl:281-291) -- for pre_svd / pre_svdcond (separable.jl:323-333): its eigen-decomposition gives the caller U and S. */
+int cmf_sep_gram(cmf_handle h, double thresh, double *XXt);
+/* SPA(data, R; thresh, pre) -> vertices (R of them, sorted)  separable.jl:280-319, with findsetmax (separable.jl:403-419) and the
+ * col2 tie-break (:306-311) on the device; nothing is read back before all R rounds are enqueued.  pre 0: none; 1 (:svd) or 2
+ * (:svdcond): `proj` holds R rows of N numbers, the matrix that takes X to Diagonal(S) * Vt = U' X or to Vt = S^-1 U' X
+ * (row r at proj + r*N), else NULL.  1 <= R <= min(N, T) (CMF_ERR_ARG); N <= 4096; a residual that vanishes before R rounds
+ * (fewer than R independent columns) is CMF_ERR_UNSUPPORTED. */
+int cmf_sep_spa(cmf_handle h, int64_t R, double thresh, int pre, const double *proj, int64_t *vertices);
+/* V = data[:, vertices]; G = nonneg_lsq(V, data); renormalize!(V, G)  separable.jl:23-27, :340-348.  V: N x R, G: R x T.  The T
+ * problems share V'V and run in the solver of cmf_anls_update_motifs (tol 1e-8): R <= 128 (CMF_ERR_UNSUPPORTED beyond), the same
+ * refusal of a non-positive pivot or a capped problem, V and G untouched on failure.  `vertices` is read only. */
+int cmf_sep_nnls(cmf_handle h, int64_t *vertices, int64_t R, double *V, double *G);
+/* What shift_cos / cosL (separable.jl:364-385) are made of, for shift_cluster (:144-150) and sort_group (:100-105):
+ * P[a, b, l] = sum_t G[a, t] G[b, t+l] (R x R x L) and head[a, l] = norm(G[a, 1:T-l]) (R x L), so that
+ * cosL(a, b, l, "a") = P[a, b, l] / (head[a, l] head[b, 0]) and cosL(a, b, l, "b") = P[b, a, l] / (head[a, 0] head[b, l]).
+ * A zero row of G (a cosine 0/0) is CMF_ERR_UNSUPPORTED and the message names it; 1 <= L <= T. */
+int cmf_sep_shift_table(cmf_handle h, const double *G, int64_t R, int64_t L, double *P, double *head);
+/* construct_WH(V, G, groups; average_H=true)  separable.jl:59-87, with the reference's divisor min(T, t+L) - t + 1.  groups: K x L
+ * rows of G (read only), in the sorted order; W: K x N x L, H: K x T. */
+int cmf_sep_construct(cmf_handle h, const double *V, const double *G, int64_t *groups, double *W, double *H);
 
 /* converged(loss_hist, patience, tol): src/model.jl:91-107 (host arithmetic). */
 int cmf_converged(const double *loss_hist, int64_t len, int64_t patience, double tol);
