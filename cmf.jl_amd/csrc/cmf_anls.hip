@@ -4,6 +4,7 @@
 // package are in DESIGN.md, "The ANLS rule".
 #include "cmf_internal.h"
 #include "cmf_anls.h"
+#include "cmf_nnls_large.h"
 
 using namespace fp64;
 using namespace anls;
@@ -16,6 +17,7 @@ struct AnlsState : Fp64State { // Hd: [k][t] in the W call (the stacked loaders)
     double *Bt = nullptr;               // H step: transconv(W, data) as [t][k]
     double *Alag = nullptr;             // L x (2L-1) x K x K (anls_lag_gram_kernel)
     unsigned long long *st = nullptr;   // ST_N counters of the running call
+    LargeScratch large;                 // the slabs of nnls_large_kernel (option "nnls_large"), made by the first call that needs them
     struct Host { unsigned long long st[ST_N]; double sum; } *host = nullptr; // pinned
     int64_t w_exchanges = 0, h_exchanges = 0, backup = 0, capped = 0; // of the last call (exchanges: of the last call of each kind)
 };
@@ -24,6 +26,7 @@ void anls_free(cmf_handle_s *h)
 {
     if (!h || !h->anls) return;
     fp64_release(h, h->anls);
+    large_release(&h->anls->large);
     if (h->anls->host) (void)hipHostFree(h->anls->host);
     delete h->anls;
     h->anls = nullptr;
@@ -62,7 +65,9 @@ int cmf_anls_prepare(cmf_handle h, const double *data)
     h->anls = s;
     auto bail = [&](int rc) { anls_free(h); return rc; };
     int rc = fp64_prepare_common(h, s, data);
-    const bool w_ok = s->LK <= WMAX, h_ok = K <= KMAX; // the entries refuse what is beyond; the state of the other one is still made
+    // the entries refuse what is beyond; the state of the other one is still made.  (WMAX < K*L <= WLARGE: option "nnls_large" is set
+    // after the rule is made, so update_motifs! makes G, C, X when it first runs there.)
+    const bool w_ok = s->LK <= WMAX, h_ok = K <= KMAX;
     if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->G, (size_t)s->LK * s->LK);
     if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->C, (size_t)s->LK * N);
     if (rc == CMF_OK && w_ok) rc = fp64_alloc(s, &s->X, (size_t)s->LK * N);
@@ -97,9 +102,17 @@ int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W)
     CMFTRY(anls_state(h, &s));
     if (!H || !W) return fail(CMF_ERR_ARG, "NULL argument");
     const int64_t N = s->N, T = s->T, K = s->K, L = s->L, LK = s->LK;
-    if (LK > WMAX)
+    const bool large = LK > WMAX && h->nnls_large;
+    if (LK > WMAX && !large)
         return fail(CMF_ERR_UNSUPPORTED, "ANLS: update_motifs! solves K*L <= %d unknowns per unit in LDS (K*L = %lld)", WMAX, (long long)LK);
+    if (LK > WLARGE)
+        return fail(CMF_ERR_UNSUPPORTED, "ANLS: update_motifs! solves K*L <= %d unknowns per unit (option \"nnls_large\"; K*L = %lld)", WLARGE, (long long)LK);
     hipStream_t st = h->stream;
+    if (!s->G) { // (only where cmf_anls_prepare left them out: K*L > WMAX)
+        CMFTRY(fp64_alloc(s, &s->G, (size_t)LK * LK));
+        CMFTRY(fp64_alloc(s, &s->C, (size_t)LK * N));
+        CMFTRY(fp64_alloc(s, &s->X, (size_t)LK * N));
+    }
     std::vector<double> Hr;
     CMFTRY(fp64_upload_H_rows(s, st, H, Hr));
     HIPCHK(hipMemsetAsync(s->st, 0, ST_N * sizeof(unsigned long long), st));
@@ -109,8 +122,12 @@ int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W)
     CMFTRY((fp64_gemm<false, false>(s, st, RULE, hs, hst, EpiStore{s->G, LK, 0.0}, LK, LK, T, false)));
     CMFTRY((fp64_gemm<false, true>(s, st, RULE, hs, RowMajor{s->data, N}, EpiStore{s->C, N, 0.0}, LK, N, T, false)));
     const int bo = h->anls_backup_only;
-    hipLaunchKernelGGL(anls_nnls_w_kernel, dim3((unsigned)N), dim3(256), 0, st, s->G, s->C, s->X, (int)LK, N, ANLS_TOL, anls_round_cap((int)LK, bo), bo, s->st);
-    KCHK("anls_nnls_w_kernel");
+    if (large) {
+        CMFTRY(nnls_large(&s->large, st, RULE, s->G, s->C, s->X, (int)LK, N, ANLS_TOL, bo, s->st));
+    } else {
+        hipLaunchKernelGGL(anls_nnls_w_kernel, dim3((unsigned)N), dim3(256), 0, st, s->G, s->C, s->X, (int)LK, N, ANLS_TOL, anls_round_cap((int)LK, bo), bo, s->st);
+        KCHK("anls_nnls_w_kernel");
+    }
     std::vector<double> Xh((size_t)LK * N);
     HIPCHK(hipMemcpyAsync(Xh.data(), s->X, Xh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     CMFTRY(finish(s, st, "update_motifs!", &s->w_exchanges));

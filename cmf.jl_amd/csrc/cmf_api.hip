@@ -1263,6 +1263,12 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         h->anls_backup_only = value;
         return CMF_OK;
     }
+    if (std::strcmp(name, "nnls_large") == 0) { // cmf_anls_update_motifs / cmf_sep_nnls: 129 .. 1024 unknowns through global scratch (not a path of the listed rules either)
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "nnls_large: the ANLS rule and the separable fit run on single-GPU handles only");
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "nnls_large must be 0 or 1");
+        h->nnls_large = value;
+        return CMF_OK;
+    }
     if (h->group) {
         cmf_group_s *g = h->group;
         CMFTRY(group_join(g));

@@ -307,6 +307,7 @@ struct cmf_handle_s {
     struct AnlsState *anls = nullptr;     // the ANLS rule's fp64 state (cmf_anls_prepare; cmf_anls.hip)
     struct SepState *sep = nullptr;       // the separable fit's fp64 state (cmf_sep_prepare; cmf_sep.hip)
     int anls_backup_only = 0;             // cmf_set_option "anls_backup_only": every exchange of the ANLS solver is a backup-rule exchange
+    int nnls_large = 0;                   // cmf_set_option "nnls_large": 129 .. 1024 unknowns run in nnls_large_kernel (cmf_nnls_large.h) instead of being refused
 };
 
 // cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)

@@ -4,6 +4,7 @@
 // DESIGN.md 6d.  The decisions on R x R numbers (grouping, sorting) are the host language's.
 #include "cmf_internal.h"
 #include "cmf_anls.h"
+#include "cmf_nnls_large.h"
 #include "cmf_sep.h"
 
 using namespace fp64;
@@ -21,6 +22,7 @@ struct SepState : Fp64State { // data: [t][n]
     double *Vd = nullptr, *Gram = nullptr, *C = nullptr, *Gd = nullptr, *rowsum = nullptr; // step 2, made on demand for R rows
     double *P = nullptr, *part = nullptr, *head = nullptr;                                // shift table, made on demand
     int64_t nnls_rows = 0, table_rows = 0, table_L = 0, table_splits = 0;
+    anls::LargeScratch large;                  // the slabs of nnls_large_kernel (option "nnls_large"), made by the first call that needs them
     unsigned long long *st = nullptr;          // anls::ST_N counters, then FL_N flags
     struct Host { unsigned long long st[anls::ST_N + FL_N]; } *host = nullptr; // pinned
     int64_t exchanges = 0;
@@ -31,6 +33,7 @@ void sep_free(cmf_handle_s *h)
 {
     if (!h || !h->sep) return;
     fp64_release(h, h->sep);
+    anls::large_release(&h->sep->large);
     if (h->sep->host) (void)hipHostFree(h->sep->host);
     delete h->sep;
     h->sep = nullptr;
@@ -195,7 +198,11 @@ int cmf_sep_nnls(cmf_handle h, int64_t *vertices, int64_t R, double *V, double *
     if (!vertices || !V || !G) return fail(CMF_ERR_ARG, "NULL argument");
     const int64_t N = s->N, T = s->T;
     if (R < 1) return fail(CMF_ERR_ARG, "separable: R = %lld", (long long)R);
-    if (R > anls::WMAX) return fail(CMF_ERR_UNSUPPORTED, "separable: the NNLS step solves R = K*L <= %d unknowns per column in LDS (R = %lld)", anls::WMAX, (long long)R);
+    const bool large = R > anls::WMAX && h->nnls_large;
+    if (R > anls::WMAX && !large)
+        return fail(CMF_ERR_UNSUPPORTED, "separable: the NNLS step solves R = K*L <= %d unknowns per column in LDS (R = %lld)", anls::WMAX, (long long)R);
+    if (R > anls::WLARGE)
+        return fail(CMF_ERR_UNSUPPORTED, "separable: the NNLS step solves R = K*L <= %d unknowns per column (option \"nnls_large\"; R = %lld)", anls::WLARGE, (long long)R);
     for (int64_t r = 0; r < R; ++r)
         if (vertices[r] < 0 || vertices[r] >= T) return fail(CMF_ERR_ARG, "separable: vertex %lld is not a column of the data (T = %lld)", (long long)vertices[r], (long long)T);
     hipStream_t st = h->stream;
@@ -211,9 +218,13 @@ int cmf_sep_nnls(cmf_handle h, int64_t *vertices, int64_t R, double *V, double *
         // G = nonneg_lsq(V, data) (:26) on the normal equations V'V g = V'data[:, t], all T columns sharing the Gram
         CMFTRY((fp64_gemm<false, false>(s, st, RULE, RowMajor{s->Vd, N}, ColMajor{s->Vd, N}, EpiStore{s->Gram, R, 0.0}, R, R, N, false)));
         CMFTRY((fp64_gemm<false, false>(s, st, RULE, RowMajor{s->Vd, N}, ColMajor{s->data, N}, EpiStore{s->C, T, 0.0}, R, T, N, false)));
-        hipLaunchKernelGGL(anls::anls_nnls_w_kernel, dim3((unsigned)T), dim3(256), 0, st, s->Gram, s->C, s->Gd, (int)R, T, SEP_NNLS_TOL, anls::anls_round_cap((int)R, 0), 0,
-                           s->st);
-        KCHK("anls_nnls_w_kernel");
+        if (large) {
+            CMFTRY(anls::nnls_large(&s->large, st, RULE, s->Gram, s->C, s->Gd, (int)R, T, SEP_NNLS_TOL, 0, s->st));
+        } else {
+            hipLaunchKernelGGL(anls::anls_nnls_w_kernel, dim3((unsigned)T), dim3(256), 0, st, s->Gram, s->C, s->Gd, (int)R, T, SEP_NNLS_TOL,
+                               anls::anls_round_cap((int)R, 0), 0, s->st);
+            KCHK("anls_nnls_w_kernel");
+        }
         HIPCHK(hipMemcpyAsync(s->host->st, s->st, sizeof(s->host->st), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return CMF_OK;

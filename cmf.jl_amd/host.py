@@ -691,7 +691,9 @@ class ANLSUpdate(_Fp64Rule):
     HEAD's fit_cnmf takes, model.jl:60); the name ``":anls"`` is not mapped.
 
     After a call, ``last_W_exchanges`` / ``last_H_exchanges`` hold the pivoting rounds of the NNLS solver summed over the call's
-    problems (cmf_get_counter "anls_W_exchanges" / "anls_H_exchanges").  One GPU only; K*L <= 128 and K <= 64.
+    problems (cmf_get_counter "anls_W_exchanges" / "anls_H_exchanges").  One GPU only; K <= 64, and K*L <= 128 unless
+    ``set_option("nnls_large", 1)`` (or ``fit_cnmf(..., options={"nnls_large": 1})``) lets ``update_motifs`` solve up to
+    K*L = 1024 unknowns per unit through device scratch (129 and more are refused without it; up to 128 nothing changes).
     """
 
     last_W_exchanges = last_H_exchanges = 0
@@ -733,9 +735,9 @@ class ANLSUpdate(_Fp64Rule):
         return loss.value
 
     def set_option(self, name, value):
-        if name != "anls_backup_only":
-            raise NotImplementedError(f"ANLSUpdate has one library option, 'anls_backup_only' (got {name!r}): the other names of "
-                                      "cmf_set_option select paths of the other rules")
+        if name not in ("anls_backup_only", "nnls_large"):
+            raise NotImplementedError(f"ANLSUpdate has the library options 'anls_backup_only' and 'nnls_large' (got {name!r}): the "
+                                      "other names of cmf_set_option select paths of the other rules")
         check(self._lib.cmf_set_option(self._h, name.encode(), int(value)))
 
 
@@ -881,6 +883,12 @@ class Separable(_Fp64Rule):
             raise ValueError(f"pre must be None, ':svd' or ':svdcond', got {pre!r}")
         return name
 
+    def set_option(self, name, value):
+        if name != "nnls_large":
+            raise NotImplementedError(f"Separable has one library option, 'nnls_large' (got {name!r}): the other names of "
+                                      "cmf_set_option select paths of the other rules")
+        check(self._lib.cmf_set_option(self._h, name.encode(), int(value)))
+
     def projection(self, R, thresh, pre):
         """The R x N matrix that pre_svd / pre_svdcond (separable.jl:323-333) multiply X by, from the eigen-decomposition of
         X X' (cmf_sep_gram): U' for :svd (= Diagonal(S) * Vt), S^-1 U' for :svdcond (= Vt).  SPA is invariant under the sign of a
@@ -956,14 +964,17 @@ class Separable(_Fp64Rule):
 
 
 def separable_fit(data, K, L, thresh=0, verbose=False, refit_H=False, refit_W=False, refit_H_itr=10, spectral=False, pre=None,
-                  device=None, stages=None, **kwargs):
+                  device=None, stages=None, nnls_large=False, **kwargs):
     """Separable.fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false,
     pre=nothing) -> (W, H): separable.jl:14-56.  ``verbose`` is accepted and plots nothing.  ``refit_W`` is
     ANLSUpdate.update_motifs (fp64), ``refit_H`` is ``refit_H_itr`` H sweeps of the HALS rule with l1H = l2H = 0 (fp32, like
-    that rule).  ``stages`` (a dict) receives vertices, V, G, P, head and groups.  One GPU; K*L <= 128."""
+    that rule).  ``stages`` (a dict) receives vertices, V, G, P, head and groups.  One GPU; K*L <= 128, or K*L <= 1024 with
+    ``nnls_large=True`` (the option "nnls_large" on the NNLS step and on the ANLSUpdate of ``refit_W``)."""
     data = farr(data)
     rule = Separable(data, K, L, device=device)
     try:
+        if nnls_large:
+            rule.set_option("nnls_large", 1)
         vertices = rule.spa(thresh=thresh, pre=pre)  # step 1 (:22-23)
         V, G = rule.nnls(vertices)  # step 2 (:26-27)
         P, head = rule.shift_table(G)
@@ -976,6 +987,8 @@ def separable_fit(data, K, L, thresh=0, verbose=False, refit_H=False, refit_W=Fa
     if refit_W:  # :41-43
         anls = ANLSUpdate(data, W, H, device=device)
         try:
+            if nnls_large:
+                anls.set_option("nnls_large", 1)
             anls.update_motifs(data, W, H)
         finally:
             anls.close()
@@ -1079,7 +1092,8 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "loss_func", "constrW", "constrH", "penaltiesW", "penaltiesH",  # PGDUpdate (pgd.jl:158-202)
              "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH",  # ADMMUpdate (admm.jl:24-27,124-127)
              "variant",  # ANLSUpdate (anls.jl:26)
-             "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre"}  # alg=:sep (separable.jl:14-18)
+             "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
+             "nnls_large"}  # alg=:sep: separable_fit's switch for K*L > 128
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -1126,7 +1140,7 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         # the loss of the fit and the wall time it took; max_itr, max_time, W_init and H_init do not apply.
         if devices is not None:
             raise NotImplementedError("devices=[...] (T sharding) is not available for alg=:sep: the separable fit runs on one GPU")
-        sep_kw = {k: kw[k] for k in ("thresh", "verbose", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre") if k in kw}
+        sep_kw = {k: kw[k] for k in ("thresh", "verbose", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre", "nnls_large") if k in kw}
         t0 = time.time()
         W, H = separable_fit(data, K, L, device=device, **sep_kw)
         dur = time.time() - t0

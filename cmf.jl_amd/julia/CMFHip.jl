@@ -378,7 +378,8 @@ end
 Drop-in for `ANLSUpdate(data, W, H)` (src/algs/anls.jl:10-14), computed in fp64 on one GPU, on the K x N x L layout of W.  Not in
 `ALGORITHMS`: select it by type (`fit_cnmf(data; alg=HIPANLSUpdate, variant=:block)`, model.jl:60).  `update_motifs!` reads H and
 overwrites W with the exact minimiser over W >= 0; `update_feature_maps!` overwrites H column by column (`variant=:basic`) or in
-L phases of independent columns (`variant=:block`).  K*L <= 128, K <= 64.
+L phases of independent columns (`variant=:block`).  K <= 64; K*L <= 128, or K*L <= 1024 after
+`set_option!(rule, "nnls_large", 1)` (`update_motifs!` then solves 129 and more unknowns per unit through device scratch).
 """
 mutable struct HIPANLSUpdate <: AbstractCFUpdate
     handle::Ptr{Cvoid}
@@ -436,6 +437,9 @@ end
 "Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", ..."
 set_option!(rule::HIPMultUpdate, name::AbstractString, value::Integer) =
     check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), rule.handle, name, value))
+"The ANLS rule's options: \"anls_backup_only\", \"nnls_large\" (include/cmf_hip.h, the ANLS rule)."
+set_option!(rule::HIPANLSUpdate, name::AbstractString, value::Integer) =
+    check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), rule.handle, name, value))
 
 "Library identification: \"cmf_hip gfx950 <version> abi=<n> src=<digest of the sources it was built from>\"."
 version() = unsafe_string(ccall((:cmf_version, LIBCMF), Cstring, ()))
@@ -487,16 +491,17 @@ end
 
 """
     HIPSeparable.fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false,
-                     pre=nothing, device=LOCAL_RANK or 0) -> W, H
+                     pre=nothing, nnls_large=false, device=LOCAL_RANK or 0) -> W, H
 
 Drop-in for `Separable.fit` (src/algs/separable.jl:14-56) in fp64 on one GPU, on the K x N x L layout of W.  The four device stages
 are `cmf_sep_spa`, `cmf_sep_nnls`, `cmf_sep_shift_table` and `cmf_sep_construct`; the grouping and sorting of the K*L rows
-(separable.jl:96-131, :191-270) run here on the shift table.  K*L <= 128.  Row and column numbers are 0-based on the C side.
+(separable.jl:96-131, :191-270) run here on the shift table.  K*L <= 128, or K*L <= 1024 with `nnls_large=true` (the library option
+"nnls_large" on the NNLS step and on the rule of `refit_W`).  Row and column numbers are 0-based on the C side.
 """
 module HIPSeparable
 
 using LinearAlgebra
-import ..CMFHip: LIBCMF, check, HIPANLSUpdate, HIPHALSUpdate, update_motifs!, update_feature_maps!
+import ..CMFHip: LIBCMF, check, HIPANLSUpdate, HIPHALSUpdate, update_motifs!, update_feature_maps!, set_option!
 
 cos_ab(P, head, a, b) = (P[a, b, :] ./ (head[a, :] .* head[b, 1]), P[b, a, :] ./ (head[a, 1] .* head[b, :]))
 
@@ -554,7 +559,7 @@ function projection(handle, N, R, thresh, pre)  # pre_svd / pre_svdcond (separab
 end
 
 function fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, refit_H_itr=10, spectral=false, pre=nothing,
-             device::Integer=parse(Int, get(ENV, "LOCAL_RANK", "0")), kwargs...)
+             nnls_large::Bool=false, device::Integer=parse(Int, get(ENV, "LOCAL_RANK", "0")), kwargs...)
     pre in (nothing, :svd, :svdcond) || throw(ArgumentError("pre must be nothing, :svd or :svdcond"))
     d = Matrix{Float64}(data)
     N, T = size(d)
@@ -564,6 +569,7 @@ function fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, 
     W, H = zeros(K, N, L), zeros(K, T)
     try
         check(ccall((:cmf_sep_prepare, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], d))
+        nnls_large && check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), h[], "nnls_large", 1))
         proj = pre === nothing ? Ptr{Float64}(C_NULL) : projection(h[], N, R, Float64(thresh), pre)
         vertices = zeros(Int64, R)
         check(ccall((:cmf_sep_spa, LIBCMF), Cint, (Ptr{Cvoid}, Int64, Float64, Cint, Ptr{Float64}, Ptr{Int64}),
@@ -583,7 +589,11 @@ function fit(data, K, L; thresh=0, verbose=false, refit_H=false, refit_W=false, 
     finally
         ccall((:cmf_destroy, LIBCMF), Cint, (Ptr{Cvoid},), h[])
     end
-    refit_W && update_motifs!(HIPANLSUpdate(d, W, H; device=device), d, W, H)   # separable.jl:41-43
+    if refit_W                                                                    # separable.jl:41-43
+        anls = HIPANLSUpdate(d, W, H; device=device)
+        nnls_large && set_option!(anls, "nnls_large", 1)
+        update_motifs!(anls, d, W, H)
+    end
     if refit_H                                                                    # separable.jl:46-52
         rule = HIPHALSUpdate(d, W, H; device=device)
         for itr in 1:refit_H_itr

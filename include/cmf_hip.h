@@ -67,7 +67,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_sep.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_internal.h, cmf_kernels.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -456,13 +456,20 @@ int cmf_admm_update_feature_maps(cmf_handle h, const double *W, double *H, doubl
  * kind; "anls_backup" = problems of the last call that took the backup rule; "anls_capped" = problems of the last call that hit
  * the cap.
  *
+ * cmf_set_option(h, "nnls_large", 1) (default 0; cmf_option_names does not list it either): cmf_anls_update_motifs and
+ * cmf_sep_nnls solve problems of 129 .. 1024 unknowns, which they otherwise refuse, with the same solver -- the same exchange
+ * rules, cap, tol, counters and failure behaviour -- whose factorisation runs blocked through device scratch (persistent
+ * workgroups, one slab each; csrc/cmf_nnls_large.h).  The scratch is allocated by the first call that needs it and freed with
+ * the handle's state; if it cannot be allocated the call returns CMF_ERR_HIP.  Problems of up to 128 unknowns run as with 0, bit
+ * for bit.  Single-GPU handles only; any value but 0 or 1 is CMF_ERR_ARG.
+ *
  * ANLSUpdate(data, W, H) (src/algs/anls.jl:10-14): uploads `data` (N x T, fp64) and keeps norm(data); allocates the rule's fp64
  * state on the handle's device.  (The residual the constructor forms is recomputed by every update_feature_maps!, anls.jl:27.) */
 int cmf_anls_prepare(cmf_handle h, const double *data);
 /* update_motifs!(rule::ANLSUpdate, data, W, H)  src/algs/anls.jl:22-24, :47-57.  Reads H (K x T) only and overwrites W (K x N x L)
  * with argmin_{W >= 0} |data - conv(W, H)|: N independent problems of K*L unknowns on G = Hstk*Hstk', C = Hstk*data', one
- * workgroup each, the passive-set Gram factorised in LDS.  K*L <= 128 (CMF_ERR_UNSUPPORTED beyond: nothing runs through global
- * scratch). */
+ * workgroup each, the passive-set Gram factorised in LDS.  K*L <= 128 (CMF_ERR_UNSUPPORTED beyond), or K*L <= 1024 under the option
+ * "nnls_large" (above), where 129 and more unknowns are factorised through global scratch. */
 int cmf_anls_update_motifs(cmf_handle h, const double *H, double *W);
 /* update_feature_maps!(rule::ANLSUpdate, data, W, H; variant=:basic) -> loss  src/algs/anls.jl:26-36, :63-137.  Reads W and H,
  * overwrites H; *loss (may be NULL) = norm(conv(W, H) - data) / norm(data) of the new H (anls.jl:35).  variant 0 (:basic,
@@ -494,7 +501,8 @@ int cmf_sep_gram(cmf_handle h, double thresh, double *XXt);
  * (fewer than R independent columns) is CMF_ERR_UNSUPPORTED. */
 int cmf_sep_spa(cmf_handle h, int64_t R, double thresh, int pre, const double *proj, int64_t *vertices);
 /* V = data[:, vertices]; G = nonneg_lsq(V, data); renormalize!(V, G)  separable.jl:23-27, :340-348.  V: N x R, G: R x T.  The T
- * problems share V'V and run in the solver of cmf_anls_update_motifs (tol 1e-8): R <= 128 (CMF_ERR_UNSUPPORTED beyond), the same
+ * problems share V'V and run in the solver of cmf_anls_update_motifs (tol 1e-8): R <= 128 (CMF_ERR_UNSUPPORTED beyond; R <= 1024
+ * under the option "nnls_large" of the ANLS rule), the same
  * refusal of a non-positive pivot or a capped problem, V and G untouched on failure.  `vertices` is read only. */
 int cmf_sep_nnls(cmf_handle h, int64_t *vertices, int64_t R, double *V, double *G);
 /* What shift_cos / cosL (separable.jl:364-385) are made of, for shift_cluster (:144-150) and sort_group (:100-105):
