@@ -216,7 +216,7 @@ static void destroy_impl(cmf_handle_s *h)
     (void)hipSetDevice(h->device);
     float *fbufs[] = {h->H, h->Ht, h->Wt, h->Wn, h->X, h->XT, h->est, h->estT, h->wslabs, h->numden_own, h->hslabs,
                       h->halo_own[0], h->halo_own[1], h->halo_own[2], h->halo_own[3],
-                      h->gram_numden_h, h->pgd_gradH, h->M, h->MT, h->hals_snap, h->hals_HX, h->hals_cslabs, h->hals_C, h->hals_HH, h->hals_PT, h->hals_D, h->hals_PW, h->hals_GW, h->hals_GE, h->hals_GWt};
+                      h->gram_numden_h, h->pgd_gradH, h->M, h->MT, h->Xm, h->XmT, h->hals_snap, h->hals_HX, h->hals_cslabs, h->hals_C, h->hals_HH, h->hals_PT, h->hals_D, h->hals_PW, h->hals_GW, h->hals_GE, h->hals_GWt};
     for (float *p : fbufs)
         if (mine(p)) (void)hipFree(p);
     for (int v = 0; v < 3; ++v)
@@ -423,7 +423,8 @@ int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, i
 int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, int nsrc, float *slabs, int nchunks, int chunk_len,
                          int main_rows)
 {
-    ProfScope prof_(h, (nsrc == 2 && X0 == h->X) ? PROF_HXT : (nsrc == 1 && X0 == h->X) ? PROF_HXT_NUM : (nsrc == 1 && X0 == h->est && h->est_kind == 1) ? PROF_HXT_DEN
+    const bool x0_data = X0 == mu_X(h);
+    ProfScope prof_(h, (nsrc == 2 && x0_data) ? PROF_HXT : (nsrc == 1 && x0_data) ? PROF_HXT_NUM : (nsrc == 1 && X0 == h->est && h->est_kind == mu_est_kind(h)) ? PROF_HXT_DEN
                           : (nsrc == 1 && X0 == h->est) ? PROF_HXT_RESID : (X0 == h->hals_HX && h->hals_HX) ? PROF_HXT_HH : PROF_OTHER);
     const CmfDims &d = h->d;
     h->spec_gen = -1; // (the slabs of a speculated contraction are being overwritten)
@@ -542,20 +543,26 @@ static int check_ready(cmf_handle_s *h, bool need_data)
 // update_feature_maps! before): est is current and nothing has touched H, W, est or the slabs since.
 static bool w_speculated(cmf_handle_s *h)
 {
-    const bool hit = h->spec_gen >= 0 && h->spec_gen == h->est_gen && h->reuse_est && h->est_kind == 1 && !h->carry.partial;
+    const bool hit = h->spec_gen >= 0 && h->spec_gen == h->est_gen && h->reuse_est && h->est_kind == mu_est_kind(h) && !h->carry.partial;
     h->spec_gen = -1;
     if (hit) h->spec_hits += 1;
     return hit;
+}
+
+// est = tensor_conv(W, H) in the [t][n] layout (mult.jl:28); under the MU rule's mask: mask .* est
+static int mu_conv_est(cmf_handle_s *h)
+{
+    return h->mu_mask ? launch_conv<8>(h, h->est, h->d.Tl, h->conv_gy) : launch_conv<0>(h, h->est, h->d.Tl, h->conv_gy);
 }
 
 int w_partial_impl(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
     if (w_speculated(h)) return CMF_OK;
-    if (!(h->reuse_est && h->est_kind == 1))
-        CMFTRY(launch_conv<0>(h, h->est, d.Tl, h->conv_gy)); // mult.jl:28 (skipped when est is still current)
-    set_est(h, 1);
-    return hxt_contract(h, h->X, h->est, 2, h->numden, true); // mult.jl:31-34
+    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)))
+        CMFTRY(mu_conv_est(h)); // mult.jl:28 (skipped when est is still current)
+    set_est(h, mu_est_kind(h));
+    return hxt_contract(h, mu_X(h), h->est, 2, h->numden, true); // mult.jl:31-34
 }
 
 // The two halves of w_partial_impl as separate steps (same arithmetic, the sources contracted one at a time): the
@@ -592,10 +599,10 @@ static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
         return w_apply_impl(h, l1W, l2W);
     }
     if (!w_speculated(h)) {
-        if (!(h->reuse_est && h->est_kind == 1))
-            CMFTRY(launch_conv<0>(h, h->est, d.Tl, h->conv_gy)); // mult.jl:28 (skipped when est is still current)
-        set_est(h, 1);
-        CMFTRY(hxt_contract(h, h->X, h->est, 2, nullptr, false, true)); // mult.jl:31-34: the slabs only
+        if (!(h->reuse_est && h->est_kind == mu_est_kind(h)))
+            CMFTRY(mu_conv_est(h)); // mult.jl:28 (skipped when est is still current)
+        set_est(h, mu_est_kind(h));
+        CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, nullptr, false, true)); // mult.jl:31-34: the slabs only
     }
     CmfLossCarry carry{};
     if (h->carry.partial) { // a loss reduction deferred by cmf_iterate rides on this launch
@@ -645,14 +652,15 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         set_est(h, 0);
         return wb_after_H(h);
     }
-    CMFTRY(launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
+    if (h->mu_mask) CMFTRY(launch_conv<9>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // (mask .* est)' under the MU rule's mask
+    else CMFTRY(launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
     if (sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
-        CMFTRY(launch_transconv_small(h, 2, nullptr, true, (float)l1H, (float)(2.0 * l2H)));
+        CMFTRY(launch_transconv_small(h, 2, mu_XT(h), true, (float)l1H, (float)(2.0 * l2H)));
         ++h->sk_fused_h;
         set_est(h, 0);
         return wb_after_H(h);
     }
-    CMFTRY(launch_transconv(h, 2));                                         // mult.jl:47-48
+    CMFTRY(launch_transconv(h, 2, mu_XT(h)));                               // mult.jl:47-48
     dim3 grid((d.Tl + HUPD_T - 1) / HUPD_T, d.KB);
     const size_t TK = (size_t)d.Tl * d.K32;
     hipLaunchKernelGGL(h_update_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs, 2 * TK, h->tc_S, h->hslabs + TK, 2 * TK, h->tc_S,
@@ -666,6 +674,12 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
 int launch_loss_conv(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
+    if (h->mu_mask) { // the sum of (mask .* (est - data))^2; mask .* est kept when est is reused
+        if (!h->reuse_est) return launch_conv<10>(h, nullptr, d.Tl, h->conv_gy);
+        CMFTRY(launch_conv<11>(h, h->est, d.Tl, h->conv_gy));
+        set_est(h, 6);
+        return CMF_OK;
+    }
     if (h->reuse_est && !h->gram) { // (the Gram form never reads est: nothing to keep)
         CMFTRY(launch_conv<3>(h, h->est, d.Tl, h->conv_gy)); // est kept for the next update_motifs!
         set_est(h, 1);
@@ -681,9 +695,9 @@ int launch_loss_conv(cmf_handle_s *h)
 // (the call before this one was update_motifs!); a caller that stops pays one contraction nobody reads.
 static int w_speculate(cmf_handle_s *h)
 {
-    if (!(h->reuse_est && h->est_kind == 1) || h->gram || h->group || h->carry.partial) return CMF_OK;
-    if (h->small_k) CMFTRY(hxt_contract(h, h->X, h->est, 2, nullptr, false, true));
-    else CMFTRY(hxt_contract(h, h->X, h->est, 2, h->numden, true));
+    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)) || h->gram || h->group || h->carry.partial) return CMF_OK;
+    if (h->small_k) CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, nullptr, false, true));
+    else CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, h->numden, true));
     h->spec_gen = h->est_gen;
     return CMF_OK;
 }
@@ -1333,6 +1347,8 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
     if (std::strcmp(name, "gram") == 0) {
         if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "gram must be 0, 1 or 2");
         if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
+        if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
+                                                                  "which is not a product of Gram matrices): clear the mask of cmf_mu_set_mask first");
         h->gram = value;
         set_est(h, 0);
         return CMF_OK;
@@ -1485,7 +1501,7 @@ static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double
     CMFTRY(h_update_impl(h, l1H, l2H));
     double ss = 0.0;
     CMFTRY(loss_partial_impl(h, &ss, true, nullptr, speculate));
-    *loss = std::sqrt(ss) / h->data_norm;
+    *loss = std::sqrt(ss) / mu_norm(h);
     return CMF_OK;
 }
 
@@ -1572,7 +1588,7 @@ int cmf_compute_loss(cmf_handle h, double *loss)
     CMFTRY(check_ready(h, true));
     double ss = 0.0;
     CMFTRY(loss_partial_impl(h, &ss));
-    *loss = std::sqrt(ss) / h->data_norm;
+    *loss = std::sqrt(ss) / mu_norm(h);
     return CMF_OK;
 }
 
@@ -1580,6 +1596,7 @@ int cmf_hals_update_motifs(cmf_handle h, double l1W, double l2W)
 {
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     CMFTRY(check_ready(h, true));
+    if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
     h->last_rule_call = 1;
     return hals_w_impl(h, l1W, l2W);
 }
@@ -1589,6 +1606,7 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     if (!loss) return fail(CMF_ERR_ARG, "loss is NULL");
     CMFTRY(check_ready(h, true));
+    if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates (alternating.jl:51-54): update_motifs! comes next
     h->last_rule_call = 2;
     CMFTRY(hals_h_impl(h, l1H, l2H));
@@ -1619,6 +1637,101 @@ int cmf_hals_update_feature_maps(cmf_handle h, double l1H, double l2H, double *l
     return wb_finish(h, hals_update_feature_maps_body(h, l1H, l2H, loss));
 }
 
+// The MU entries leave the masked rule: est, the speculated contraction and a deferred loss are void, the masked copies of data freed.
+static int mu_mask_off(cmf_handle_s *h)
+{
+    drop_carry(h);
+    h->spec_gen = -1;
+    set_est(h, 0);
+    if (!h->mu_mask && !h->Xm && !h->XmT) return CMF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->Xm) (void)hipFree(h->Xm);
+    if (h->XmT) (void)hipFree(h->XmT);
+    h->Xm = h->XmT = nullptr;
+    h->mu_mask = false;
+    h->xm_sumsq = h->xm_norm = 0.0;
+    return CMF_OK;
+}
+
+// sum over the flat [TP][Np] array of select(mask, data, 0)^2 (comp: mask == 0), optionally writing the masked copies (mask_select_kernel)
+static int mask_select(cmf_handle_s *h, bool write, int comp, double *sumsq)
+{
+    const CmfDims &d = h->d;
+    const size_t n4 = (size_t)d.TP * d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
+    hipLaunchKernelGGL(mask_select_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, write ? h->Xm : nullptr, write ? h->XT : nullptr,
+                       write ? h->MT : nullptr, write ? h->XmT : nullptr, n4, comp, h->partial);
+    KCHK("mask_select_kernel");
+    std::vector<double> part((size_t)nb);
+    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (double v : part) s += v;
+    *sumsq = s;
+    return CMF_OK;
+}
+
+int cmf_mu_set_mask(cmf_handle h, const double *mask)
+{
+    if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
+    if (h->group || h->root_only || h->sharded)
+        return fail(CMF_ERR_UNSUPPORTED, "the masked MU rule runs on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
+    if (h->wb && h->wb->armed) wb_disarm(h);
+    if (!mask) { // the unmasked rule again; the mask itself goes too
+        CMFTRY(mu_mask_off(h));
+        if (h->M) (void)hipFree(h->M);
+        if (h->MT) (void)hipFree(h->MT);
+        h->M = h->MT = nullptr;
+        return CMF_OK;
+    }
+    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
+                                                  "which is not a product of Gram matrices; set gram = 0 first");
+    const CmfDims &d = h->d;
+    const size_t NT = (size_t)d.N * d.Tl;
+    size_t ones = 0;
+    for (size_t i = 0; i < NT; ++i) {
+        if (mask[i] == 1.0) ++ones;
+        else if (!(mask[i] == 0.0))
+            return fail(CMF_ERR_ARG, "the MU rule takes a mask of 0 and 1 only (entry %zu is %g); real-valued weights exist for the PGD rule (cmf_set_mask)", i, mask[i]);
+    }
+    if (ones == 0) return fail(CMF_ERR_ARG, "the mask observes nothing (every entry is 0)");
+    CMFTRY(mu_mask_off(h));
+    const size_t TPNp = (size_t)d.TP * d.Np;
+    if (!h->M) CMFTRY(dalloc_zero(&h->M, TPNp));
+    if (!h->MT) CMFTRY(dalloc_zero(&h->MT, TPNp));
+    CMFTRY(upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT));
+    CMFTRY(dalloc_zero(&h->Xm, TPNp));
+    CMFTRY(dalloc_zero(&h->XmT, TPNp));
+    CMFTRY(mask_select(h, true, 0, &h->xm_sumsq));
+    h->xm_norm = std::sqrt(h->xm_sumsq);
+    h->mu_mask = true;
+    set_est(h, 0);
+    return CMF_OK;
+}
+
+int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *data_sumsq)
+{
+    if (!h || !resid_sumsq || !data_sumsq) return fail(CMF_ERR_ARG, "NULL argument");
+    if (h->group || h->root_only || h->sharded)
+        return fail(CMF_ERR_UNSUPPORTED, "cmf_masked_loss runs on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
+    CMFTRY(check_ready(h, true));
+    if (!h->M || !h->MT) return fail(CMF_ERR_STATE, "no mask installed: call cmf_mu_set_mask or cmf_set_mask first");
+    if (h->carry.partial) return fail(CMF_ERR_STATE, "internal: a deferred loss reduction is pending"); // (cmf_iterate leaves none behind)
+    const bool comp = complement != 0;
+    // One loss-only conv (nothing stored: est, the factors and the rule's state stay as they are) on the raw data with the mask as a
+    // select, then the same select on data^2.  Both use the loss partials, one after the other on the stream.
+    h->mask_complement_now = comp ? 1 : 0;
+    const int rc = launch_conv<10>(h, nullptr, h->d.Tl, h->conv_gy);
+    h->mask_complement_now = 0;
+    CMFTRY(rc);
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, h->conv_partials, h->d_scalar + 1, (double *)nullptr);
+    KCHK("loss_reduce_kernel");
+    CMFTRY(read_scalar(h, 1, resid_sumsq));
+    return mask_select(h, false, comp ? 1 : 0, data_sumsq);
+}
+
 int cmf_set_mask(cmf_handle h, const double *mask)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
@@ -1627,6 +1740,7 @@ int cmf_set_mask(cmf_handle h, const double *mask)
     if (h->sharded) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
     const CmfDims &d = h->d;
     set_est(h, 0);
+    CMFTRY(mu_mask_off(h)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
     if (!mask) { // back to the plain SquareLoss
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->M) (void)hipFree(h->M);
@@ -1734,7 +1848,7 @@ static int iterate_single(cmf_handle_s *h, int64_t n, int eval_mode, double l1W,
         const unsigned long long bits = ring[slot];
         double ss;
         std::memcpy(&ss, &bits, 8);
-        losses[it] = std::sqrt(ss) / h->data_norm;
+        losses[it] = std::sqrt(ss) / mu_norm(h);
         if (stamps) stamps[it] = now();
         return CMF_OK;
     };

@@ -260,10 +260,16 @@ struct cmf_handle_s {
     // PGD rule state (pgd.jl:139-154)
     double pgd_stepW = 5.0, pgd_stepH = 5.0, pgd_cur_loss = -1.0;
     float *pgd_gradH = nullptr;
+    int mask_complement_now = 0; // cmf_masked_loss: the loss-only masked conv being launched sums over mask == 0
     int pgd_loss_abs_now = 0;  // loss kind of the residual conv being launched (set by resid_and_loss / the PGD H phase)
     int pgd_loss_abs = 0;      // 0 SquareLoss (pgd.jl:29-36), 1 AbsoluteLoss (pgd.jl:41-47)
     double *pgd_knorm = nullptr; // [K32] per-component sums of squares of UnitNormConstraint (pgd.jl:100-110)
     float *M = nullptr, *MT = nullptr; // mask of MaskedLoss (pgd.jl:58-70) in the layouts of X and XT; null = no mask
+    // the MU rule under that mask (cmf_mu_set_mask): M / MT hold 0 and 1, Xm / XmT = select(mask, data, 0) in the layouts of X and XT,
+    // and the MU entries contract Xm and mask .* est (est_kind 6) where they contract data and est; cmf_set_mask switches it off again
+    bool mu_mask = false;
+    float *Xm = nullptr, *XmT = nullptr;
+    double xm_sumsq = 0.0, xm_norm = 0.0; // sum of Xm^2 and its root: what the masked MU loss is divided by
 
     double data_sumsq = 0.0, data_norm = 0.0;
     bool factors_set = false;
@@ -281,7 +287,8 @@ struct cmf_handle_s {
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
     int est_kind = 0;       // what est[t][n] holds for the resident W, H: 0 nothing, 1 tensor_conv(W,H), 2 tensor_conv(W,H) - data, 3 mask .* (tensor_conv(W,H) - data),
-                            // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient)
+                            // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient), 6 mask .* tensor_conv(W,H) (the MU rule
+                            // under a mask: mu_est_kind)
     void *arena = nullptr;  // the small buffers of the handle as ONE device allocation (cmf_create): 21 hipFree calls cost 1.3 ms, one 0.16
     size_t arena_bytes = 0;
     bool streams_may_hang = false;  // set on the shards of a FAILED group: their streams are not waited for when they are given back
@@ -477,6 +484,12 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
     h->est_kind = kind;
     ++h->est_gen;
 }
+// What the MU entries read for data / data' / "est is current", and what their loss is divided by: the masked copies while a mask of
+// cmf_mu_set_mask is installed.  reuse_est, the speculated C2 contraction and the deferred loss carry all compare against mu_est_kind.
+static inline const float *mu_X(const cmf_handle_s *h) { return h->mu_mask ? h->Xm : h->X; }
+static inline const float *mu_XT(const cmf_handle_s *h) { return h->mu_mask ? h->XmT : h->XT; }
+static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? 6 : 1; }
+static inline double mu_norm(const cmf_handle_s *h) { return h->mu_mask ? h->xm_norm : h->data_norm; }
 int wb_after_H(cmf_handle_s *h); // hook: the kernels that make H final have been enqueued (cmf_writeback.h)
 int gram_ensure(cmf_handle_s *h);
 int hals_w_impl(cmf_handle_s *h, double l1W, double l2W);
@@ -612,14 +625,16 @@ struct ProfScope {
 template <int MODE>
 static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
 {
-    ProfScope prof_(h, MODE == 0 ? PROF_CONV : MODE == 1 ? PROF_CONV_T : MODE == 2 ? PROF_CONV_LOSS : MODE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
+    constexpr int BASE = MODE >= 8 ? MODE - 8 : MODE; // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask (cmf_kernels.h)
+    ProfScope prof_(h, BASE == 0 ? PROF_CONV : BASE == 1 ? PROF_CONV_T : BASE == 2 ? PROF_CONV_LOSS : BASE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
+    if (MODE >= 8 && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
     p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : h->X; p.partial = h->partial;
-    p.mask = (MODE == 7) ? h->MT : h->M;
+    p.mask = (MODE == 7 || MODE == 9) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
-    p.loss_abs = (MODE >= 4) ? h->pgd_loss_abs_now : 0;
+    p.loss_abs = (MODE >= 4 && MODE <= 7) ? h->pgd_loss_abs_now : (MODE == 10 ? h->mask_complement_now : 0);
     dim3 grid(h->conv_gx, gy), block(256);
     // measured at config 2 (tools/time_kernels.py): the one-wave kernel wins for the epilogues that read data
     // (0.924 vs 0.931 ms loss only, 0.936 vs 0.943 ms loss + store), the 128 x 128 tiles for the store-only ones
@@ -654,8 +669,8 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
             const int n_full = tiles3 - cutq;
             grid = dim3(n_full + 4 * cutq);
             // (loss + store on a short launch: the data tile is requested before the MFMA loop, conv3_tile)
-            const bool pre = MODE == 3 && nkp <= 4 && tiles3 <= 4 * per_round;
-#define CASE(NKP_) do { if (pre) hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_, (MODE == 3 && NKP_ <= 4)>), grid, dim3(64), 0, h->stream, p, gx3, n_full); \
+            const bool pre = BASE == 3 && nkp <= 4 && tiles3 <= 4 * per_round;
+#define CASE(NKP_) do { if (pre) hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_, (BASE == 3 && NKP_ <= 4)>), grid, dim3(64), 0, h->stream, p, gx3, n_full); \
                         else hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_>), grid, dim3(64), 0, h->stream, p, gx3, n_full); } while (0)
             if (nkp <= 1) CASE(1); else if (nkp == 2) CASE(2); else if (nkp == 3) CASE(3); else if (nkp == 4) CASE(4);
             else if (nkp <= 6) CASE(6); else CASE(8);
@@ -669,7 +684,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         }
     }
     const bool split = cut > 0;
-    const int variant = (h->conv_variant && MODE <= 2) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
+    const int variant = (h->conv_variant && BASE <= 2) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
     if (d.K % 32 == 0 && variant == 3) {
         const int n_full = tiles3 - cut;
         // quarter tiles reach every SIMD only from one tile per CU on; below that, sixteenth tiles
@@ -682,8 +697,8 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         // the 128 x 128 kernel exists for the epilogues that only store or only sum (est, est', loss): with a data tile
         // read AND a store in the epilogue (mode 3 and the residual modes) it needs more than the 168 registers three
         // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
-        if constexpr (MODE <= 2) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
-        if constexpr (MODE <= 2) h->launches[LA_CONV2] += 1;
+        if constexpr (BASE <= 2) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
+        if constexpr (BASE <= 2) h->launches[LA_CONV2] += 1;
     } else {
         hipLaunchKernelGGL((conv_kernel<MODE, 0>), grid, block, 0, h->stream, p);
         h->launches[LA_CONV] += 1;

@@ -67,6 +67,10 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //   MODE 7: MODE 5 with the residual multiplied by p.mask = maskT [n][t]
 //   (modes 4-7 with p.loss_abs: the stored quantity is the AbsoluteLoss gradient sign(est - data) [.* mask] and the
 //    loss sum is sum |mask .* (est - data)|, pgd.jl:41-47)
+//   MODE 8 .. 11: modes 0 .. 3 of the MU rule under a 0/1 mask (p.mask in the layout of the store: [t][n], MODE 9: maskT [n][t]):
+//     what is stored is mask .* est, what is summed is (mask .* (est - data))^2.  The mask acts as a SELECT (an entry with mask == 0
+//     contributes 0 whatever data holds there, NaN included).  MODE 10 with p.loss_abs != 0 sums over the entries with mask == 0
+//     instead (cmf_masked_loss: the held-out score).
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
@@ -78,7 +82,8 @@ struct ConvParams {
     int Np, TP, PADL, K, KB, L;
     int T_store; // rows t < T_store are stored / counted
     int N;       // columns n >= N are padding: a 32-column MFMA block that lies wholly behind N is not computed (its sums are 0)
-    int loss_abs; // residual modes (4-7) only: 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
+    int loss_abs; // residual modes (4-7): 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
+                  // MODE 10: 1 = the sum runs over the entries with mask == 0 (the complement)
 };
 
 // agent-scope accesses (global_load / global_store ... sc1): the hand-off forms of MI355X_MICROARCH.md "inter-workgroup visibility"
@@ -95,7 +100,10 @@ __device__ __forceinline__ f32x4 cmf_load4_sc1(const float *p)
     return v;
 }
 
-#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7)
+#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9)
+#define CONV_MU_MASKED(MODE) ((MODE) >= 8)                       // the masked forms of modes 0 .. 3
+#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11)
+#define CONV_PGD(MODE) ((MODE) >= 4 && (MODE) <= 7)              // the residual modes (the only ones p.loss_abs = AbsoluteLoss applies to)
 #define CONV_HS_STRIDE 160
 #define CONV_HS_FLOATS (32 * CONV_HS_STRIDE)
 #define CONV_WS_FLOATS (32 * 128)
@@ -117,9 +125,10 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 {
     if (pidx < 0) pidx = blockIdx.y * gridDim.x + blockIdx.x; // slot of this tile's loss partial
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 6);
+    constexpr bool LOSS = CONV_LOSS(MODE);
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
+    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
@@ -141,7 +150,8 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
             // all operand loads of a group first (the W registers are dead by now), then arithmetic and stores: a load
             // queued behind stores would wait for them on the in-order vmcnt.  A group is the whole 64 x 64 sub-tile,
             // or one 32 x 32 block when the mask doubles the operands (the registers do not stretch further).
-            constexpr int GT = MASKED ? 1 : 2; // blocks per group along t and n
+            constexpr int GT = (MASKED || (MUM && LOSS)) ? 1 : 2; // blocks per group along t and n
+            const bool comp = (MODE == 10) && p.loss_abs; // wave-uniform: the sum over the held-out entries
 #pragma unroll
             for (int gt = 0; gt < 2; gt += GT)
 #pragma unroll
@@ -156,7 +166,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                 const int so = (((gt + ti) * 32 + (r & 3) + 8 * (r >> 2)) * Np + (gn + ni) * 32) * 4;
                                 dv[ti][ni][r] = !LOSS ? 0.f : (PRE && !MASKED) ? pre[gt + ti][gn + ni][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
                                                                                : cmf_bload(rd, voff, so); // rows past T_store read as 0 (masked below)
-                                mv[ti][ni][r] = MASKED ? cmf_bload(rm, voff, so) : 1.f;
+                                mv[ti][ni][r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
                             }
 #pragma unroll
                     for (int ti = 0; ti < GT; ++ti)
@@ -168,6 +178,11 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                 const float v = acc[gt + ti][gn + ni][r];
                                 float d = MASKED ? (v - dv[ti][ni][r]) * mv[ti][ni][r] : v - dv[ti][ni][r];
                                 if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, so);
+                                if (MUM) {
+                                    const bool obs = mv[ti][ni][r] != 0.f;
+                                    if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
+                                    d = (obs != comp) ? d : 0.f;
+                                }
                                 if (RESID) {
                                     if (ABS) {
                                         const float sg = (v > dv[ti][ni][r]) ? 1.f : ((v < dv[ti][ni][r]) ? -1.f : 0.f);
@@ -219,7 +234,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
         const __amdgpu_buffer_rsrc_t rm = cmf_rsrc(p.mask + origin, bytes);
         const int voff = (4 * h * TP + i) * 4;
         const bool full = (tw + 64 <= p.T_store); // wave-uniform
-        const bool abs_t = (MODE != 1) && p.loss_abs; // wave-uniform; MODE 1 (the MU path) compiles to the plain store loop
+        const bool abs_t = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; MODE 1 (the MU path) compiles to the plain store loop
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -229,10 +244,10 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                        dv[r] = (MODE != 1) ? cmf_bload(rd, voff, so) : 0.f;
-                        mv[r] = MASKED ? cmf_bload(rm, voff, so) : 1.f;
+                        dv[r] = CONV_PGD(MODE) ? cmf_bload(rd, voff, so) : 0.f;
+                        mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
                     }
-                    if (MODE != 1 && abs_t) { // AbsoluteLoss: the stored quantity is the gradient sign(est - data)
+                    if (CONV_PGD(MODE) && abs_t) { // AbsoluteLoss: the stored quantity is the gradient sign(est - data)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
@@ -244,7 +259,8 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                            cmf_bstore(MASKED ? (acc[ni][ti][r] - dv[r]) * mv[r] : acc[ni][ti][r] - dv[r], ro, voff, so);
+                            if (MUM) cmf_bstore(mv[r] != 0.f ? acc[ni][ti][r] : 0.f, ro, voff, so);
+                            else cmf_bstore(MASKED ? (acc[ni][ti][r] - dv[r]) * mv[r] : acc[ni][ti][r] - dv[r], ro, voff, so);
                         }
                     }
                 }
@@ -560,7 +576,7 @@ __device__ __forceinline__ void conv3_tile(const ConvParams &p, float *Hs, int t
     // HBM round trip per tile; here it is requested before the loop (64 registers that the few k pairs leave free) with the epilogue's
     // descriptor and offsets, and the epilogue finds it there (protocol shape: 37.8 -> 35.8 us).  On a launch of many rounds (N = 2000:
     // eight tiles per SIMD slot, bandwidth-bound) the W rows of the first lags queue behind these 64 loads and it costs 7 %: not used there.
-    constexpr bool PRE = (PREQ && MODE == 3 && NKP <= 4 && NBL == 2);
+    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11) && NKP <= 4 && NBL == 2);
     float dpre[2][2][16];
     if (PRE) {
         int rows = p.T_store - t0;
@@ -617,10 +633,12 @@ template <int MODE>
 __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 6);
+    constexpr bool LOSS = CONV_LOSS(MODE);
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
-    const bool abs_loss = (MODE >= 4) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
+    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
+    const bool abs_loss = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
+    const bool comp = (MODE == 10) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) {
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
@@ -635,7 +653,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
         for (int r = 0; r < 16; ++r) {
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
             dv[r] = LOSS ? cmf_bload(rd, voff, so) : 0.f; // rows past T_store read as 0 (masked below)
-            mv[r] = MASKED ? cmf_bload(rm, voff, so) : 1.f;
+            mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
         }
         float lsum = 0.f;
 #pragma unroll
@@ -644,6 +662,11 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
             const float v = acc[r];
             float d = MASKED ? (v - dv[r]) * mv[r] : v - dv[r];
             if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, so);
+            if (MUM) {
+                const bool obs = mv[r] != 0.f;
+                if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
+                d = (obs != comp) ? d : 0.f;
+            }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
                 cmf_bstore(abs_loss ? (MASKED ? sg * mv[r] : sg) : d, ro, voff, so);
@@ -675,14 +698,15 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
-                dv[r] = (MODE != 1) ? cmf_bload(rd, voff, so) : 0.f;
-                mv[r] = MASKED ? cmf_bload(rm, voff, so) : 1.f;
+                dv[r] = CONV_PGD(MODE) ? cmf_bload(rd, voff, so) : 0.f;
+                mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
                 float d = acc[r] - dv[r];
                 if (abs_loss) d = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+                if (MUM) d = mv[r] != 0.f ? d : 0.f;
                 cmf_bstore(MASKED ? d * mv[r] : d, ro, voff, so);
             }
         }
@@ -795,10 +819,12 @@ template <int MODE>
 __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 6);
+    constexpr bool LOSS = CONV_LOSS(MODE);
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
-    const bool abs_loss = (MODE >= 4) && p.loss_abs;
+    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
+    const bool abs_loss = CONV_PGD(MODE) && p.loss_abs;
+    const bool comp = (MODE == 10) && p.loss_abs; // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
@@ -812,7 +838,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             dv[r] = LOSS ? cmf_bload(rd, voff, r * Np * 4) : 0.f;
-            mv[r] = MASKED ? cmf_bload(rm, voff, r * Np * 4) : 1.f;
+            mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, r * Np * 4) : 1.f;
         }
         float lsum = 0.f;
 #pragma unroll
@@ -820,6 +846,11 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
             const float v = acc[r];
             float d = MASKED ? (v - dv[r]) * mv[r] : v - dv[r];
             if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, r * Np * 4);
+            if (MUM) {
+                const bool obs = mv[r] != 0.f;
+                if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, r * Np * 4);
+                d = (obs != comp) ? d : 0.f;
+            }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
                 cmf_bstore(abs_loss ? (MASKED ? sg * mv[r] : sg) : d, ro, voff, r * Np * 4);
@@ -849,10 +880,11 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
         if (tb + j < p.T_store) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float dvr = (MODE != 1) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
-                const float mvr = MASKED ? cmf_bload(rm, voff, r * TP * 4) : 1.f;
+                const float dvr = CONV_PGD(MODE) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
+                const float mvr = (MASKED || MUM) ? cmf_bload(rm, voff, r * TP * 4) : 1.f;
                 float d = acc[r] - dvr;
                 if (abs_loss) d = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+                if (MUM) d = mvr != 0.f ? d : 0.f;
                 cmf_bstore(MASKED ? d * mvr : d, ro, voff, r * TP * 4);
             }
         }
@@ -3489,6 +3521,44 @@ static __global__ __launch_bounds__(256) void sumsq_f64_kernel(const double *in,
         __syncthreads();
     }
     if (threadIdx.x == 0) out_accum[blockIdx.x] = red[0];
+}
+
+// The MU rule under a 0/1 mask (cmf_mu_set_mask): Xm = select(M != 0, X, 0) in both resident layouts -- the padded [TP][Np] and
+// [Np][TP] arrays are walked flat, mask and data share a layout (padding: M = 0, so Xm = 0) -- and the per-block sums of Xm^2 of the
+// first layout in fp64 (partial[gridDim.x]).  A select, not a product: what data holds under M == 0 (NaN, Inf) never enters.
+// comp != 0: the selected entries are those with M == 0 (cmf_masked_loss's held-out sums; the padding of X is zero and adds nothing).
+// Xm may be NULL (the sums only); XT / MT / XmT may be NULL together.
+static __global__ __launch_bounds__(256) void mask_select_kernel(const float *X, const float *M, float *Xm, const float *XT, const float *MT,
+                                                                 float *XmT, size_t n4, int comp, double *partial)
+{
+    __shared__ double red[256];
+    double s = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * 256) {
+        const float4 x = reinterpret_cast<const float4 *>(X)[idx];
+        const float4 m = reinterpret_cast<const float4 *>(M)[idx];
+        const float xv[4] = {x.x, x.y, x.z, x.w}, mv[4] = {m.x, m.y, m.z, m.w};
+        float o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool sel = comp ? (mv[q] == 0.f) : (mv[q] != 0.f);
+            o[q] = sel ? xv[q] : 0.f;
+            s += (double)o[q] * (double)o[q];
+        }
+        if (Xm) reinterpret_cast<float4 *>(Xm)[idx] = make_float4(o[0], o[1], o[2], o[3]);
+        if (XmT) {
+            const float4 xt = reinterpret_cast<const float4 *>(XT)[idx];
+            const float4 mt = reinterpret_cast<const float4 *>(MT)[idx];
+            reinterpret_cast<float4 *>(XmT)[idx] = make_float4(mt.x != 0.f ? xt.x : 0.f, mt.y != 0.f ? xt.y : 0.f, mt.z != 0.f ? xt.z : 0.f,
+                                                               mt.w != 0.f ? xt.w : 0.f);
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
 // =============================================================================================

@@ -270,16 +270,51 @@ class MultUpdate(AbstractCFUpdate):
         self._check_arrays(W, H)
         check(self._lib.cmf_arm_writeback(self._h, None if W is None else ptr(W), None if H is None else ptr(H)))
 
+    # -- the rule under a mask (cmf_mu_set_mask) -----------------------------------------
+    _mu_mask_key = None  # id() of the mask object the rule methods last installed (None: unmasked)
+    _mu_mask_ref = None  # ... and the object itself, so that its id cannot be reused while it is the key
+
+    def set_mask(self, mask):
+        """Fit under a 0/1 mask (1 = observed): the multiplicative update of norm(mask .* (data - tensor_conv(W, H)))^2
+        (MaskedLoss, pgd.jl:58-70, for this rule).  What ``data`` holds under ``mask == 0`` never enters, NaN included; the loss is
+        norm(mask .* (est - data)) / norm(select(mask, data, 0)).  ``None`` restores the unmasked rule."""
+        if mask is None:
+            check(self._lib.cmf_mu_set_mask(self._h, None))
+            self._mu_mask_key = self._mu_mask_ref = None
+            return
+        m = farr(mask)
+        if m.shape != (self.N, self.T):
+            raise ValueError(f"mask must be {self.N} x {self.T} like data, got {m.shape}")
+        check(self._lib.cmf_mu_set_mask(self._h, ptr(m)))
+        self._mu_mask_key, self._mu_mask_ref = id(mask), mask
+
+    def _select_mask(self, kwargs):
+        """``mask=`` of a rule call: installed when the object changes (compared by identity, like PGDUpdate._select_loss)."""
+        if "mask" not in kwargs:
+            return
+        mask = kwargs["mask"]
+        if (None if mask is None else id(mask)) != self._mu_mask_key:
+            self.set_mask(mask)
+
+    def masked_loss(self, complement=False):
+        """(sum of (tensor_conv(W, H) - data)^2, sum of data^2) over the entries with mask == 1 -- with ``complement`` over those
+        with mask == 0 -- for the resident factors (cmf_masked_loss); est, the factors and the rule's state stay as they are."""
+        r, d = ctypes.c_double(), ctypes.c_double()
+        check(self._lib.cmf_masked_loss(self._h, int(bool(complement)), ctypes.byref(r), ctypes.byref(d)))
+        return r.value, d.value
+
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
-        """update_motifs!(rule, data, W, H; l1W=0, l2W=0): src/algs/mult.jl:23-39."""
+        """update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing): src/algs/mult.jl:23-39."""
+        self._select_mask(kwargs)
         self._sync_args(W, H)
         check(self._lib.cmf_update_motifs(self._h, float(l1W), float(l2W)))
         self._after_motifs(W)
 
     def update_feature_maps(self, data=None, W=None, H=None, l1H=0, l2H=0, **kwargs):
-        """update_feature_maps!(rule, data, W, H; l1H=0, l2H=0) -> loss: src/algs/mult.jl:42-58."""
+        """update_feature_maps!(rule, data, W, H; l1H=0, l2H=0, mask=nothing) -> loss: src/algs/mult.jl:42-58."""
         loss = ctypes.c_double()
+        self._select_mask(kwargs)
         self._sync_args(W, H)
         self._arm_writeback(W, H)
         check(self._lib.cmf_update_feature_maps(self._h, float(l1H), float(l2H), ctypes.byref(loss)))
@@ -1093,7 +1128,8 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "rhow", "rhoh", "admm_W_maxiter", "admm_H_maxiter", "admm_tol", "nonnegW", "nonnegH",  # ADMMUpdate (admm.jl:24-27,124-127)
              "variant",  # ANLSUpdate (anls.jl:26)
              "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
-             "nnls_large"}  # alg=:sep: separable_fit's switch for K*L > 128
+             "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
+             "mask"}  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -1135,6 +1171,18 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     options = kw.pop("options", None)  # {name: value} for cmf_set_option on the rule (include/cmf_hip.h lists them)
     rule_type = _resolve_alg(alg)
     data = farr(data)
+    mask = kw.get("mask", None)
+    if mask is not None:
+        if rule_type is PGDUpdate:
+            raise ValueError("alg=:pgd takes its mask through the loss: loss_func=MaskedLoss(SquareLoss(), mask) (pgd.jl:58-70)")
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("mask= is implemented for alg=:mult (and, as loss_func=MaskedLoss(...), for :pgd); the HALS, ADMM, "
+                                      "ANLS and separable fits have no masked form")
+        if devices is not None:
+            raise NotImplementedError("mask= is not available with devices=[...]: the masked MU rule runs on one GPU")
+        mask = kw["mask"] = farr(mask, data.shape)  # (one object from here on: the rule methods compare by identity)
+        if not np.isin(mask, (0.0, 1.0)).all():
+            raise ValueError("mask must hold 0 and 1 only (1 = observed)")
     if rule_type is Separable:
         # The separable fit has no iteration and HEAD has no mapping for it (model.jl:3-8 is commented out): the result holds
         # the loss of the fit and the wall time it took; max_itr, max_time, W_init and H_init do not apply.
@@ -1148,7 +1196,8 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
 
     seed = kw.get("seed", None)  # :64-67
     # Initialize (:70) -- always runs, like the reference (it consumes the RNG even when inits are given)
-    W_init, H_init = init_rand(data, L, K, seed=seed, device=device)
+    # (under a mask from Xm = select(mask, data, 0): the held-out entries may hold anything)
+    W_init, H_init = init_rand(data if mask is None else np.where(mask != 0, data, 0.0), L, K, seed=seed, device=device)
     W_init = kw.get("W_init", W_init)  # :72-73
     H_init = kw.get("H_init", H_init)
 
@@ -1166,6 +1215,8 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     try:
         for name, value in (options or {}).items():
             rule.set_option(name, value)
+        if mask is not None:
+            rule.set_mask(mask)  # (before the loop: loss_hist[0] is the masked loss too)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
         loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init")}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
@@ -1208,6 +1259,103 @@ def evaluate_test(r, test, num_iter=30, device=None):
         return rule.compute_loss()
     finally:
         rule.close()
+
+
+def holdout_mask(N, T, frac=0.1, block=1, seed=None):
+    """An N x T mask of 0 and 1 (1 = observed) that holds out about ``frac`` of the entries in runs of exactly ``block``
+    consecutive samples of one unit (a run that reaches T is cut there).  A convolutive model interpolates an isolated entry
+    from its neighbours in time, so ``block=L`` is the useful setting for choosing K and L.  Along every unit, runs alternate
+    with observed stretches of at least one sample whose lengths are geometric with mean block (1 - frac) / frac, which makes
+    the expected held-out share ``frac``.  ``block=1`` is plain speckle: every entry is held out independently with probability
+    ``frac`` (single entries may touch).  Deterministic in ``seed`` (numpy's default_rng), pure numpy."""
+    N, T, block = int(N), int(T), int(block)
+    if not (0.0 <= frac < 1.0):
+        raise ValueError("frac must be in [0, 1)")
+    if block < 1:
+        raise ValueError("block must be >= 1")
+    rng = np.random.default_rng(seed)
+    if frac == 0.0:
+        return np.ones((N, T), order="F")
+    if block == 1:
+        return np.asfortranarray(np.where(rng.random((N, T)) < frac, 0.0, 1.0))
+    p = frac / (block * (1.0 - frac))  # 1 / mean observed stretch
+    if p > 1.0:
+        raise ValueError(f"frac={frac} cannot be reached with separated runs of block={block}: at most block / (block + 1)")
+    ncyc = T // (block + 1) + 2  # a cycle (stretch + run) is at least block + 1 long
+    gaps = rng.geometric(p, size=(N, ncyc)).astype(np.int64)
+    gaps[:, 0] -= 1  # (a run may start at the first sample)
+    starts = np.cumsum(gaps + block, axis=1) - block
+    diff = np.zeros((N, T + 1), dtype=np.int32)
+    rows = np.broadcast_to(np.arange(N)[:, None], starts.shape)
+    live = starts < T
+    np.add.at(diff, (rows[live], starts[live]), 1)
+    np.add.at(diff, (rows[live], np.minimum(starts[live] + block, T)), -1)
+    held = np.cumsum(diff[:, :T], axis=1) > 0
+    return np.asfortranarray(np.where(held, 0.0, 1.0))
+
+
+def evaluate_heldout(r, mask, device=None):
+    """(train, test) = sqrt(sum of (est - data)^2 / sum of data^2) over the entries with ``mask == 1`` and over those with
+    ``mask == 0``, for the fitted model ``r`` (cmf_masked_loss: one loss-only conv each, sums by select)."""
+    mask = farr(mask, np.shape(r.data))
+    rule = MultUpdate(r.data, r.W, r.H, device=device)
+    try:
+        rule.set_mask(mask)
+        out = []
+        for comp in (False, True):
+            resid, dat = rule.masked_loss(complement=comp)
+            out.append(math.sqrt(resid / dat) if dat > 0 else math.nan)
+        return out[0], out[1]
+    finally:
+        rule.close()
+
+
+def _process_group(group):
+    """(dist module or None, rank, world) of an initialised torch.distributed process group (parameter_sweep's rule: torch is
+    never imported from here)."""
+    import sys
+
+    dist = None
+    if "torch" in sys.modules:
+        import torch.distributed as _dist
+
+        if _dist.is_available() and _dist.is_initialized():
+            dist = _dist
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if dist else (0, 1)
+    return dist, rank, world
+
+
+def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=None, group=None, **fit_kw):
+    """Held-out scores for choosing L and K: for every (L, K) and every repeat, draw ``holdout_mask(N, T, frac, block, seed')``,
+    fit ``fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=seed', **fit_kw)`` and score it with ``evaluate_heldout``.
+    Returns ``{(L, K): {"train": array(repeats), "test": array(repeats)}}``.  ``block`` defaults to the combination's L.
+    seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
+    by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
+    combinations and the scores gathered on all ranks."""
+    data = farr(data)
+    N, T = data.shape
+    if "mask" in fit_kw or "alg" in fit_kw:
+        raise TypeError("cross_validate draws its own masks and fits with alg=':mult'")
+    combos = [(L, K) for L in L_vals for K in K_vals]
+    jobs = [(c, rep) for c in combos for rep in range(int(repeats))]
+    dist, rank, world = _process_group(group)
+    device = fit_kw.get("device", None)
+    mine = {}
+    for idx, ((L, K), rep) in enumerate(jobs):
+        if idx % world != rank:
+            continue
+        s = None if seed is None else int(seed) + idx
+        mask = holdout_mask(N, T, frac=frac, block=L if block is None else block, seed=s)
+        r = fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=s, **fit_kw)
+        mine[idx] = evaluate_heldout(r, mask, device=device)
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine, group=group)
+        mine = {k: v for part in parts for k, v in part.items()}
+    out = {c: {"train": np.zeros(int(repeats)), "test": np.zeros(int(repeats))} for c in combos}
+    for idx, (c, rep) in enumerate(jobs):
+        out[c]["train"][rep], out[c]["test"][rep] = mine[idx]
+    return out
 
 
 def evaluate_convergence(r, thresh=0.01):

@@ -69,6 +69,7 @@ mutable struct HIPMultUpdate <: AbstractCFUpdate
     seen_H::UInt64           # deep-copies the initial factors, alternating.jl:33-34 -- equal arrays elsewhere are the same factors)
     w_pending::Bool          # update_motifs! has run and W has not been written back yet
     reuploads::Int
+    mask_id::UInt            # objectid of the mask installed with cmf_mu_set_mask (0 = the unmasked rule)
 end
 
 function fingerprint(rule::HIPMultUpdate, a::Array{Float64})
@@ -100,7 +101,7 @@ function HIPMultUpdate(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Floa
     check(ccall((:cmf_set_factors, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h[], W, H))
     ss = Ref{Float64}(0.0)
     check(ccall((:cmf_get_data_sumsq, LIBCMF), Cint, (Ptr{Cvoid}, Ref{Float64}), h[], ss))
-    rule = HIPMultUpdate(h[], sqrt(ss[]), sync_every_call, verify_args, strict_inplace, UInt64(0), UInt64(0), false, 0)
+    rule = HIPMultUpdate(h[], sqrt(ss[]), sync_every_call, verify_args, strict_inplace, UInt64(0), UInt64(0), false, 0, UInt(0))
     rule.seen_W = fingerprint(rule, W)   # what cmf_set_factors has just read
     rule.seen_H = fingerprint(rule, H)
     finalizer(r -> (r.handle != C_NULL && ccall((:cmf_destroy, LIBCMF), Cint, (Ptr{Cvoid},), r.handle); r.handle = C_NULL), rule)
@@ -163,8 +164,24 @@ function upload!(rule::HIPMultUpdate, W::Array{Float64}, H::Array{Float64})
     rule.w_pending = false
 end
 
-# update_motifs!(rule, data, W, H; l1W=0, l2W=0)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
-function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, kwargs...)
+# The rule under a mask (cmf_mu_set_mask): mask is N x T of 0 and 1, 1 = observed; the update is mult.jl:23-58 with
+# data -> select(mask, data, 0) and est -> mask .* est (MaskedLoss, pgd.jl:58-70, for this rule).  Installed when the object
+# changes (compared by objectid, like select_loss! of the PGD rule); `nothing` restores the unmasked rule.
+function select_mask!(rule::HIPMultUpdate, mask)
+    id = mask === nothing ? UInt(0) : objectid(mask)
+    id == rule.mask_id && return
+    if mask === nothing
+        check(ccall((:cmf_mu_set_mask, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), rule.handle, C_NULL))
+    else
+        m = Matrix{Float64}(mask)
+        check(ccall((:cmf_mu_set_mask, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}), rule.handle, m))
+    end
+    rule.mask_id = id
+end
+
+# update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
+function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)
+    select_mask!(rule, mask)
     GC.@preserve W H begin
         sync_args!(rule, W, H)
         check(ccall((:cmf_update_motifs, LIBCMF), Cint, (Ptr{Cvoid}, Float64, Float64), rule.handle,
@@ -174,8 +191,9 @@ function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, kwargs...
     return W
 end
 
-# update_feature_maps!(rule, data, W, H; l1H=0, l2H=0) -> loss  -- src/algs/mult.jl:42-58, alternating.jl:54
-function update_feature_maps!(rule::HIPMultUpdate, data, W, H; l1H=0, l2H=0, kwargs...)
+# update_feature_maps!(rule, data, W, H; l1H=0, l2H=0, mask=nothing) -> loss  -- src/algs/mult.jl:42-58, alternating.jl:54
+function update_feature_maps!(rule::HIPMultUpdate, data, W, H; l1H=0, l2H=0, mask=nothing, kwargs...)
+    select_mask!(rule, mask)
     loss = Ref{Float64}(0.0)
     GC.@preserve W H begin
         sync_args!(rule, W, H)
@@ -418,6 +436,22 @@ function update_feature_maps!(rule::HIPANLSUpdate, data, W, H; variant=:basic, k
                 rule.handle, Wc, Hc, variant == :block ? 1 : 0, loss))
     Hc === H || (H .= Hc)
     return loss[]
+end
+
+# evaluate_heldout(data, W, H, mask; device=0) -> (train, test): sqrt(sum of (est - data)^2 / sum of data^2) over the entries with
+# mask == 1 and over those with mask == 0, for a fitted model (cmf_masked_loss: one loss-only conv each, sums by select, so NaNs among
+# the held-out data stay out of the train score).
+function evaluate_heldout(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Float64}, mask; device::Integer=0)
+    rule = HIPMultUpdate(data, W, H; device=device, sync_every_call=false)
+    select_mask!(rule, mask)
+    scores = Float64[]
+    for complement in (0, 1)
+        r, d = Ref{Float64}(0.0), Ref{Float64}(0.0)
+        check(ccall((:cmf_masked_loss, LIBCMF), Cint, (Ptr{Cvoid}, Cint, Ref{Float64}, Ref{Float64}), rule.handle, complement, r, d))
+        push!(scores, sqrt(r[] / d[]))
+    end
+    finalize(rule)
+    return scores[1], scores[2]
 end
 
 """

@@ -394,10 +394,32 @@ int cmf_hals_update_feature_maps(cmf_handle h, double l1H, double l2H, double *l
 int cmf_pgd_reset(cmf_handle h);
 /* MaskedLoss(SquareLoss(), mask)  src/algs/pgd.jl:58-70 (the loss_func of the reference's own test/test.jl:45):
  * gradient 2*(est - data) .* mask, loss norm(mask.*data - mask.*est)^2.  `mask` is N x T column-major like data
- * (borrowed for the call); NULL restores the plain SquareLoss.  Only the PGD entries read the mask.  On a group handle the
+ * (borrowed for the call); NULL restores the plain SquareLoss.  The PGD entries read the mask as weights; the MU entries read it
+ * only when it was installed with cmf_mu_set_mask (below), and run unmasked again after this call.  On a group handle the
  * mask is cut along T like data: cmf_create_multi groups take the whole N x T mask, a cmf_create_shard handle its own
  * columns followed by the right lag halo (the layout of data_local). */
 int cmf_set_mask(cmf_handle h, const double *mask);
+/* The MU rule under a mask: the multiplicative update (src/algs/mult.jl:23-58) of the weighted objective
+ * norm(mask .* (data - tensor_conv(W, H)))^2 -- MaskedLoss (src/algs/pgd.jl:58-70) for the headline rule, so that entries of data
+ * can be held out of a fit and scored afterwards (cmf_masked_loss).  `mask` is N x T column-major like data (borrowed for the
+ * call), 0 and 1 only, 1 = observed; it goes into the handle's one mask (the storage of cmf_set_mask).  From then on
+ * cmf_update_motifs, cmf_update_feature_maps, cmf_iterate, cmf_fit and cmf_compute_loss run mult.jl with
+ * data -> Xm = select(mask, data, 0) and est -> mask .* est wherever the rule reads them.  A select, not a product: what data
+ * holds under mask == 0 (NaN and Inf included: missing samples) never enters.
+ * LOSS: norm(mask .* (est - data)) / norm(Xm) -- the share of the FITTED entries left unexplained.  pgd.jl:201 divides by
+ * norm(data) for MaskedLoss; with missing samples that norm may be NaN, and the two agree for an all-ones mask.
+ * A row or column without an observed entry is legal (its factor entries fall to eps, as the formulas say).
+ * NULL restores the unmasked rule and frees the mask and the masked copies.  Every option is honoured under a mask except
+ * "gram".  Errors: CMF_ERR_ARG for a mask that is not 0/1 or observes nothing; CMF_ERR_UNSUPPORTED with the Gram forms (option
+ * "gram": the Gram rewriting of the denominators has no masked form) and on group handles (cmf_create_multi, cmf_create_shard);
+ * the HALS entries answer CMF_ERR_STATE while this mask is installed. */
+int cmf_mu_set_mask(cmf_handle h, const double *mask);
+/* Sums over the entries with mask != 0 (complement != 0: over the entries with mask == 0) of (tensor_conv(W, H) - data)^2 and of
+ * data^2, for the resident factors: sqrt(resid_sumsq / data_sumsq) is the masked loss (pgd.jl:58-70) on the observed entries,
+ * or the held-out score on the others.  Both sums are by select, so a NaN among the held-out data never enters the observed sums.
+ * One loss-only conv and one pass over data; est, the factors and the rule's state are left as they were.  Works with the mask of
+ * cmf_mu_set_mask or of cmf_set_mask; CMF_ERR_STATE without one, CMF_ERR_UNSUPPORTED on group handles. */
+int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *data_sumsq);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
