@@ -219,6 +219,8 @@ static void destroy_impl(cmf_handle_s *h)
                       h->gram_numden_h, h->pgd_gradH, h->M, h->MT, h->Xm, h->XmT, h->hals_snap, h->hals_HX, h->hals_cslabs, h->hals_C, h->hals_HH, h->hals_PT, h->hals_D, h->hals_PW, h->hals_GW, h->hals_GE, h->hals_GWt};
     for (float *p : fbufs)
         if (mine(p)) (void)hipFree(p);
+    if (h->kl_denH) (void)hipFree(h->kl_denH);
+    if (h->kl_sums) (void)hipFree(h->kl_sums);
     for (int v = 0; v < 3; ++v)
         if (h->tc_tab[v]) (void)hipFree(h->tc_tab[v]);
     if (mine(h->partial)) (void)hipFree(h->partial);
@@ -589,11 +591,50 @@ int w_apply_impl(cmf_handle_s *h, double l1W, double l2W, const float *tail_src,
     return w_apply_impl_(h, l1W, l2W, tail_src, tail_dst, tail_n, den);
 }
 
+// update_motifs! of the KL form (cmf_mu_set_divergence): R = data ./ (est + eps) where the squared-error rule forms est (kept from the
+// loss conv when est is reused), numW = the C2 contraction of R alone (mult.jl:32 with data -> R), denomW from the row sums of H, and
+// the element-wise update as it is (mult.jl:37-38).  One path for every K: the few-component fusions (the slab sum inside
+// w_update_small_kernel, the speculated contraction) are not taken.
+static int kl_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
+{
+    const CmfDims &d = h->d;
+    if (!(h->reuse_est && h->est_kind == 7)) CMFTRY(launch_conv<12>(h, h->est, d.Tl, h->conv_gy));
+    set_est(h, 7);
+    CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden, true)); // (+ a loss reduction deferred by cmf_iterate)
+    float *den = h->numden + (size_t)d.L * d.K32 * d.Np;
+    hipLaunchKernelGGL(kl_hsum_kernel, dim3(d.K, KL_HCHUNKS), dim3(256), 0, h->stream, h->Ht, d.TP, d.PADL, d.Tl, h->kl_sums);
+    KCHK("kl_hsum_kernel");
+    hipLaunchKernelGGL(kl_den_w_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Ht, h->kl_sums, den, d.TP, d.PADL, d.Tl, d.K32, d.Np);
+    KCHK("kl_den_w_kernel");
+    return w_apply_impl(h, l1W, l2W, nullptr, nullptr, 0, den);
+}
+
+// update_feature_maps! of the KL form up to the loss: R' with the new W, numH = tensor_transconv(W, R) (one source), denomH from the
+// sums of W over n, and the element-wise update as it is (mult.jl:51-52).  The few-component fusion of the update into the C3 launch
+// (sk_can_fuse_h) is not taken.
+static int kl_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
+{
+    const CmfDims &d = h->d;
+    CMFTRY(launch_conv<13>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext));
+    CMFTRY(launch_transconv(h, 1, h->estT));
+    hipLaunchKernelGGL(kl_wsum_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Wt, d.K32, d.Np, h->kl_sums);
+    KCHK("kl_wsum_kernel");
+    const size_t TK = (size_t)d.Tl * d.K32;
+    hipLaunchKernelGGL(kl_den_h_kernel, dim3((unsigned)((TK + 255) / 256)), dim3(256), 0, h->stream, h->kl_sums, h->kl_denH, d.Tl, d.K, d.K32, d.L);
+    KCHK("kl_den_h_kernel");
+    hipLaunchKernelGGL(h_update_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs, TK, h->tc_S1,
+                       h->kl_denH, (size_t)0, 1, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52
+    KCHK("h_update_kernel");
+    set_est(h, 0);
+    return wb_after_H(h);
+}
+
 // update_motifs! of the MU rule on a single handle (mult.jl:23-39).  Few components: conv (unless est is current), the C2
 // kernel, and ONE launch that sums its slabs, updates W and packs the C3 operand (w_update_small_kernel).
 static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 {
     const CmfDims &d = h->d;
+    if (h->mu_div) return kl_w_phase_impl(h, l1W, l2W);
     if (!h->small_k) {
         CMFTRY(w_partial_impl(h));
         return w_apply_impl(h, l1W, l2W);
@@ -652,6 +693,7 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         set_est(h, 0);
         return wb_after_H(h);
     }
+    if (h->mu_div) return kl_h_update_impl(h, l1H, l2H);
     if (h->mu_mask) CMFTRY(launch_conv<9>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // (mask .* est)' under the MU rule's mask
     else CMFTRY(launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
     if (sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
@@ -674,6 +716,12 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
 int launch_loss_conv(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
+    if (h->mu_div) { // the sum of the divergence terms; R = data ./ (est + eps) kept for the next update_motifs! when est is reused
+        if (!h->reuse_est) return launch_conv<14>(h, nullptr, d.Tl, h->conv_gy);
+        CMFTRY(launch_conv<15>(h, h->est, d.Tl, h->conv_gy));
+        set_est(h, 7);
+        return CMF_OK;
+    }
     if (h->mu_mask) { // the sum of (mask .* (est - data))^2; mask .* est kept when est is reused
         if (!h->reuse_est) return launch_conv<10>(h, nullptr, d.Tl, h->conv_gy);
         CMFTRY(launch_conv<11>(h, h->est, d.Tl, h->conv_gy));
@@ -695,7 +743,7 @@ int launch_loss_conv(cmf_handle_s *h)
 // (the call before this one was update_motifs!); a caller that stops pays one contraction nobody reads.
 static int w_speculate(cmf_handle_s *h)
 {
-    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)) || h->gram || h->group || h->carry.partial) return CMF_OK;
+    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)) || h->gram || h->group || h->carry.partial || h->mu_div) return CMF_OK;
     if (h->small_k) CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, nullptr, false, true));
     else CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, h->numden, true));
     h->spec_gen = h->est_gen;
@@ -1347,6 +1395,8 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
     if (std::strcmp(name, "gram") == 0) {
         if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "gram must be 0, 1 or 2");
         if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
+        if (value && h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no KL form: "
+                                                                 "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
                                                                   "which is not a product of Gram matrices): clear the mask of cmf_mu_set_mask first");
         h->gram = value;
@@ -1501,7 +1551,7 @@ static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double
     CMFTRY(h_update_impl(h, l1H, l2H));
     double ss = 0.0;
     CMFTRY(loss_partial_impl(h, &ss, true, nullptr, speculate));
-    *loss = std::sqrt(ss) / mu_norm(h);
+    *loss = mu_loss(h, ss);
     return CMF_OK;
 }
 
@@ -1588,7 +1638,7 @@ int cmf_compute_loss(cmf_handle h, double *loss)
     CMFTRY(check_ready(h, true));
     double ss = 0.0;
     CMFTRY(loss_partial_impl(h, &ss));
-    *loss = std::sqrt(ss) / mu_norm(h);
+    *loss = mu_loss(h, ss);
     return CMF_OK;
 }
 
@@ -1597,6 +1647,7 @@ int cmf_hals_update_motifs(cmf_handle h, double l1W, double l2W)
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
+    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     h->last_rule_call = 1;
     return hals_w_impl(h, l1W, l2W);
 }
@@ -1607,6 +1658,7 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     if (!loss) return fail(CMF_ERR_ARG, "loss is NULL");
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
+    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates (alternating.jl:51-54): update_motifs! comes next
     h->last_rule_call = 2;
     CMFTRY(hals_h_impl(h, l1H, l2H));
@@ -1686,6 +1738,7 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
         h->M = h->MT = nullptr;
         return CMF_OK;
     }
+    if (h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
                                                   "which is not a product of Gram matrices; set gram = 0 first");
     const CmfDims &d = h->d;
@@ -1708,6 +1761,54 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
     h->xm_norm = std::sqrt(h->xm_sumsq);
     h->mu_mask = true;
     set_est(h, 0);
+    return CMF_OK;
+}
+
+int cmf_mu_set_divergence(cmf_handle h, int kind)
+{
+    if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
+    if (kind != CMF_DIV_SQUARE && kind != CMF_DIV_KL) return fail(CMF_ERR_ARG, "kind must be CMF_DIV_SQUARE (0) or CMF_DIV_KL (1)");
+    if (h->group || h->root_only || h->sharded)
+        return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
+    HIPCHK(hipSetDevice(h->device));
+    if (kind == h->mu_div) return CMF_OK;
+    if (h->wb && h->wb->armed) wb_disarm(h);
+    drop_carry(h);
+    h->spec_gen = -1;
+    set_est(h, 0);
+    if (kind == CMF_DIV_SQUARE) { // today's rule again, launch for launch
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->kl_denH) (void)hipFree(h->kl_denH);
+        if (h->kl_sums) (void)hipFree(h->kl_sums);
+        h->kl_denH = nullptr;
+        h->kl_sums = nullptr;
+        h->mu_div = CMF_DIV_SQUARE;
+        return CMF_OK;
+    }
+    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
+    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no KL form; set gram = 0 first");
+    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: clear the mask of cmf_mu_set_mask first");
+    // data must be finite and non-negative with a positive sum: one pass (the padding of X is zero)
+    const CmfDims &d = h->d;
+    const size_t n4 = (size_t)d.TP * d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h) / 2, std::min<size_t>(1024, (n4 + 255) / 256));
+    if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
+    hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, h->partial);
+    KCHK("kl_data_check_kernel");
+    std::vector<double> part((size_t)2 * nb);
+    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double sum = 0.0, bad = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        sum += part[(size_t)b];
+        bad += part[(size_t)nb + b];
+    }
+    if (bad > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", bad);
+    if (!(sum > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
+    if (!h->kl_denH) CMFTRY(dalloc_zero(&h->kl_denH, (size_t)d.Tl * d.K32));
+    if (!h->kl_sums) CMFTRY(dalloc_zero(&h->kl_sums, (size_t)d.K32 * std::max(d.L, KL_HCHUNKS)));
+    h->data_sum = sum;
+    h->mu_div = CMF_DIV_KL;
     return CMF_OK;
 }
 
@@ -1782,6 +1883,7 @@ int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int nonne
         return group_pgd_w(h, h->group, pen_sq, pen_abs, nonneg);
     }
     CMFTRY(check_ready(h, true));
+    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_w_impl(h, pen_sq, pen_abs, nonneg);
 }
 
@@ -1794,6 +1896,7 @@ static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_
         return group_pgd_h(h, h->group, pen_sq, pen_abs, nonneg, loss);
     }
     CMFTRY(check_ready(h, true));
+    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_h_impl(h, pen_sq, pen_abs, nonneg, loss);
 }
 
@@ -1848,7 +1951,7 @@ static int iterate_single(cmf_handle_s *h, int64_t n, int eval_mode, double l1W,
         const unsigned long long bits = ring[slot];
         double ss;
         std::memcpy(&ss, &bits, 8);
-        losses[it] = std::sqrt(ss) / mu_norm(h);
+        losses[it] = mu_loss(h, ss);
         if (stamps) stamps[it] = now();
         return CMF_OK;
     };

@@ -270,6 +270,12 @@ struct cmf_handle_s {
     bool mu_mask = false;
     float *Xm = nullptr, *XmT = nullptr;
     double xm_sumsq = 0.0, xm_norm = 0.0; // sum of Xm^2 and its root: what the masked MU loss is divided by
+    // the KL form of the MU rule (cmf_mu_set_divergence): est / estT hold R = data ./ (est + eps) (est_kind 7) where the squared-error
+    // rule keeps est, the contractions run on that one source, and the denominators come from two small tables (kl_den_w / kl_den_h)
+    int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL
+    double data_sum = 0.0;       // sum(data): what the divergence is divided by
+    float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
+    double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
 
     double data_sumsq = 0.0, data_norm = 0.0;
     bool factors_set = false;
@@ -288,7 +294,7 @@ struct cmf_handle_s {
     std::vector<hipEvent_t> prof_pool;
     int est_kind = 0;       // what est[t][n] holds for the resident W, H: 0 nothing, 1 tensor_conv(W,H), 2 tensor_conv(W,H) - data, 3 mask .* (tensor_conv(W,H) - data),
                             // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient), 6 mask .* tensor_conv(W,H) (the MU rule
-                            // under a mask: mu_est_kind)
+                            // under a mask: mu_est_kind), 7 data ./ (tensor_conv(W,H) + eps) (the KL form of the MU rule)
     void *arena = nullptr;  // the small buffers of the handle as ONE device allocation (cmf_create): 21 hipFree calls cost 1.3 ms, one 0.16
     size_t arena_bytes = 0;
     bool streams_may_hang = false;  // set on the shards of a FAILED group: their streams are not waited for when they are given back
@@ -488,8 +494,10 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
 // cmf_mu_set_mask is installed.  reuse_est, the speculated C2 contraction and the deferred loss carry all compare against mu_est_kind.
 static inline const float *mu_X(const cmf_handle_s *h) { return h->mu_mask ? h->Xm : h->X; }
 static inline const float *mu_XT(const cmf_handle_s *h) { return h->mu_mask ? h->XmT : h->XT; }
-static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? 6 : 1; }
+static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? 6 : h->mu_div ? 7 : 1; }
 static inline double mu_norm(const cmf_handle_s *h) { return h->mu_mask ? h->xm_norm : h->data_norm; }
+// the loss of the MU entries from the sum its loss conv leaves: norm(est - data) / norm(data), or D(data, est) / sum(data) under KL
+static inline double mu_loss(const cmf_handle_s *h, double ss) { return h->mu_div ? ss / h->data_sum : std::sqrt(ss) / mu_norm(h); }
 int wb_after_H(cmf_handle_s *h); // hook: the kernels that make H final have been enqueued (cmf_writeback.h)
 int gram_ensure(cmf_handle_s *h);
 int hals_w_impl(cmf_handle_s *h, double l1W, double l2W);
@@ -625,12 +633,13 @@ struct ProfScope {
 template <int MODE>
 static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
 {
-    constexpr int BASE = MODE >= 8 ? MODE - 8 : MODE; // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask (cmf_kernels.h)
+    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms (cmf_kernels.h)
+    constexpr int BASE = MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
     ProfScope prof_(h, BASE == 0 ? PROF_CONV : BASE == 1 ? PROF_CONV_T : BASE == 2 ? PROF_CONV_LOSS : BASE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
-    if (MODE >= 8 && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
+    if (MODE >= 8 && MODE <= 11 && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
-    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : h->X; p.partial = h->partial;
+    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (MODE == 13 ? h->XT : h->X); p.partial = h->partial;
     p.mask = (MODE == 7 || MODE == 9) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
@@ -684,7 +693,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         }
     }
     const bool split = cut > 0;
-    const int variant = (h->conv_variant && BASE <= 2) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
+    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
     if (d.K % 32 == 0 && variant == 3) {
         const int n_full = tiles3 - cut;
         // quarter tiles reach every SIMD only from one tile per CU on; below that, sixteenth tiles
@@ -697,8 +706,10 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         // the 128 x 128 kernel exists for the epilogues that only store or only sum (est, est', loss): with a data tile
         // read AND a store in the epilogue (mode 3 and the residual modes) it needs more than the 168 registers three
         // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
-        if constexpr (BASE <= 2) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
-        if constexpr (BASE <= 2) h->launches[LA_CONV2] += 1;
+        // (KL: the loss-only mode alone -- modes 12 and 13 read a data tile and store, and run on the one-wave kernel like mode 3)
+        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13;
+        if constexpr (TILES128) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
+        if constexpr (TILES128) h->launches[LA_CONV2] += 1;
     } else {
         hipLaunchKernelGGL((conv_kernel<MODE, 0>), grid, block, 0, h->stream, p);
         h->launches[LA_CONV] += 1;

@@ -71,12 +71,17 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //     what is stored is mask .* est, what is summed is (mask .* (est - data))^2.  The mask acts as a SELECT (an entry with mask == 0
 //     contributes 0 whatever data holds there, NaN included).  MODE 10 with p.loss_abs != 0 sums over the entries with mask == 0
 //     instead (cmf_masked_loss: the held-out score).
+//   MODE 12 .. 15: the KL form of the MU rule (cmf_mu_set_divergence), e = est + eps:
+//     MODE 12: store R[t][n] = data / e                    MODE 13: store R'[n][t] (p.data = dataT [Np][TP])
+//     MODE 14: no store; per-workgroup sum of the divergence terms (data > 0 ? data log(data / e) : 0) - data + est -> partial[]
+//     MODE 15: MODE 12 + MODE 14
+//     Padding (n >= N, where data and est are 0) stores 0 / eps = 0 and adds 0 to the sum.  (16 .. 19 are left for these under a mask.)
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
     const float *Wt;
     float *out;
-    const float *data; // X [TP][Np] (modes 2, 3, 4, 6) or XT [Np][TP] (modes 5, 7)
+    const float *data; // X [TP][Np] (modes 2, 3, 4, 6, 10 - 12, 14, 15) or XT [Np][TP] (modes 5, 7, 13)
     const float *mask; // same layout as data (modes 6, 7)
     double *partial;   // [gridDim.x * gridDim.y]
     int Np, TP, PADL, K, KB, L;
@@ -100,9 +105,11 @@ __device__ __forceinline__ f32x4 cmf_load4_sc1(const float *p)
     return v;
 }
 
-#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9)
-#define CONV_MU_MASKED(MODE) ((MODE) >= 8)                       // the masked forms of modes 0 .. 3
-#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11)
+#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9 || (MODE) == 13)
+#define CONV_MU_MASKED(MODE) ((MODE) >= 8 && (MODE) <= 11)       // the masked forms of modes 0 .. 3
+#define CONV_KL(MODE) ((MODE) >= 12 && (MODE) <= 15)             // the KL forms: R = data / (est + eps) stored, the divergence summed
+#define CONV_KL_STORE(MODE) ((MODE) == 12 || (MODE) == 15)
+#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15)
 #define CONV_PGD(MODE) ((MODE) >= 4 && (MODE) <= 7)              // the residual modes (the only ones p.loss_abs = AbsoluteLoss applies to)
 #define CONV_HS_STRIDE 160
 #define CONV_HS_FLOATS (32 * CONV_HS_STRIDE)
@@ -113,6 +120,12 @@ __device__ __forceinline__ void cmf_bstore(float v, __amdgpu_buffer_rsrc_t r, in
 {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff_bytes, soff_bytes, 0);
 }
+
+// The KL epilogue of one element (modes 12 .. 15): q = data / (est + eps), what modes 12, 13 and 15 store, and the element's
+// divergence term (data > 0 ? data log(data / e) : 0) - data + est.  The logarithm is guarded by a select on q, which is > 0
+// exactly where data is unless the quotient underflows, and there data log(data / e) is 0 to fp32 as well.  Padding: 0 / eps = 0, term 0.
+__device__ __forceinline__ float cmf_kl_ratio(float x, float v) { return x / (v + CMF_EPS_F); }
+__device__ __forceinline__ float cmf_kl_term(float x, float v, float q) { return ((q > 0.f) ? x * logf(q) : 0.f) + (v - x); }
 
 // Every access of the epilogue is a buffer load / store: descriptor on the wave's 64 x 64 sub-tile (a wave-uniform
 // base), one per-lane byte offset, and a scalar offset per element -- no vector address arithmetic (VALU slots are
@@ -129,6 +142,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
@@ -164,7 +178,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int so = (((gt + ti) * 32 + (r & 3) + 8 * (r >> 2)) * Np + (gn + ni) * 32) * 4;
-                                dv[ti][ni][r] = !LOSS ? 0.f : (PRE && !MASKED) ? pre[gt + ti][gn + ni][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
+                                dv[ti][ni][r] = !(LOSS || KL) ? 0.f : (PRE && !MASKED) ? pre[gt + ti][gn + ni][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
                                                                                : cmf_bload(rd, voff, so); // rows past T_store read as 0 (masked below)
                                 mv[ti][ni][r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
                             }
@@ -183,6 +197,11 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                     if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
                                     d = (obs != comp) ? d : 0.f;
                                 }
+                                if (KL) {
+                                    const float q = cmf_kl_ratio(dv[ti][ni][r], v);
+                                    if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
+                                    if (LOSS) d = cmf_kl_term(dv[ti][ni][r], v, q);
+                                }
                                 if (RESID) {
                                     if (ABS) {
                                         const float sg = (v > dv[ti][ni][r]) ? 1.f : ((v < dv[ti][ni][r]) ? -1.f : 0.f);
@@ -193,7 +212,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                 }
                                 if (LOSS) {
                                     if (PARTIAL) d = ((gt + ti) * 32 + cmf_crow(r, h) < rows) ? d : 0.f;
-                                    lsum = ABS ? lsum + fabsf(d) : fmaf(d, d, lsum);
+                                    lsum = ABS ? lsum + fabsf(d) : KL ? lsum + d : fmaf(d, d, lsum);
                                 }
                             }
                 }
@@ -244,7 +263,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                        dv[r] = CONV_PGD(MODE) ? cmf_bload(rd, voff, so) : 0.f;
+                        dv[r] = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
                         mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
                     }
                     if (CONV_PGD(MODE) && abs_t) { // AbsoluteLoss: the stored quantity is the gradient sign(est - data)
@@ -260,6 +279,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                         for (int r = 0; r < 16; ++r) {
                             const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
                             if (MUM) cmf_bstore(mv[r] != 0.f ? acc[ni][ti][r] : 0.f, ro, voff, so);
+                            else if (KL) cmf_bstore(cmf_kl_ratio(dv[r], acc[ni][ti][r]), ro, voff, so);
                             else cmf_bstore(MASKED ? (acc[ni][ti][r] - dv[r]) * mv[r] : acc[ni][ti][r] - dv[r], ro, voff, so);
                         }
                     }
@@ -576,7 +596,7 @@ __device__ __forceinline__ void conv3_tile(const ConvParams &p, float *Hs, int t
     // HBM round trip per tile; here it is requested before the loop (64 registers that the few k pairs leave free) with the epilogue's
     // descriptor and offsets, and the epilogue finds it there (protocol shape: 37.8 -> 35.8 us).  On a launch of many rounds (N = 2000:
     // eight tiles per SIMD slot, bandwidth-bound) the W rows of the first lags queue behind these 64 loads and it costs 7 %: not used there.
-    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11) && NKP <= 4 && NBL == 2);
+    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15) && NKP <= 4 && NBL == 2);
     float dpre[2][2][16];
     if (PRE) {
         int rows = p.T_store - t0;
@@ -637,6 +657,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
     const bool comp = (MODE == 10) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) {
@@ -652,7 +673,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
-            dv[r] = LOSS ? cmf_bload(rd, voff, so) : 0.f; // rows past T_store read as 0 (masked below)
+            dv[r] = (LOSS || KL) ? cmf_bload(rd, voff, so) : 0.f; // rows past T_store read as 0 (masked below)
             mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
         }
         float lsum = 0.f;
@@ -667,13 +688,18 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
                 if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
                 d = (obs != comp) ? d : 0.f;
             }
+            if (KL) {
+                const float q = cmf_kl_ratio(dv[r], v);
+                if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
+                if (LOSS) d = cmf_kl_term(dv[r], v, q);
+            }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
                 cmf_bstore(abs_loss ? (MASKED ? sg * mv[r] : sg) : d, ro, voff, so);
             }
             if (LOSS) {
                 d = (cmf_crow(r, h) < rows) ? d : 0.f;
-                lsum = abs_loss ? lsum + fabsf(d) : fmaf(d, d, lsum);
+                lsum = abs_loss ? lsum + fabsf(d) : KL ? lsum + d : fmaf(d, d, lsum);
             }
         }
         if (LOSS) {
@@ -698,7 +724,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
-                dv[r] = CONV_PGD(MODE) ? cmf_bload(rd, voff, so) : 0.f;
+                dv[r] = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
                 mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
             }
 #pragma unroll
@@ -707,6 +733,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
                 float d = acc[r] - dv[r];
                 if (abs_loss) d = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
                 if (MUM) d = mv[r] != 0.f ? d : 0.f;
+                if (KL) d = cmf_kl_ratio(dv[r], acc[r]);
                 cmf_bstore(MASKED ? d * mv[r] : d, ro, voff, so);
             }
         }
@@ -823,6 +850,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
     constexpr bool RESID = (MODE == 4 || MODE == 6);
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs;
     const bool comp = (MODE == 10) && p.loss_abs; // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
@@ -837,7 +865,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
         float dv[4], mv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            dv[r] = LOSS ? cmf_bload(rd, voff, r * Np * 4) : 0.f;
+            dv[r] = (LOSS || KL) ? cmf_bload(rd, voff, r * Np * 4) : 0.f;
             mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, r * Np * 4) : 1.f;
         }
         float lsum = 0.f;
@@ -851,13 +879,18 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
                 if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, r * Np * 4);
                 d = (obs != comp) ? d : 0.f;
             }
+            if (KL) {
+                const float q = cmf_kl_ratio(dv[r], v);
+                if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, r * Np * 4);
+                if (LOSS) d = cmf_kl_term(dv[r], v, q);
+            }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
                 cmf_bstore(abs_loss ? (MASKED ? sg * mv[r] : sg) : d, ro, voff, r * Np * 4);
             }
             if (LOSS) {
                 d = (4 * kq + r < rows) ? d : 0.f;
-                lsum = abs_loss ? lsum + fabsf(d) : fmaf(d, d, lsum);
+                lsum = abs_loss ? lsum + fabsf(d) : KL ? lsum + d : fmaf(d, d, lsum);
             }
         }
         if (LOSS) {
@@ -880,11 +913,12 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
         if (tb + j < p.T_store) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float dvr = CONV_PGD(MODE) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
+                const float dvr = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
                 const float mvr = (MASKED || MUM) ? cmf_bload(rm, voff, r * TP * 4) : 1.f;
                 float d = acc[r] - dvr;
                 if (abs_loss) d = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
                 if (MUM) d = mvr != 0.f ? d : 0.f;
+                if (KL) d = cmf_kl_ratio(dvr, acc[r]);
                 cmf_bstore(MASKED ? d * mvr : d, ro, voff, r * TP * 4);
             }
         }
@@ -3559,6 +3593,106 @@ static __global__ __launch_bounds__(256) void mask_select_kernel(const float *X,
         __syncthreads();
     }
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// ---------------------------------------------------------------------------------------------
+// The KL form of the MU rule (cmf_mu_set_divergence): the check of data and the two denominators.  With R = data ./ (est + eps) the
+// numerators are the contractions of the squared-error rule on R; the denominators are what those contractions give on all ones:
+//   denomW[k, n, l] = sum(H[k, 1:T-l])  (the same for every n)      denomH[k, t] = sum over l < min(L, T-t+1), over n, of W[k, n, l+1]
+// Both are summed in fp64 and broadcast into the layouts w_update_kernel and h_update_kernel read ([L][K32][Np] and [Tl][K32]).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double cmf_block_sum_f64(double s, double *red)
+{
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    const double tot = red[0];
+    __syncthreads();
+    return tot;
+}
+
+// One pass over the flat padded data [TP][Np] (padding is zero): partial[b] = the block's sum, partial[gridDim.x + b] = how many of its
+// entries are negative, NaN or infinite.
+static __global__ __launch_bounds__(256) void kl_data_check_kernel(const float *X, size_t n4, double *partial)
+{
+    __shared__ double red[256];
+    double s = 0.0, bad = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * 256) {
+        const float4 x = reinterpret_cast<const float4 *>(X)[idx];
+        const float xv[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool ok = xv[q] >= 0.f && xv[q] <= 3.402823466e+38f; // (false for NaN)
+            s += ok ? (double)xv[q] : 0.0;
+            bad += ok ? 0.0 : 1.0;
+        }
+    }
+    s = cmf_block_sum_f64(s, red);
+    bad = cmf_block_sum_f64(bad, red);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = s;
+        partial[gridDim.x + blockIdx.x] = bad;
+    }
+}
+
+#define KL_HCHUNKS 16
+// grid (K, KL_HCHUNKS): sums[k * KL_HCHUNKS + c] = the sum of H[k, t] over the c-th of KL_HCHUNKS equal pieces of [0, Tl)
+static __global__ __launch_bounds__(256) void kl_hsum_kernel(const float *Ht, int TP, int PADL, int Tl, double *sums)
+{
+    __shared__ double red[256];
+    const int k = blockIdx.x, c = blockIdx.y;
+    const int len = (Tl + KL_HCHUNKS - 1) / KL_HCHUNKS;
+    const int t0 = c * len, t1 = (t0 + len < Tl) ? t0 + len : Tl;
+    const float *row = Ht + (size_t)k * TP + PADL;
+    double s = 0.0;
+    for (int t = t0 + (int)threadIdx.x; t < t1; t += 256) s += (double)row[t];
+    s = cmf_block_sum_f64(s, red);
+    if (threadIdx.x == 0) sums[k * KL_HCHUNKS + c] = s;
+}
+
+// grid (L, K): den[l][k][0 .. Np) = sum(H[k, 0 : Tl - l]) = the row sum minus its last l entries (0 when l >= Tl)
+static __global__ __launch_bounds__(256) void kl_den_w_kernel(const float *Ht, const double *sums, float *den, int TP, int PADL, int Tl,
+                                                              int K32, int Np)
+{
+    __shared__ double red[256];
+    const int l = blockIdx.x, k = blockIdx.y;
+    const float *row = Ht + (size_t)k * TP + PADL;
+    double s = 0.0;
+    if ((int)threadIdx.x < KL_HCHUNKS) s = sums[k * KL_HCHUNKS + threadIdx.x];
+    if (l < Tl)
+        for (int j = threadIdx.x; j < l; j += 256) s -= (double)row[Tl - 1 - j];
+    s = cmf_block_sum_f64(s, red);
+    const float v = (l < Tl) ? (float)s : 0.f;
+    float *out = den + ((size_t)l * K32 + k) * Np;
+    for (int n = threadIdx.x; n < Np; n += 256) out[n] = v;
+}
+
+// grid (L, K): sums[l * K32 + k] = sum over n of W[k, n, l]   (Wt: [L][K32][Np], padding zero)
+static __global__ __launch_bounds__(256) void kl_wsum_kernel(const float *Wt, int K32, int Np, double *sums)
+{
+    __shared__ double red[256];
+    const int l = blockIdx.x, k = blockIdx.y;
+    const float *row = Wt + ((size_t)l * K32 + k) * Np;
+    double s = 0.0;
+    for (int n = threadIdx.x; n < Np; n += 256) s += (double)row[n];
+    s = cmf_block_sum_f64(s, red);
+    if (threadIdx.x == 0) sums[l * K32 + k] = s;
+}
+
+// den[t][k] = sum over l < min(L, Tl - t) of sums[l][k]   ([Tl][K32]; components k >= K: 0)
+static __global__ __launch_bounds__(256) void kl_den_h_kernel(const double *sums, float *den, int Tl, int K, int K32, int L)
+{
+    const size_t e = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (e >= (size_t)Tl * K32) return;
+    const int t = (int)(e / K32), k = (int)(e % K32);
+    const int m = (Tl - t < L) ? Tl - t : L;
+    double s = 0.0;
+    if (k < K)
+        for (int l = 0; l < m; ++l) s += sums[l * K32 + k];
+    den[e] = (float)s;
 }
 
 // =============================================================================================

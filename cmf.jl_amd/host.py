@@ -126,6 +126,16 @@ def rccl_version():
 # --------------------------------------------------------------------------------------
 # update rules (the plugin boundary: abstract type AbstractCFUpdate, alternating.jl:1-8)
 # --------------------------------------------------------------------------------------
+_DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1}  # CMF_DIV_SQUARE, CMF_DIV_KL (include/cmf_hip.h)
+
+
+def _divergence_kind(kind):
+    key = kind if isinstance(kind, str) else (":" + getattr(kind, "name", str(kind)))
+    if key not in _DIVERGENCES:
+        raise ValueError(f"divergence must be ':square' or ':kl', got {kind!r}")
+    return _DIVERGENCES[key]
+
+
 class AbstractCFUpdate:
     """An update rule that updates both W and H (src/algs/alternating.jl:1-8).
 
@@ -302,6 +312,14 @@ class MultUpdate(AbstractCFUpdate):
         r, d = ctypes.c_double(), ctypes.c_double()
         check(self._lib.cmf_masked_loss(self._h, int(bool(complement)), ctypes.byref(r), ctypes.byref(d)))
         return r.value, d.value
+
+    # -- the divergence the rule minimises (cmf_mu_set_divergence) ---------------------------
+    def set_divergence(self, kind):
+        """``":kl"``: the multiplicative update of the generalised Kullback-Leibler divergence (Smaragdis' convolutive NMF), for counts
+        and spectrogram magnitudes: R = data ./ (est + eps) takes the place of data in the numerators, the denominators are sums of H
+        and of W, and the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative with a positive sum.
+        ``":square"`` restores the squared-error rule of mult.jl exactly."""
+        check(self._lib.cmf_mu_set_divergence(self._h, _divergence_kind(kind)))
 
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
@@ -1129,7 +1147,8 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "variant",  # ANLSUpdate (anls.jl:26)
              "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
              "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
-             "mask"}  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
+             "mask",  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
+             "divergence"}  # alg=:mult: ":square" (default) or ":kl" (MultUpdate.set_divergence)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -1183,6 +1202,15 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         mask = kw["mask"] = farr(mask, data.shape)  # (one object from here on: the rule methods compare by identity)
         if not np.isin(mask, (0.0, 1.0)).all():
             raise ValueError("mask must hold 0 and 1 only (1 = observed)")
+    divergence = _divergence_kind(kw.get("divergence", ":square"))
+    if divergence:
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("divergence=':kl' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable fits "
+                                      "minimise the squared error (PGD also the absolute error)")
+        if mask is not None:
+            raise NotImplementedError("divergence=':kl' is not available with mask=: the KL form of the MU rule has no masked form yet")
+        if devices is not None:
+            raise NotImplementedError("divergence=':kl' is not available with devices=[...]: the KL form of the MU rule runs on one GPU")
     if rule_type is Separable:
         # The separable fit has no iteration and HEAD has no mapping for it (model.jl:3-8 is commented out): the result holds
         # the loss of the fit and the wall time it took; max_itr, max_time, W_init and H_init do not apply.
@@ -1217,8 +1245,10 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
             rule.set_option(name, value)
         if mask is not None:
             rule.set_mask(mask)  # (before the loop: loss_hist[0] is the masked loss too)
+        if divergence:
+            rule.set_divergence(":kl")  # (before the loop: loss_hist[0] is the divergence too)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
-        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init")}
+        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence")}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
     finally:
         if hasattr(rule, "close"):
@@ -1244,6 +1274,17 @@ def gen_synthetic(N=100, T=500, K=3, L=20, alpha=0.1, p_h=0.5, sigma=0.2, noise_
 def evaluate_mse(r, device=None):
     """evaluate_mse(r::CNMF_results): src/evaluate.jl:1-5."""
     return compute_loss(r.data, r.W, r.H, device=device)
+
+
+def evaluate_divergence(r, kind=":kl", device=None):
+    """The loss of the fitted model ``r`` under ``kind`` (cmf_compute_loss): for ``":kl"`` D(data, est + eps) / sum(data), what
+    ``fit_cnmf(divergence=":kl")`` records in ``loss_hist``; for ``":square"`` evaluate_mse's value."""
+    rule = MultUpdate(r.data, r.W, r.H, device=device)
+    try:
+        rule.set_divergence(kind)
+        return rule.compute_loss()
+    finally:
+        rule.close()
 
 
 def evaluate_test(r, test, num_iter=30, device=None):

@@ -179,6 +179,15 @@ function select_mask!(rule::HIPMultUpdate, mask)
     rule.mask_id = id
 end
 
+# set_divergence!(rule, :kl): the rule becomes the multiplicative update of the generalised Kullback-Leibler divergence
+# (cmf_mu_set_divergence): R = data ./ (est + eps) takes the place of data in mult.jl:32 and :47, the denominators are sums of H and
+# of W, the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative.  :square restores mult.jl exactly.
+function set_divergence!(rule::HIPMultUpdate, kind::Symbol)
+    kind in (:square, :kl) || throw(ArgumentError("divergence must be :square or :kl"))
+    check(ccall((:cmf_mu_set_divergence, LIBCMF), Cint, (Ptr{Cvoid}, Cint), rule.handle, kind === :kl ? 1 : 0))
+    return rule
+end
+
 # update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
 function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)
     select_mask!(rule, mask)

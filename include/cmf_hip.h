@@ -420,6 +420,28 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask);
  * One loss-only conv and one pass over data; est, the factors and the rule's state are left as they were.  Works with the mask of
  * cmf_mu_set_mask or of cmf_set_mask; CMF_ERR_STATE without one, CMF_ERR_UNSUPPORTED on group handles. */
 int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *data_sumsq);
+/* The divergence the MU rule minimises.  CMF_DIV_SQUARE (default) is src/algs/mult.jl as it stands and restores exactly today's rule,
+ * launch for launch.  CMF_DIV_KL is the multiplicative update of the generalised Kullback-Leibler divergence (Smaragdis' convolutive
+ * NMF; beta_loss="kullback-leibler" elsewhere), for counts and spectrogram magnitudes.  With eps = eps(Float64) (src/CMF.jl:20) and
+ * e = tensor_conv(W, H) + eps, from this call on cmf_update_motifs, cmf_update_feature_maps, cmf_compute_loss, cmf_iterate and
+ * cmf_fit (eval_mode included) run
+ *   update_motifs!:        R = data ./ e;  numW[:, :, l] = shift_cols(H, l) * R[:, 1+l:T]'  (mult.jl:32 with data -> R);
+ *                          denomW[k, n, l] = sum(H[k, 1:T-l])  (the same for every n; 0 when l >= T);
+ *                          W .*= numW ./ (denomW + l1W + 2 l2W W + eps);  W = max(eps, W)  (mult.jl:37-38 unchanged)
+ *   update_feature_maps!:  R = data ./ e (e from the new W);  numH = tensor_transconv(W, R);
+ *                          denomH[k, t] = sum over l < min(L, T-t+1), over n, of W[k, n, l+1];  the same update of H
+ * -- denomW and denomH are what mult.jl:33 and :48 give with est replaced by all ones.
+ * LOSS: D(data, e) / sum(data), D = sum over entries of (data > 0 ? data log(data / e) : 0) - data + e, with e from the new H:
+ * dimensionless, 0 for a perfect fit, no square root, and with l1 = l2 = 0 it does not increase from one iteration to the next.
+ * Data must be finite and non-negative with a positive sum (checked here in one pass over the resident data); zeros are legal, and
+ * so is a unit whose data are all zero (its motif entries fall to eps).  Every option is honoured except "gram"; the few-component
+ * fusions that "small_k_fuse" and "speculate" select are not taken under KL, so results do not depend on them.
+ * Errors: CMF_ERR_ARG for another kind, or for data with a negative, NaN or infinite entry or a sum of 0; CMF_ERR_UNSUPPORTED on
+ * group handles (cmf_create_multi, cmf_create_shard), with the Gram forms (option "gram", in either order) and together with
+ * cmf_mu_set_mask (in either order); the HALS and PGD entries answer CMF_ERR_STATE while CMF_DIV_KL is installed. */
+#define CMF_DIV_SQUARE 0
+#define CMF_DIV_KL 1
+int cmf_mu_set_divergence(cmf_handle h, int kind);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
