@@ -598,6 +598,13 @@ int w_apply_impl(cmf_handle_s *h, double l1W, double l2W, const float *tail_src,
 static int kl_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 {
     const CmfDims &d = h->d;
+    if (h->mu_mask) { // under a mask (option "kl_mask"): R = Xm ./ e, and the denominator is the same contraction on the mask itself
+        // (mode 12 with data = Xm stores 0 / (v + eps) = 0 at the held-out entries: the store-only form needs no masked mode)
+        if (!(h->reuse_est && h->est_kind == 8)) CMFTRY(launch_conv<12>(h, h->est, d.Tl, h->conv_gy, h->Xm));
+        set_est(h, 8);
+        CMFTRY(hxt_contract(h, h->est, h->M, 2, h->numden, true)); // [numW | denomW] (+ a loss reduction deferred by cmf_iterate)
+        return w_apply_impl(h, l1W, l2W, nullptr, nullptr, 0, nullptr);
+    }
     if (!(h->reuse_est && h->est_kind == 7)) CMFTRY(launch_conv<12>(h, h->est, d.Tl, h->conv_gy));
     set_est(h, 7);
     CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden, true)); // (+ a loss reduction deferred by cmf_iterate)
@@ -615,6 +622,16 @@ static int kl_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 static int kl_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
 {
     const CmfDims &d = h->d;
+    if (h->mu_mask) { // under a mask: R' from Xm' (mode 13 with data = XmT), then the two-source C3 on (mask', R') = [denomH | numH]
+        CMFTRY(launch_conv<13>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext, h->XmT));
+        CMFTRY(launch_transconv(h, 2, h->MT));
+        const size_t TKm = (size_t)d.Tl * d.K32;
+        hipLaunchKernelGGL(h_update_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs + TKm, 2 * TKm, h->tc_S,
+                           h->hslabs, 2 * TKm, h->tc_S, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52 (numerator second)
+        KCHK("h_update_kernel");
+        set_est(h, 0);
+        return wb_after_H(h);
+    }
     CMFTRY(launch_conv<13>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext));
     CMFTRY(launch_transconv(h, 1, h->estT));
     hipLaunchKernelGGL(kl_wsum_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Wt, d.K32, d.Np, h->kl_sums);
@@ -716,6 +733,12 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
 int launch_loss_conv(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
+    if (h->mu_div && h->mu_mask) { // the divergence over the observed entries; R = Xm ./ (est + eps) kept when est is reused
+        if (!h->reuse_est) return launch_conv<18>(h, nullptr, d.Tl, h->conv_gy, h->Xm);
+        CMFTRY(launch_conv<19>(h, h->est, d.Tl, h->conv_gy, h->Xm));
+        set_est(h, 8);
+        return CMF_OK;
+    }
     if (h->mu_div) { // the sum of the divergence terms; R = data ./ (est + eps) kept for the next update_motifs! when est is reused
         if (!h->reuse_est) return launch_conv<14>(h, nullptr, d.Tl, h->conv_gy);
         CMFTRY(launch_conv<15>(h, h->est, d.Tl, h->conv_gy));
@@ -1331,6 +1354,13 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         h->nnls_large = value;
         return CMF_OK;
     }
+    if (std::strcmp(name, "kl_mask") == 0) { // cmf_mu_set_mask + cmf_mu_set_divergence(KL) together (not listed by cmf_option_names: off by default, see the header)
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "kl_mask: the mask and the divergence of the MU rule are chosen on single-GPU handles only");
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "kl_mask must be 0 or 1");
+        if (!value && h->mu_mask && h->mu_div) return fail(CMF_ERR_STATE, "kl_mask: the KL form and a mask are both installed; clear the mask or restore CMF_DIV_SQUARE first");
+        h->kl_mask = value;
+        return CMF_OK;
+    }
     if (h->group) {
         cmf_group_s *g = h->group;
         CMFTRY(group_join(g));
@@ -1689,9 +1719,40 @@ int cmf_hals_update_feature_maps(cmf_handle h, double l1H, double l2H, double *l
     return wb_finish(h, hals_update_feature_maps_body(h, l1H, l2H, loss));
 }
 
+// What the KL form asks of the data it reads (X, or Xm under a mask): finite and non-negative with a positive sum.  One pass over the
+// flat padded array (its padding is zero); *sum is what the divergence is divided by.
+static int kl_check_data(cmf_handle_s *h, const float *X, double *sum_out)
+{
+    const CmfDims &d = h->d;
+    const size_t n4 = (size_t)d.TP * d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h) / 2, std::min<size_t>(1024, (n4 + 255) / 256));
+    if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
+    hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, X, n4, h->partial);
+    KCHK("kl_data_check_kernel");
+    std::vector<double> part((size_t)2 * nb);
+    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double sum = 0.0, bad = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        sum += part[(size_t)b];
+        bad += part[(size_t)nb + b];
+    }
+    if (bad > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", bad);
+    if (!(sum > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
+    *sum_out = sum;
+    return CMF_OK;
+}
+
 // The MU entries leave the masked rule: est, the speculated contraction and a deferred loss are void, the masked copies of data freed.
+// While the KL form is installed (option "kl_mask") the rule goes back to the raw data, which must pass the KL check first: a failure
+// returns CMF_ERR_ARG and leaves the handle as it was.
 static int mu_mask_off(cmf_handle_s *h)
 {
+    if (h->mu_mask && h->mu_div) {
+        double sum = 0.0;
+        CMFTRY(kl_check_data(h, h->X, &sum));
+        h->data_sum = sum;
+    }
     drop_carry(h);
     h->spec_gen = -1;
     set_est(h, 0);
@@ -1723,6 +1784,55 @@ static int mask_select(cmf_handle_s *h, bool write, int comp, double *sumsq)
     return CMF_OK;
 }
 
+// the mask and the masked copies of data, into whichever of h->M, h->MT is not there yet and into fresh h->Xm, h->XmT
+static int mu_install_mask(cmf_handle_s *h, const double *mask)
+{
+    const CmfDims &d = h->d;
+    const size_t TPNp = (size_t)d.TP * d.Np;
+    if (!h->M) CMFTRY(dalloc_zero(&h->M, TPNp));
+    if (!h->MT) CMFTRY(dalloc_zero(&h->MT, TPNp));
+    CMFTRY(upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT));
+    CMFTRY(dalloc_zero(&h->Xm, TPNp));
+    CMFTRY(dalloc_zero(&h->XmT, TPNp));
+    CMFTRY(mask_select(h, true, 0, &h->xm_sumsq));
+    h->xm_norm = std::sqrt(h->xm_sumsq);
+    h->mu_mask = true;
+    set_est(h, 0);
+    return CMF_OK;
+}
+
+// cmf_mu_set_mask while the KL form is installed (option "kl_mask"): the mask goes into buffers of its own, Xm must pass the KL check
+// (finite and non-negative where observed, a positive sum), and only then does it replace what the handle had -- a mask that fails
+// returns CMF_ERR_ARG and leaves the handle as it was (est, the speculation and a deferred loss are void either way).
+static int kl_install_mask(cmf_handle_s *h, const double *mask)
+{
+    drop_carry(h);
+    h->spec_gen = -1;
+    set_est(h, 0);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float *const old[4] = {h->M, h->MT, h->Xm, h->XmT};
+    const bool old_on = h->mu_mask;
+    const double old_ss = h->xm_sumsq, old_norm = h->xm_norm;
+    h->M = h->MT = h->Xm = h->XmT = nullptr;
+    double sum = 0.0;
+    int rc = mu_install_mask(h, mask);
+    if (rc == CMF_OK) rc = kl_check_data(h, h->Xm, &sum);
+    if (rc != CMF_OK) {
+        (void)hipStreamSynchronize(h->stream);
+        for (float *q : {h->M, h->MT, h->Xm, h->XmT})
+            if (q) (void)hipFree(q);
+        h->M = old[0]; h->MT = old[1]; h->Xm = old[2]; h->XmT = old[3];
+        h->mu_mask = old_on;
+        h->xm_sumsq = old_ss;
+        h->xm_norm = old_norm;
+        return rc;
+    }
+    for (float *q : old)
+        if (q) (void)hipFree(q);
+    h->data_sum = sum;
+    return CMF_OK;
+}
+
 int cmf_mu_set_mask(cmf_handle h, const double *mask)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
@@ -1738,7 +1848,7 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
         h->M = h->MT = nullptr;
         return CMF_OK;
     }
-    if (h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
+    if (h->mu_div && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
                                                   "which is not a product of Gram matrices; set gram = 0 first");
     const CmfDims &d = h->d;
@@ -1750,18 +1860,9 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
             return fail(CMF_ERR_ARG, "the MU rule takes a mask of 0 and 1 only (entry %zu is %g); real-valued weights exist for the PGD rule (cmf_set_mask)", i, mask[i]);
     }
     if (ones == 0) return fail(CMF_ERR_ARG, "the mask observes nothing (every entry is 0)");
+    if (h->mu_div) return kl_install_mask(h, mask);
     CMFTRY(mu_mask_off(h));
-    const size_t TPNp = (size_t)d.TP * d.Np;
-    if (!h->M) CMFTRY(dalloc_zero(&h->M, TPNp));
-    if (!h->MT) CMFTRY(dalloc_zero(&h->MT, TPNp));
-    CMFTRY(upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT));
-    CMFTRY(dalloc_zero(&h->Xm, TPNp));
-    CMFTRY(dalloc_zero(&h->XmT, TPNp));
-    CMFTRY(mask_select(h, true, 0, &h->xm_sumsq));
-    h->xm_norm = std::sqrt(h->xm_sumsq);
-    h->mu_mask = true;
-    set_est(h, 0);
-    return CMF_OK;
+    return mu_install_mask(h, mask);
 }
 
 int cmf_mu_set_divergence(cmf_handle h, int kind)
@@ -1787,24 +1888,11 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
     }
     if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no KL form; set gram = 0 first");
-    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: clear the mask of cmf_mu_set_mask first");
-    // data must be finite and non-negative with a positive sum: one pass (the padding of X is zero)
+    if (h->mu_mask && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: clear the mask of cmf_mu_set_mask first");
+    // data must be finite and non-negative with a positive sum: one pass (the padding of X is zero).  Under a mask: where observed (Xm)
     const CmfDims &d = h->d;
-    const size_t n4 = (size_t)d.TP * d.Np / 4;
-    const int nb = (int)std::min<size_t>(n_partial(h) / 2, std::min<size_t>(1024, (n4 + 255) / 256));
-    if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
-    hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, h->partial);
-    KCHK("kl_data_check_kernel");
-    std::vector<double> part((size_t)2 * nb);
-    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    double sum = 0.0, bad = 0.0;
-    for (int b = 0; b < nb; ++b) {
-        sum += part[(size_t)b];
-        bad += part[(size_t)nb + b];
-    }
-    if (bad > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", bad);
-    if (!(sum > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
+    double sum = 0.0;
+    CMFTRY(kl_check_data(h, h->mu_mask ? h->Xm : h->X, &sum));
     if (!h->kl_denH) CMFTRY(dalloc_zero(&h->kl_denH, (size_t)d.Tl * d.K32));
     if (!h->kl_sums) CMFTRY(dalloc_zero(&h->kl_sums, (size_t)d.K32 * std::max(d.L, KL_HCHUNKS)));
     h->data_sum = sum;
@@ -1823,14 +1911,27 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
     const bool comp = complement != 0;
     // One loss-only conv (nothing stored: est, the factors and the rule's state stay as they are) on the raw data with the mask as a
     // select, then the same select on data^2.  Both use the loss partials, one after the other on the stream.
+    // Under the KL form with its mask (option "kl_mask") the pair is (sum of the divergence terms, sum of data) over the selected entries.
+    const bool kl = h->mu_div && h->mu_mask;
     h->mask_complement_now = comp ? 1 : 0;
-    const int rc = launch_conv<10>(h, nullptr, h->d.Tl, h->conv_gy);
+    const int rc = kl ? launch_conv<18>(h, nullptr, h->d.Tl, h->conv_gy) : launch_conv<10>(h, nullptr, h->d.Tl, h->conv_gy);
     h->mask_complement_now = 0;
     CMFTRY(rc);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, h->conv_partials, h->d_scalar + 1, (double *)nullptr);
     KCHK("loss_reduce_kernel");
     CMFTRY(read_scalar(h, 1, resid_sumsq));
-    return mask_select(h, false, comp ? 1 : 0, data_sumsq);
+    if (!kl) return mask_select(h, false, comp ? 1 : 0, data_sumsq);
+    const size_t n4 = (size_t)h->d.TP * h->d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
+    hipLaunchKernelGGL(kl_masked_sum_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, n4, comp ? 1 : 0, h->partial);
+    KCHK("kl_masked_sum_kernel");
+    std::vector<double> part((size_t)nb);
+    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (double v : part) s += v;
+    *data_sumsq = s;
+    return CMF_OK;
 }
 
 int cmf_set_mask(cmf_handle h, const double *mask)

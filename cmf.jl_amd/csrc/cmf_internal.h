@@ -273,7 +273,8 @@ struct cmf_handle_s {
     // the KL form of the MU rule (cmf_mu_set_divergence): est / estT hold R = data ./ (est + eps) (est_kind 7) where the squared-error
     // rule keeps est, the contractions run on that one source, and the denominators come from two small tables (kl_den_w / kl_den_h)
     int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL
-    double data_sum = 0.0;       // sum(data): what the divergence is divided by
+    double data_sum = 0.0;       // sum(data): what the divergence is divided by (under a mask: sum(Xm))
+    int kl_mask = 0;             // cmf_set_option "kl_mask": 1 lets the KL form and a mask of cmf_mu_set_mask be installed together
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
     double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
 
@@ -294,7 +295,8 @@ struct cmf_handle_s {
     std::vector<hipEvent_t> prof_pool;
     int est_kind = 0;       // what est[t][n] holds for the resident W, H: 0 nothing, 1 tensor_conv(W,H), 2 tensor_conv(W,H) - data, 3 mask .* (tensor_conv(W,H) - data),
                             // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient), 6 mask .* tensor_conv(W,H) (the MU rule
-                            // under a mask: mu_est_kind), 7 data ./ (tensor_conv(W,H) + eps) (the KL form of the MU rule)
+                            // under a mask: mu_est_kind), 7 data ./ (tensor_conv(W,H) + eps) (the KL form of the MU rule), 8 Xm ./ (tensor_conv(W,H) + eps)
+                            // (R of the KL form under a mask: exactly 0 where the mask is 0)
     void *arena = nullptr;  // the small buffers of the handle as ONE device allocation (cmf_create): 21 hipFree calls cost 1.3 ms, one 0.16
     size_t arena_bytes = 0;
     bool streams_may_hang = false;  // set on the shards of a FAILED group: their streams are not waited for when they are given back
@@ -494,7 +496,7 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
 // cmf_mu_set_mask is installed.  reuse_est, the speculated C2 contraction and the deferred loss carry all compare against mu_est_kind.
 static inline const float *mu_X(const cmf_handle_s *h) { return h->mu_mask ? h->Xm : h->X; }
 static inline const float *mu_XT(const cmf_handle_s *h) { return h->mu_mask ? h->XmT : h->XT; }
-static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? 6 : h->mu_div ? 7 : 1; }
+static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? (h->mu_div ? 8 : 6) : h->mu_div ? 7 : 1; }
 static inline double mu_norm(const cmf_handle_s *h) { return h->mu_mask ? h->xm_norm : h->data_norm; }
 // the loss of the MU entries from the sum its loss conv leaves: norm(est - data) / norm(data), or D(data, est) / sum(data) under KL
 static inline double mu_loss(const cmf_handle_s *h, double ss) { return h->mu_div ? ss / h->data_sum : std::sqrt(ss) / mu_norm(h); }
@@ -633,17 +635,18 @@ struct ProfScope {
 template <int MODE>
 static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
 {
-    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms (cmf_kernels.h)
-    constexpr int BASE = MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
+    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms; 18, 19: modes 14, 15 under the mask (cmf_kernels.h)
+    constexpr int BASE = MODE >= 16 ? MODE - 16 : MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
+    constexpr bool KLM = CONV_KL_MASKED(MODE);
     ProfScope prof_(h, BASE == 0 ? PROF_CONV : BASE == 1 ? PROF_CONV_T : BASE == 2 ? PROF_CONV_LOSS : BASE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
-    if (MODE >= 8 && MODE <= 11 && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
+    if (((MODE >= 8 && MODE <= 11) || KLM) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
     p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (MODE == 13 ? h->XT : h->X); p.partial = h->partial;
     p.mask = (MODE == 7 || MODE == 9) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
-    p.loss_abs = (MODE >= 4 && MODE <= 7) ? h->pgd_loss_abs_now : (MODE == 10 ? h->mask_complement_now : 0);
+    p.loss_abs = (MODE >= 4 && MODE <= 7) ? h->pgd_loss_abs_now : ((MODE == 10 || MODE == 18) ? h->mask_complement_now : 0);
     dim3 grid(h->conv_gx, gy), block(256);
     // measured at config 2 (tools/time_kernels.py): the one-wave kernel wins for the epilogues that read data
     // (0.924 vs 0.931 ms loss only, 0.936 vs 0.943 ms loss + store), the 128 x 128 tiles for the store-only ones
@@ -693,7 +696,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         }
     }
     const bool split = cut > 0;
-    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
+    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13 && !KLM) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
     if (d.K % 32 == 0 && variant == 3) {
         const int n_full = tiles3 - cut;
         // quarter tiles reach every SIMD only from one tile per CU on; below that, sixteenth tiles
@@ -706,8 +709,9 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         // the 128 x 128 kernel exists for the epilogues that only store or only sum (est, est', loss): with a data tile
         // read AND a store in the epilogue (mode 3 and the residual modes) it needs more than the 168 registers three
         // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
-        // (KL: the loss-only mode alone -- modes 12 and 13 read a data tile and store, and run on the one-wave kernel like mode 3)
-        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13;
+        // (KL: the loss-only mode alone -- modes 12 and 13 read a data tile and store, and run on the one-wave kernel like mode 3;
+        //  mode 18 adds a mask tile to mode 14's operands and is routed to the one-wave tiles whatever option "conv_kernel" says)
+        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13 && !KLM;
         if constexpr (TILES128) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
         if constexpr (TILES128) h->launches[LA_CONV2] += 1;
     } else {

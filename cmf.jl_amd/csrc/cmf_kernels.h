@@ -75,20 +75,25 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //     MODE 12: store R[t][n] = data / e                    MODE 13: store R'[n][t] (p.data = dataT [Np][TP])
 //     MODE 14: no store; per-workgroup sum of the divergence terms (data > 0 ? data log(data / e) : 0) - data + est -> partial[]
 //     MODE 15: MODE 12 + MODE 14
-//     Padding (n >= N, where data and est are 0) stores 0 / eps = 0 and adds 0 to the sum.  (16 .. 19 are left for these under a mask.)
+//     Padding (n >= N, where data and est are 0) stores 0 / eps = 0 and adds 0 to the sum.
+//   MODE 18, 19: modes 14 and 15 under the MU rule's 0/1 mask (p.mask [t][n], the mask tile of modes 10 and 11): the summed term is
+//     obs ? term : 0, a SELECT.  MODE 19 is given p.data = Xm = select(mask, data, 0) and stores R = Xm / e (exactly 0 where mask == 0).
+//     MODE 18 with p.loss_abs != 0 sums over the entries with mask == 0 instead and is then given the raw data (cmf_masked_loss).
+//     The store-only forms under a mask need no mode of their own: modes 12 and 13 with p.data = Xm / XmT store 0 / (v + eps) = 0 at
+//     the held-out entries (16 and 17 stay unassigned).  Padding (mask == 0) adds exactly 0.
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
     const float *Wt;
     float *out;
-    const float *data; // X [TP][Np] (modes 2, 3, 4, 6, 10 - 12, 14, 15) or XT [Np][TP] (modes 5, 7, 13)
-    const float *mask; // same layout as data (modes 6, 7)
+    const float *data; // X [TP][Np] (modes 2, 3, 4, 6, 10 - 12, 14, 15, 18, 19) or XT [Np][TP] (modes 5, 7, 13)
+    const float *mask; // same layout as data (modes 6 - 11, 18, 19)
     double *partial;   // [gridDim.x * gridDim.y]
     int Np, TP, PADL, K, KB, L;
     int T_store; // rows t < T_store are stored / counted
     int N;       // columns n >= N are padding: a 32-column MFMA block that lies wholly behind N is not computed (its sums are 0)
     int loss_abs; // residual modes (4-7): 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
-                  // MODE 10: 1 = the sum runs over the entries with mask == 0 (the complement)
+                  // MODE 10, 18: 1 = the sum runs over the entries with mask == 0 (the complement)
 };
 
 // agent-scope accesses (global_load / global_store ... sc1): the hand-off forms of MI355X_MICROARCH.md "inter-workgroup visibility"
@@ -107,9 +112,10 @@ __device__ __forceinline__ f32x4 cmf_load4_sc1(const float *p)
 
 #define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9 || (MODE) == 13)
 #define CONV_MU_MASKED(MODE) ((MODE) >= 8 && (MODE) <= 11)       // the masked forms of modes 0 .. 3
-#define CONV_KL(MODE) ((MODE) >= 12 && (MODE) <= 15)             // the KL forms: R = data / (est + eps) stored, the divergence summed
-#define CONV_KL_STORE(MODE) ((MODE) == 12 || (MODE) == 15)
-#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15)
+#define CONV_KL_MASKED(MODE) ((MODE) == 18 || (MODE) == 19)      // modes 14 and 15 under the MU rule's mask: the summed term is a select
+#define CONV_KL(MODE) (((MODE) >= 12 && (MODE) <= 15) || CONV_KL_MASKED(MODE)) // the KL forms: R = data / (est + eps) stored, the divergence summed
+#define CONV_KL_STORE(MODE) ((MODE) == 12 || (MODE) == 15 || (MODE) == 19)
+#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15 || CONV_KL_MASKED(MODE))
 #define CONV_PGD(MODE) ((MODE) >= 4 && (MODE) <= 7)              // the residual modes (the only ones p.loss_abs = AbsoluteLoss applies to)
 #define CONV_HS_STRIDE 160
 #define CONV_HS_FLOATS (32 * CONV_HS_STRIDE)
@@ -143,6 +149,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
@@ -164,12 +171,36 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
             // all operand loads of a group first (the W registers are dead by now), then arithmetic and stores: a load
             // queued behind stores would wait for them on the in-order vmcnt.  A group is the whole 64 x 64 sub-tile,
             // or one 32 x 32 block when the mask doubles the operands (the registers do not stretch further).
-            constexpr int GT = (MASKED || (MUM && LOSS)) ? 1 : 2; // blocks per group along t and n
-            const bool comp = (MODE == 10) && p.loss_abs; // wave-uniform: the sum over the held-out entries
+            constexpr int GT = (MASKED || ((MUM || KLM) && LOSS)) ? 1 : 2; // blocks per group along t and n
+            const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs; // wave-uniform: the sum over the held-out entries
 #pragma unroll
             for (int gt = 0; gt < 2; gt += GT)
 #pragma unroll
                 for (int gn = 0; gn < 2; gn += GT) {
+                    if constexpr (KLM && PRE) {
+                        // mode 19 with the preloaded data tile (conv3_tile): the 64 preloaded values, a block's 16 mask values and the
+                        // logarithm's temporaries do not fit beside the accumulators (3 VGPRs spilled), so the mask of the block is
+                        // loaded in two halves of 8 elements, each half before its own stores.  Same arithmetic, element for element.
+#pragma unroll
+                        for (int r0 = 0; r0 < 16; r0 += 8) {
+                            float mh[8];
+#pragma unroll
+                            for (int r = r0; r < r0 + 8; ++r)
+                                mh[r - r0] = cmf_bload(rm, voff, ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4);
+#pragma unroll
+                            for (int r = r0; r < r0 + 8; ++r) {
+                                const int so = ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4;
+                                const float v = acc[gt][gn][r], x = pre[gt][gn][r];
+                                const float q = cmf_kl_ratio(x, v);
+                                cmf_bstore(q, ro, voff, so);
+                                float d = cmf_kl_term(x, v, q);
+                                d = ((mh[r - r0] != 0.f) != comp) ? d : 0.f;
+                                if (PARTIAL) d = (gt * 32 + cmf_crow(r, h) < rows) ? d : 0.f;
+                                lsum += d;
+                            }
+                        }
+                        continue;
+                    }
                     float dv[GT][GT][16], mv[GT][GT][16];
 #pragma unroll
                     for (int ti = 0; ti < GT; ++ti)
@@ -180,7 +211,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                 const int so = (((gt + ti) * 32 + (r & 3) + 8 * (r >> 2)) * Np + (gn + ni) * 32) * 4;
                                 dv[ti][ni][r] = !(LOSS || KL) ? 0.f : (PRE && !MASKED) ? pre[gt + ti][gn + ni][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
                                                                                : cmf_bload(rd, voff, so); // rows past T_store read as 0 (masked below)
-                                mv[ti][ni][r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
+                                mv[ti][ni][r] = (MASKED || MUM || KLM) ? cmf_bload(rm, voff, so) : 1.f;
                             }
 #pragma unroll
                     for (int ti = 0; ti < GT; ++ti)
@@ -201,6 +232,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                     const float q = cmf_kl_ratio(dv[ti][ni][r], v);
                                     if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
                                     if (LOSS) d = cmf_kl_term(dv[ti][ni][r], v, q);
+                                    if (KLM) d = ((mv[ti][ni][r] != 0.f) != comp) ? d : 0.f;
                                 }
                                 if (RESID) {
                                     if (ABS) {
@@ -596,7 +628,7 @@ __device__ __forceinline__ void conv3_tile(const ConvParams &p, float *Hs, int t
     // HBM round trip per tile; here it is requested before the loop (64 registers that the few k pairs leave free) with the epilogue's
     // descriptor and offsets, and the epilogue finds it there (protocol shape: 37.8 -> 35.8 us).  On a launch of many rounds (N = 2000:
     // eight tiles per SIMD slot, bandwidth-bound) the W rows of the first lags queue behind these 64 loads and it costs 7 %: not used there.
-    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15) && NKP <= 4 && NBL == 2);
+    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15 || MODE == 19) && NKP <= 4 && NBL == 2);
     float dpre[2][2][16];
     if (PRE) {
         int rows = p.T_store - t0;
@@ -658,8 +690,9 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
-    const bool comp = (MODE == 10) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
+    const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) {
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
@@ -674,7 +707,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
         for (int r = 0; r < 16; ++r) {
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
             dv[r] = (LOSS || KL) ? cmf_bload(rd, voff, so) : 0.f; // rows past T_store read as 0 (masked below)
-            mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
+            mv[r] = (MASKED || MUM || KLM) ? cmf_bload(rm, voff, so) : 1.f;
         }
         float lsum = 0.f;
 #pragma unroll
@@ -692,6 +725,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
                 const float q = cmf_kl_ratio(dv[r], v);
                 if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
                 if (LOSS) d = cmf_kl_term(dv[r], v, q);
+                if (KLM) d = ((mv[r] != 0.f) != comp) ? d : 0.f;
             }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
@@ -851,8 +885,9 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
     constexpr bool MASKED = (MODE == 6 || MODE == 7);
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs;
-    const bool comp = (MODE == 10) && p.loss_abs; // wave-uniform: the sum over the held-out entries
+    const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs; // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
@@ -866,7 +901,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             dv[r] = (LOSS || KL) ? cmf_bload(rd, voff, r * Np * 4) : 0.f;
-            mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, r * Np * 4) : 1.f;
+            mv[r] = (MASKED || MUM || KLM) ? cmf_bload(rm, voff, r * Np * 4) : 1.f;
         }
         float lsum = 0.f;
 #pragma unroll
@@ -883,6 +918,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
                 const float q = cmf_kl_ratio(dv[r], v);
                 if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, r * Np * 4);
                 if (LOSS) d = cmf_kl_term(dv[r], v, q);
+                if (KLM) d = ((mv[r] != 0.f) != comp) ? d : 0.f;
             }
             if (RESID) {
                 const float sg = (v > dv[r]) ? 1.f : ((v < dv[r]) ? -1.f : 0.f);
@@ -3636,6 +3672,23 @@ static __global__ __launch_bounds__(256) void kl_data_check_kernel(const float *
         partial[blockIdx.x] = s;
         partial[gridDim.x + blockIdx.x] = bad;
     }
+}
+
+// cmf_masked_loss under KL: partial[b] = the block's fp64 sum of the entries of the flat padded data [TP][Np] that the mask selects
+// (comp: those with M == 0; the padding of X is zero and adds nothing).  A select: what data holds elsewhere never enters.
+static __global__ __launch_bounds__(256) void kl_masked_sum_kernel(const float *X, const float *M, size_t n4, int comp, double *partial)
+{
+    __shared__ double red[256];
+    double s = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * 256) {
+        const float4 x = reinterpret_cast<const float4 *>(X)[idx];
+        const float4 m = reinterpret_cast<const float4 *>(M)[idx];
+        const float xv[4] = {x.x, x.y, x.z, x.w}, mv[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += ((mv[q] != 0.f) != (comp != 0)) ? (double)xv[q] : 0.0;
+    }
+    s = cmf_block_sum_f64(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 #define KL_HCHUNKS 16

@@ -308,7 +308,9 @@ class MultUpdate(AbstractCFUpdate):
 
     def masked_loss(self, complement=False):
         """(sum of (tensor_conv(W, H) - data)^2, sum of data^2) over the entries with mask == 1 -- with ``complement`` over those
-        with mask == 0 -- for the resident factors (cmf_masked_loss); est, the factors and the rule's state stay as they are."""
+        with mask == 0 -- for the resident factors (cmf_masked_loss); est, the factors and the rule's state stay as they are.
+        Under ``set_divergence(":kl")`` with a mask (option "kl_mask") the pair is (sum of the divergence terms
+        (x > 0 ? x log(x / e) : 0) - x + e, sum of data) over the same entries: their quotient is the KL loss on them."""
         r, d = ctypes.c_double(), ctypes.c_double()
         check(self._lib.cmf_masked_loss(self._h, int(bool(complement)), ctypes.byref(r), ctypes.byref(d)))
         return r.value, d.value
@@ -318,7 +320,9 @@ class MultUpdate(AbstractCFUpdate):
         """``":kl"``: the multiplicative update of the generalised Kullback-Leibler divergence (Smaragdis' convolutive NMF), for counts
         and spectrogram magnitudes: R = data ./ (est + eps) takes the place of data in the numerators, the denominators are sums of H
         and of W, and the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative with a positive sum.
-        ``":square"`` restores the squared-error rule of mult.jl exactly."""
+        ``":square"`` restores the squared-error rule of mult.jl exactly.  Together with ``set_mask`` (either order) after
+        ``set_option("kl_mask", 1)``: R = select(mask, data, 0) ./ (est + eps), the denominators are the contractions of H and of W
+        with the mask, the loss runs over the observed entries, and data need be valid only where observed."""
         check(self._lib.cmf_mu_set_divergence(self._h, _divergence_kind(kind)))
 
     # -- the two rule methods -----------------------------------------------------------
@@ -1207,8 +1211,9 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if rule_type is not MultUpdate:
             raise NotImplementedError("divergence=':kl' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable fits "
                                       "minimise the squared error (PGD also the absolute error)")
-        if mask is not None:
-            raise NotImplementedError("divergence=':kl' is not available with mask=: the KL form of the MU rule has no masked form yet")
+        if mask is not None and not (options or {}).get("kl_mask", 0):
+            raise NotImplementedError("divergence=':kl' is not available with mask=: the KL form of the MU rule has no masked form yet "
+                                      "unless the library option is set: options={'kl_mask': 1}")
         if devices is not None:
             raise NotImplementedError("divergence=':kl' is not available with devices=[...]: the KL form of the MU rule runs on one GPU")
     if rule_type is Separable:
@@ -1335,17 +1340,24 @@ def holdout_mask(N, T, frac=0.1, block=1, seed=None):
     return np.asfortranarray(np.where(held, 0.0, 1.0))
 
 
-def evaluate_heldout(r, mask, device=None):
+def evaluate_heldout(r, mask, device=None, divergence=":square"):
     """(train, test) = sqrt(sum of (est - data)^2 / sum of data^2) over the entries with ``mask == 1`` and over those with
-    ``mask == 0``, for the fitted model ``r`` (cmf_masked_loss: one loss-only conv each, sums by select)."""
+    ``mask == 0``, for the fitted model ``r`` (cmf_masked_loss: one loss-only conv each, sums by select).
+    ``divergence=":kl"``: D / sum(data) over the same two sets of entries, D the sum of the divergence terms there (no square
+    root): what ``fit_cnmf(divergence=":kl", mask=...)`` records in ``loss_hist``, and its held-out counterpart."""
     mask = farr(mask, np.shape(r.data))
+    kl = _divergence_kind(divergence)
     rule = MultUpdate(r.data, r.W, r.H, device=device)
     try:
+        if kl:
+            rule.set_option("kl_mask", 1)
         rule.set_mask(mask)
+        if kl:
+            rule.set_divergence(":kl")
         out = []
         for comp in (False, True):
             resid, dat = rule.masked_loss(complement=comp)
-            out.append(math.sqrt(resid / dat) if dat > 0 else math.nan)
+            out.append((resid / dat if kl else math.sqrt(resid / dat)) if dat > 0 else math.nan)
         return out[0], out[1]
     finally:
         rule.close()
@@ -1369,6 +1381,8 @@ def _process_group(group):
 def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=None, group=None, **fit_kw):
     """Held-out scores for choosing L and K: for every (L, K) and every repeat, draw ``holdout_mask(N, T, frac, block, seed')``,
     fit ``fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=seed', **fit_kw)`` and score it with ``evaluate_heldout``.
+    ``divergence=":kl"`` (for counts) fits the KL form under the mask -- the library option "kl_mask" is set here, beside whatever
+    ``options=`` holds -- and scores with the same divergence.
     Returns ``{(L, K): {"train": array(repeats), "test": array(repeats)}}``.  ``block`` defaults to the combination's L.
     seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
     by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
@@ -1381,6 +1395,9 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     jobs = [(c, rep) for c in combos for rep in range(int(repeats))]
     dist, rank, world = _process_group(group)
     device = fit_kw.get("device", None)
+    divergence = fit_kw.get("divergence", ":square")
+    if _divergence_kind(divergence):
+        fit_kw["options"] = dict(fit_kw.get("options") or {}, kl_mask=1)
     mine = {}
     for idx, ((L, K), rep) in enumerate(jobs):
         if idx % world != rank:
@@ -1388,7 +1405,7 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
         s = None if seed is None else int(seed) + idx
         mask = holdout_mask(N, T, frac=frac, block=L if block is None else block, seed=s)
         r = fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=s, **fit_kw)
-        mine[idx] = evaluate_heldout(r, mask, device=device)
+        mine[idx] = evaluate_heldout(r, mask, device=device, divergence=divergence)
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, mine, group=group)

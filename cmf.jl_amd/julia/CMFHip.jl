@@ -447,17 +447,21 @@ function update_feature_maps!(rule::HIPANLSUpdate, data, W, H; variant=:basic, k
     return loss[]
 end
 
-# evaluate_heldout(data, W, H, mask; device=0) -> (train, test): sqrt(sum of (est - data)^2 / sum of data^2) over the entries with
-# mask == 1 and over those with mask == 0, for a fitted model (cmf_masked_loss: one loss-only conv each, sums by select, so NaNs among
-# the held-out data stay out of the train score).
-function evaluate_heldout(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Float64}, mask; device::Integer=0)
+# evaluate_heldout(data, W, H, mask; device=0, divergence=:square) -> (train, test): sqrt(sum of (est - data)^2 / sum of data^2) over
+# the entries with mask == 1 and over those with mask == 0, for a fitted model (cmf_masked_loss: one loss-only conv each, sums by
+# select, so NaNs among the held-out data stay out of the train score).  divergence=:kl: D / sum(data) over the same two sets of
+# entries (no square root), through the library option "kl_mask" (the KL form of the MU rule under a mask, include/cmf_hip.h).
+function evaluate_heldout(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Float64}, mask; device::Integer=0, divergence::Symbol=:square)
+    divergence in (:square, :kl) || throw(ArgumentError("divergence must be :square or :kl"))
     rule = HIPMultUpdate(data, W, H; device=device, sync_every_call=false)
+    divergence === :kl && set_option!(rule, "kl_mask", 1)
     select_mask!(rule, mask)
+    divergence === :kl && set_divergence!(rule, :kl)
     scores = Float64[]
     for complement in (0, 1)
         r, d = Ref{Float64}(0.0), Ref{Float64}(0.0)
         check(ccall((:cmf_masked_loss, LIBCMF), Cint, (Ptr{Cvoid}, Cint, Ref{Float64}, Ref{Float64}), rule.handle, complement, r, d))
-        push!(scores, sqrt(r[] / d[]))
+        push!(scores, divergence === :kl ? r[] / d[] : sqrt(r[] / d[]))
     end
     finalize(rule)
     return scores[1], scores[2]
@@ -477,7 +481,7 @@ function iterate!(rule::HIPMultUpdate, n::Integer; l1W=0, l2W=0, l1H=0, l2H=0, e
     return losses
 end
 
-"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", ..."
+"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", \"kl_mask\" (set_divergence!(rule, :kl) together with a mask), ..."
 set_option!(rule::HIPMultUpdate, name::AbstractString, value::Integer) =
     check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), rule.handle, name, value))
 "The ANLS rule's options: \"anls_backup_only\", \"nnls_large\" (include/cmf_hip.h, the ANLS rule)."

@@ -442,6 +442,20 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
 #define CMF_DIV_SQUARE 0
 #define CMF_DIV_KL 1
 int cmf_mu_set_divergence(cmf_handle h, int kind);
+/* The KL form under a mask: cmf_set_option(h, "kl_mask", 1) (default 0; values other than 0 and 1: CMF_ERR_ARG; cmf_option_names does
+ * not list it, like "nnls_large" below).  With it on, cmf_mu_set_mask under CMF_DIV_KL and cmf_mu_set_divergence(CMF_DIV_KL) under
+ * a mask both succeed, in either order, and the MU entries run, with M the mask and Xm = select(M, data, 0),
+ *   update_motifs!:        R = Xm ./ e (exactly 0 where M == 0, whatever data holds there);  numW as above from this R;
+ *                          denomW[:, :, l] = shift_cols(H, l) * M[:, 1+l:T]'  (mult.jl:33 with est -> M: no longer the same for every n)
+ *   update_feature_maps!:  R from the new W;  numH = tensor_transconv(W, R);  denomH = tensor_transconv(W, M)
+ * LOSS: D_M / sum(Xm), D_M the divergence terms summed over the entries with M == 1.  Data must be finite and non-negative WHERE
+ * OBSERVED with sum(Xm) > 0: installing the second of the two checks Xm, and whatever takes the MU mask away while CMF_DIV_KL is
+ * installed (cmf_mu_set_mask(h, NULL), cmf_set_mask) checks the raw data first -- CMF_ERR_ARG, and the handle as it was, when a
+ * check fails.  A unit or a sample with nothing observed is legal (numerator and denominator are 0 there: its factor entries fall
+ * to eps); with an all-ones mask the rule is the unmasked KL rule.  cmf_masked_loss then returns (sum of the divergence terms, sum
+ * of data) over the selected entries.  Turning the option off while both are installed: CMF_ERR_STATE.  Off (the default), every
+ * call answers as documented above: CMF_ERR_UNSUPPORTED for the combination.  Groups, the Gram forms, the HALS and PGD entries and
+ * real-valued weights stay refused as above. */
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
