@@ -221,6 +221,8 @@ static void destroy_impl(cmf_handle_s *h)
         if (mine(p)) (void)hipFree(p);
     if (h->kl_denH) (void)hipFree(h->kl_denH);
     if (h->kl_sums) (void)hipFree(h->kl_sums);
+    if (h->est2) (void)hipFree(h->est2);
+    if (h->est2T) (void)hipFree(h->est2T);
     for (int v = 0; v < 3; ++v)
         if (h->tc_tab[v]) (void)hipFree(h->tc_tab[v]);
     if (mine(h->partial)) (void)hipFree(h->partial);
@@ -646,11 +648,44 @@ static int kl_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
     return wb_after_H(h);
 }
 
+// update_motifs! of the Itakura-Saito form: one conv stores P = (data ./ e) ./ e into est and Q = 1 ./ e into est2 (kept from the loss
+// conv when est is reused), the two-source C2 contraction on (P, Q) is [numW | denomW] (mult.jl:32-33 with data -> P, est -> Q), and the
+// element-wise update takes the square root of the quotient.  One path for every K, as under KL: the few-component fusions (the slab
+// sum inside w_update_small_kernel, the speculated contraction) are not taken.
+static int is_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
+{
+    const CmfDims &d = h->d;
+    if (!(h->reuse_est && h->est_kind == 9)) CMFTRY(launch_conv<20>(h, h->est, d.Tl, h->conv_gy));
+    set_est(h, 9);
+    CMFTRY(hxt_contract(h, h->est, h->est2, 2, h->numden, true)); // [numW | denomW] (+ a loss reduction deferred by cmf_iterate)
+    hipLaunchKernelGGL(w_update_sqrt_kernel, dim3(d.Np / 64, d.KB, d.L), dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, h->numden + (size_t)d.L * d.K32 * d.Np,
+                       d.N, d.K, d.L, d.Np, d.K32, (float)l1W, (float)(2.0 * l2W), (const float *)nullptr, (float *)nullptr, 0);
+    KCHK("w_update_sqrt_kernel");
+    set_est(h, 0);
+    return CMF_OK;
+}
+
+// update_feature_maps! of the Itakura-Saito form up to the loss: P' and Q' with the new W from one conv, the two-source C3 on
+// (Q', P') = [denomH | numH], and the square-root update.  The few-component fusion of the update into the C3 launch is not taken.
+static int is_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
+{
+    const CmfDims &d = h->d;
+    CMFTRY(launch_conv<21>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext));
+    CMFTRY(launch_transconv(h, 2, h->est2T));
+    const size_t TK = (size_t)d.Tl * d.K32;
+    hipLaunchKernelGGL(h_update_sqrt_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs + TK, 2 * TK, h->tc_S,
+                       h->hslabs, 2 * TK, h->tc_S, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // (numerator second)
+    KCHK("h_update_sqrt_kernel");
+    set_est(h, 0);
+    return wb_after_H(h);
+}
+
 // update_motifs! of the MU rule on a single handle (mult.jl:23-39).  Few components: conv (unless est is current), the C2
 // kernel, and ONE launch that sums its slabs, updates W and packs the C3 operand (w_update_small_kernel).
 static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 {
     const CmfDims &d = h->d;
+    if (h->mu_div == CMF_DIV_IS) return is_w_phase_impl(h, l1W, l2W);
     if (h->mu_div) return kl_w_phase_impl(h, l1W, l2W);
     if (!h->small_k) {
         CMFTRY(w_partial_impl(h));
@@ -710,6 +745,7 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         set_est(h, 0);
         return wb_after_H(h);
     }
+    if (h->mu_div == CMF_DIV_IS) return is_h_update_impl(h, l1H, l2H);
     if (h->mu_div) return kl_h_update_impl(h, l1H, l2H);
     if (h->mu_mask) CMFTRY(launch_conv<9>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // (mask .* est)' under the MU rule's mask
     else CMFTRY(launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
@@ -733,6 +769,12 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
 int launch_loss_conv(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
+    if (h->mu_div == CMF_DIV_IS) { // the sum of the Itakura-Saito terms; P and Q kept for the next update_motifs! when est is reused
+        if (!h->reuse_est) return launch_conv<22>(h, nullptr, d.Tl, h->conv_gy);
+        CMFTRY(launch_conv<23>(h, h->est, d.Tl, h->conv_gy));
+        set_est(h, 9);
+        return CMF_OK;
+    }
     if (h->mu_div && h->mu_mask) { // the divergence over the observed entries; R = Xm ./ (est + eps) kept when est is reused
         if (!h->reuse_est) return launch_conv<18>(h, nullptr, d.Tl, h->conv_gy, h->Xm);
         CMFTRY(launch_conv<19>(h, h->est, d.Tl, h->conv_gy, h->Xm));
@@ -1361,6 +1403,13 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         h->kl_mask = value;
         return CMF_OK;
     }
+    if (std::strcmp(name, "is_div") == 0) { // lets cmf_mu_set_divergence take CMF_DIV_IS (not listed by cmf_option_names: off by default, see the header)
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "is_div: the divergence of the MU rule is chosen on single-GPU handles only");
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "is_div must be 0 or 1");
+        if (!value && h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "is_div: the Itakura-Saito divergence is installed; restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
+        h->is_div = value;
+        return CMF_OK;
+    }
     if (h->group) {
         cmf_group_s *g = h->group;
         CMFTRY(group_join(g));
@@ -1425,6 +1474,8 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
     if (std::strcmp(name, "gram") == 0) {
         if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "gram must be 0, 1 or 2");
         if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
+        if (value && h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no Itakura-Saito form: "
+                                                                               "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no KL form: "
                                                                  "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
@@ -1677,6 +1728,7 @@ int cmf_hals_update_motifs(cmf_handle h, double l1W, double l2W)
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
+    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     h->last_rule_call = 1;
     return hals_w_impl(h, l1W, l2W);
@@ -1688,6 +1740,7 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     if (!loss) return fail(CMF_ERR_ARG, "loss is NULL");
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
+    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates (alternating.jl:51-54): update_motifs! comes next
     h->last_rule_call = 2;
@@ -1848,6 +1901,8 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
         h->M = h->MT = nullptr;
         return CMF_OK;
     }
+    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form (its Q = 1 ./ e would need the mask tile in the storing "
+                                                                   "epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->mu_div && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
                                                   "which is not a product of Gram matrices; set gram = 0 first");
@@ -1865,10 +1920,54 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
     return mu_install_mask(h, mask);
 }
 
+// What the Itakura-Saito form asks of data: finite and strictly positive at every entry that exists.  One pass (is_data_check_kernel).
+static int is_check_data(cmf_handle_s *h)
+{
+    const CmfDims &d = h->d;
+    const size_t n4 = (size_t)d.TP * d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
+    if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
+    hipLaunchKernelGGL(is_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, d.Np, d.N, d.PADL, d.Tl, h->partial);
+    KCHK("is_data_check_kernel");
+    std::vector<double> part((size_t)nb);
+    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double bad = 0.0;
+    for (double v : part) bad += v;
+    if (bad > 0.0)
+        return fail(CMF_ERR_ARG, "Itakura-Saito divergence needs finite, strictly positive data (%.0f entries are zero, negative, NaN or infinite): "
+                                 "add a small floor to the spectrogram, e.g. data + 1e-6 * max(data)", bad);
+    return CMF_OK;
+}
+
+// cmf_mu_set_divergence(CMF_DIV_IS) (est, the speculation and the carry have been voided): refusals, the data check, the second pair
+// of est-shaped buffers.  A failure leaves the divergence the handle had.
+static int is_install(cmf_handle_s *h)
+{
+    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no Itakura-Saito form; set gram = 0 first");
+    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
+    CMFTRY(is_check_data(h));
+    const CmfDims &d = h->d;
+    if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
+    if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
+    if (h->mu_div == CMF_DIV_KL) { // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->kl_denH) (void)hipFree(h->kl_denH);
+        if (h->kl_sums) (void)hipFree(h->kl_sums);
+        h->kl_denH = nullptr;
+        h->kl_sums = nullptr;
+    }
+    h->data_sum = (double)d.N * (double)d.Tl;
+    h->mu_div = CMF_DIV_IS;
+    return CMF_OK;
+}
+
 int cmf_mu_set_divergence(cmf_handle h, int kind)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    if (kind != CMF_DIV_SQUARE && kind != CMF_DIV_KL) return fail(CMF_ERR_ARG, "kind must be CMF_DIV_SQUARE (0) or CMF_DIV_KL (1)");
+    // (CMF_DIV_IS is taken only with option "is_div" set; without it every call answers as it did before the form existed)
+    if (kind != CMF_DIV_SQUARE && kind != CMF_DIV_KL && !(kind == CMF_DIV_IS && h->is_div))
+        return fail(CMF_ERR_ARG, h->is_div ? "kind must be CMF_DIV_SQUARE (0), CMF_DIV_KL (1) or CMF_DIV_IS (2)" : "kind must be CMF_DIV_SQUARE (0) or CMF_DIV_KL (1)");
     if (h->group || h->root_only || h->sharded)
         return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
     HIPCHK(hipSetDevice(h->device));
@@ -1887,6 +1986,7 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
         return CMF_OK;
     }
     if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
+    if (kind == CMF_DIV_IS) return is_install(h);
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no KL form; set gram = 0 first");
     if (h->mu_mask && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: clear the mask of cmf_mu_set_mask first");
     // data must be finite and non-negative with a positive sum: one pass (the padding of X is zero).  Under a mask: where observed (Xm)
@@ -1984,6 +2084,7 @@ int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int nonne
         return group_pgd_w(h, h->group, pen_sq, pen_abs, nonneg);
     }
     CMFTRY(check_ready(h, true));
+    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_w_impl(h, pen_sq, pen_abs, nonneg);
 }
@@ -1997,6 +2098,7 @@ static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_
         return group_pgd_h(h, h->group, pen_sq, pen_abs, nonneg, loss);
     }
     CMFTRY(check_ready(h, true));
+    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_h_impl(h, pen_sq, pen_abs, nonneg, loss);
 }

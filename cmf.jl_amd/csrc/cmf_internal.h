@@ -277,6 +277,11 @@ struct cmf_handle_s {
     int kl_mask = 0;             // cmf_set_option "kl_mask": 1 lets the KL form and a mask of cmf_mu_set_mask be installed together
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
     double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
+    // the Itakura-Saito form (option "is_div", then cmf_mu_set_divergence(CMF_DIV_IS)): est / estT hold P = (data ./ e) ./ e and the second
+    // pair est2 / est2T holds Q = 1 ./ e, e = tensor_conv(W,H) + eps (est_kind 9); both contractions run on the pair (P, Q) in their
+    // two-source forms.  data_sum is then N * Tl: the loss is the mean divergence per entry.
+    int is_div = 0;              // cmf_set_option "is_div": 1 lets cmf_mu_set_divergence take CMF_DIV_IS
+    float *est2 = nullptr, *est2T = nullptr; // [TP][Np] / [Np][TP], zero-filled; allocated when the form is first installed, kept until the handle goes
 
     double data_sumsq = 0.0, data_norm = 0.0;
     bool factors_set = false;
@@ -296,7 +301,7 @@ struct cmf_handle_s {
     int est_kind = 0;       // what est[t][n] holds for the resident W, H: 0 nothing, 1 tensor_conv(W,H), 2 tensor_conv(W,H) - data, 3 mask .* (tensor_conv(W,H) - data),
                             // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient), 6 mask .* tensor_conv(W,H) (the MU rule
                             // under a mask: mu_est_kind), 7 data ./ (tensor_conv(W,H) + eps) (the KL form of the MU rule), 8 Xm ./ (tensor_conv(W,H) + eps)
-                            // (R of the KL form under a mask: exactly 0 where the mask is 0)
+                            // (R of the KL form under a mask: exactly 0 where the mask is 0), 9 P of the Itakura-Saito form (and est2 holds Q)
     void *arena = nullptr;  // the small buffers of the handle as ONE device allocation (cmf_create): 21 hipFree calls cost 1.3 ms, one 0.16
     size_t arena_bytes = 0;
     bool streams_may_hang = false;  // set on the shards of a FAILED group: their streams are not waited for when they are given back
@@ -496,9 +501,10 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
 // cmf_mu_set_mask is installed.  reuse_est, the speculated C2 contraction and the deferred loss carry all compare against mu_est_kind.
 static inline const float *mu_X(const cmf_handle_s *h) { return h->mu_mask ? h->Xm : h->X; }
 static inline const float *mu_XT(const cmf_handle_s *h) { return h->mu_mask ? h->XmT : h->XT; }
-static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_mask ? (h->mu_div ? 8 : 6) : h->mu_div ? 7 : 1; }
+static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_div == 2 ? 9 : h->mu_mask ? (h->mu_div ? 8 : 6) : h->mu_div ? 7 : 1; }
 static inline double mu_norm(const cmf_handle_s *h) { return h->mu_mask ? h->xm_norm : h->data_norm; }
 // the loss of the MU entries from the sum its loss conv leaves: norm(est - data) / norm(data), or D(data, est) / sum(data) under KL
+// (Itakura-Saito: data_sum holds N * T, the mean divergence per entry)
 static inline double mu_loss(const cmf_handle_s *h, double ss) { return h->mu_div ? ss / h->data_sum : std::sqrt(ss) / mu_norm(h); }
 int wb_after_H(cmf_handle_s *h); // hook: the kernels that make H final have been enqueued (cmf_writeback.h)
 int gram_ensure(cmf_handle_s *h);
@@ -635,14 +641,17 @@ struct ProfScope {
 template <int MODE>
 static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
 {
-    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms; 18, 19: modes 14, 15 under the mask (cmf_kernels.h)
-    constexpr int BASE = MODE >= 16 ? MODE - 16 : MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
+    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms; 18, 19: modes 14, 15 under the mask;
+    // modes 20 .. 23: the Itakura-Saito forms of modes 0 .. 3, which store P through out and Q through the handle's second pair (cmf_kernels.h)
+    constexpr int BASE = MODE >= 20 ? MODE - 20 : MODE >= 16 ? MODE - 16 : MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
     constexpr bool KLM = CONV_KL_MASKED(MODE);
     ProfScope prof_(h, BASE == 0 ? PROF_CONV : BASE == 1 ? PROF_CONV_T : BASE == 2 ? PROF_CONV_LOSS : BASE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
     if (((MODE >= 8 && MODE <= 11) || KLM) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
-    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (MODE == 13 ? h->XT : h->X); p.partial = h->partial;
+    if (CONV_IS(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito conv without its second pair of buffers");
+    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : ((MODE == 13 || MODE == 21) ? h->XT : h->X); p.partial = h->partial;
+    p.out2 = MODE == 21 ? h->est2T : CONV_IS(MODE) ? h->est2 : nullptr;
     p.mask = (MODE == 7 || MODE == 9) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
@@ -696,7 +705,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         }
     }
     const bool split = cut > 0;
-    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13 && !KLM) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
+    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13 && !KLM && MODE != 20 && MODE != 21) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
     if (d.K % 32 == 0 && variant == 3) {
         const int n_full = tiles3 - cut;
         // quarter tiles reach every SIMD only from one tile per CU on; below that, sixteenth tiles
@@ -711,7 +720,8 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
         // (KL: the loss-only mode alone -- modes 12 and 13 read a data tile and store, and run on the one-wave kernel like mode 3;
         //  mode 18 adds a mask tile to mode 14's operands and is routed to the one-wave tiles whatever option "conv_kernel" says)
-        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13 && !KLM;
+        // (Itakura-Saito: the loss-only mode 22 alone, like KL)
+        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13 && !KLM && MODE != 20 && MODE != 21;
         if constexpr (TILES128) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
         if constexpr (TILES128) h->launches[LA_CONV2] += 1;
     } else {
@@ -734,6 +744,7 @@ static int launch_conv_rows(cmf_handle_s *h, float *out, int row0, int nrows, in
     const CmfDims &d = h->d;
     ConvParams p;
     p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = h->X; p.partial = h->partial; p.mask = h->M;
+    p.out2 = nullptr;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store >= 0 ? T_store : d.Tl;
     p.N = d.N;
     p.loss_abs = 0;

@@ -81,6 +81,13 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //     MODE 18 with p.loss_abs != 0 sums over the entries with mask == 0 instead and is then given the raw data (cmf_masked_loss).
 //     The store-only forms under a mask need no mode of their own: modes 12 and 13 with p.data = Xm / XmT store 0 / (v + eps) = 0 at
 //     the held-out entries (16 and 17 stay unassigned).  Padding (mask == 0) adds exactly 0.
+//   MODE 20 .. 23: the Itakura-Saito form of the MU rule (option "is_div"), e = est + eps, Q = 1 / e, P = (data * Q) * Q.  ONE accumulator
+//     tile stores TWO arrays: P through p.out, Q through p.out2.
+//     MODE 20: store P[t][n], Q[t][n]                      MODE 21: store P'[n][t], Q'[n][t] (p.data = dataT [Np][TP])
+//     MODE 22: no store; per-workgroup sum of the divergence terms (r - 1) - log(r), r = data * Q -> partial[]
+//     MODE 23: MODE 20 + MODE 22
+//     Padding: Q = 1 / (0 + eps) is NOT 0 there, so columns n >= N are stored as exact 0 and add 0 to the sum by a SELECT on n < p.N
+//     (in partly live 32-column blocks and in the wholly dead ones whose MFMAs are skipped alike).
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
@@ -94,6 +101,8 @@ struct ConvParams {
     int N;       // columns n >= N are padding: a 32-column MFMA block that lies wholly behind N is not computed (its sums are 0)
     int loss_abs; // residual modes (4-7): 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
                   // MODE 10, 18: 1 = the sum runs over the entries with mask == 0 (the complement)
+    float *out2; // modes 20, 21, 23: the second array stored from the same accumulators (Q; out takes P), in the layout of out.  (Last, so
+                 // that no other field moves: the kernels of the other modes compile to what they were.)
 };
 
 // agent-scope accesses (global_load / global_store ... sc1): the hand-off forms of MI355X_MICROARCH.md "inter-workgroup visibility"
@@ -110,12 +119,14 @@ __device__ __forceinline__ f32x4 cmf_load4_sc1(const float *p)
     return v;
 }
 
-#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9 || (MODE) == 13)
+#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9 || (MODE) == 13 || (MODE) == 21)
 #define CONV_MU_MASKED(MODE) ((MODE) >= 8 && (MODE) <= 11)       // the masked forms of modes 0 .. 3
 #define CONV_KL_MASKED(MODE) ((MODE) == 18 || (MODE) == 19)      // modes 14 and 15 under the MU rule's mask: the summed term is a select
 #define CONV_KL(MODE) (((MODE) >= 12 && (MODE) <= 15) || CONV_KL_MASKED(MODE)) // the KL forms: R = data / (est + eps) stored, the divergence summed
 #define CONV_KL_STORE(MODE) ((MODE) == 12 || (MODE) == 15 || (MODE) == 19)
-#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15 || CONV_KL_MASKED(MODE))
+#define CONV_IS(MODE) ((MODE) >= 20 && (MODE) <= 23)             // the Itakura-Saito forms: P and Q stored, the divergence summed
+#define CONV_IS_STORE(MODE) ((MODE) == 20 || (MODE) == 21 || (MODE) == 23)
+#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15 || CONV_KL_MASKED(MODE) || (MODE) == 22 || (MODE) == 23)
 #define CONV_PGD(MODE) ((MODE) >= 4 && (MODE) <= 7)              // the residual modes (the only ones p.loss_abs = AbsoluteLoss applies to)
 #define CONV_HS_STRIDE 160
 #define CONV_HS_FLOATS (32 * CONV_HS_STRIDE)
@@ -132,6 +143,225 @@ __device__ __forceinline__ void cmf_bstore(float v, __amdgpu_buffer_rsrc_t r, in
 // exactly where data is unless the quotient underflows, and there data log(data / e) is 0 to fp32 as well.  Padding: 0 / eps = 0, term 0.
 __device__ __forceinline__ float cmf_kl_ratio(float x, float v) { return x / (v + CMF_EPS_F); }
 __device__ __forceinline__ float cmf_kl_term(float x, float v, float q) { return ((q > 0.f) ? x * logf(q) : 0.f) + (v - x); }
+
+// The Itakura-Saito epilogue of one element (modes 20 .. 23).  q = 1 / (est + eps) where the column exists and exact 0 in the padding
+// (a select: 1 / eps there would pour into the denominators of the contractions that read Q); P = (x q) q, never x / (e e), whose
+// divisor underflows where e is near eps; the divergence term (r - 1) - log(r) in that order, r = x q (r - 1 is exact for r in [0.5, 2];
+// the product is rounded on its own -- contraction is off in these two functions -- so that every tile form sums the same bits).
+__device__ __forceinline__ float cmf_is_q(float v, bool live) { return live ? 1.f / (v + CMF_EPS_F) : 0.f; }
+__device__ __forceinline__ float cmf_is_p(float x, float q)
+{
+#pragma clang fp contract(off)
+    return (x * q) * q;
+}
+__device__ __forceinline__ float cmf_is_term(float x, float q)
+{
+#pragma clang fp contract(off) // (r - 1 must not become fma(x, q, -1) in one mode and a subtraction in another: modes 22 and 23 sum the same bits)
+    const float r = x * q;
+    const float d = r - 1.f;
+    return d - logf(r);
+}
+// wave sum on the DPP network (row shifts, then the two row broadcasts): the total lands in lane 63
+__device__ __forceinline__ float cmf_wave_sum63(float x)
+{
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x111, 0xf, 0xf, false)); // row_shr:1
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x112, 0xf, 0xf, false)); // row_shr:2
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x114, 0xf, 0xf, false)); // row_shr:4
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x118, 0xf, 0xf, false)); // row_shr:8
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x142, 0xa, 0xf, false)); // row_bcast:15
+    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x143, 0xc, 0xf, false)); // row_bcast:31
+    return x;
+}
+
+// conv_epilogue_ of the Itakura-Saito modes: the same descriptors and offsets, one 32 x 32 block at a time (a block's 16 data values
+// before its 32 stores: two stores per accumulator leave no room for a wider group), P through p.out and Q through p.out2.
+template <int MODE, int WAVES, bool PRE>
+__device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const ConvParams &p, int tw, int nw, int i, int h, int lane, int wave,
+                                                  int tid, int pidx, const float (&pre)[2][2][16])
+{
+    const int Np = p.Np, TP = p.TP;
+    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
+    if (!CONV_TRANSPOSED(MODE)) {
+        // acc[ti][ni][r]: t = tw + ti*32 + crow(r,h), n = nw + ni*32 + i
+        int rows = p.T_store - tw; // rows of the sub-tile that exist
+        rows = rows < 0 ? 0 : (rows > 64 ? 64 : rows);
+        const size_t origin = (size_t)(p.PADL + tw) * Np + nw;
+        const size_t bytes = rows ? ((size_t)(rows - 1) * Np + 64) * 4 : 0;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * h * Np + i) * 4;
+        float lsum = 0.f;
+#pragma unroll
+        for (int gt = 0; gt < 2; ++gt)
+#pragma unroll
+            for (int gn = 0; gn < 2; ++gn) {
+                const bool live = nw + gn * 32 + i < p.N; // this lane's column exists
+                float dv[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    dv[r] = PRE ? pre[gt][gn][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
+                                : cmf_bload(rd, voff, ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4); // rows past T_store read as 0 (selected away below)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int so = ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4;
+                    const float q = cmf_is_q(acc[gt][gn][r], live);
+                    if (STORE) {
+                        cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
+                        cmf_bstore(q, ro2, voff, so);
+                    }
+                    if (LOSS) lsum += (live && gt * 32 + cmf_crow(r, h) < rows) ? cmf_is_term(dv[r], q) : 0.f;
+                }
+            }
+        if (LOSS) {
+            const float x = cmf_wave_sum63(lsum);
+            if (WAVES == 4) {
+                __shared__ float red[4];
+                if (lane == 63) red[wave] = x;
+                __syncthreads();
+                if (tid == 0) p.partial[pidx] = ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]);
+            } else {
+                if (lane == 63) p.partial[pidx] = (double)x;
+            }
+        }
+    } else {
+        // MODE 21: acc[ni][ti][r]: n = nw + ni*32 + crow(r,h), t = tw + ti*32 + i; p.data is dataT [Np][TP]
+        const size_t origin = (size_t)nw * TP + p.PADL + tw;
+        const size_t bytes = ((size_t)63 * TP + 64) * 4;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * h * TP + i) * 4;
+        const bool full = (tw + 64 <= p.T_store); // wave-uniform
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int ti = 0; ti < 2; ++ti) {
+                if (full || tw + ti * 32 + i < p.T_store) {
+                    float dv[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) dv[r] = cmf_bload(rd, voff, ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
+                        const float q = cmf_is_q(acc[ni][ti][r], nw + ni * 32 + cmf_crow(r, h) < p.N);
+                        cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
+                        cmf_bstore(q, ro2, voff, so);
+                    }
+                }
+            }
+    }
+}
+
+// conv_epilogue_block of the Itakura-Saito modes (one 32 x 32 block at (tb, nb))
+template <int MODE>
+__device__ __forceinline__ void conv_is_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
+{
+    const int Np = p.Np, TP = p.TP;
+    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
+    if (!CONV_TRANSPOSED(MODE)) {
+        int rows = p.T_store - tb;
+        rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
+        const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
+        const size_t bytes = rows ? ((size_t)(rows - 1) * Np + 32) * 4 : 0;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * h * Np + i) * 4;
+        const bool live = nb + i < p.N;
+        float dv[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dv[r] = cmf_bload(rd, voff, (((r & 3) + 8 * (r >> 2)) * Np) * 4); // rows past T_store read as 0 (selected away below)
+        float lsum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
+            const float q = cmf_is_q(acc[r], live);
+            if (STORE) {
+                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
+                cmf_bstore(q, ro2, voff, so);
+            }
+            if (LOSS) lsum += (live && cmf_crow(r, h) < rows) ? cmf_is_term(dv[r], q) : 0.f;
+        }
+        if (LOSS) {
+            const float x = cmf_wave_sum63(lsum);
+            if (lane == 63) p.partial[pidx] = (double)x;
+        }
+    } else {
+        const size_t origin = (size_t)nb * TP + p.PADL + tb;
+        const size_t bytes = ((size_t)31 * TP + 32) * 4;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * h * TP + i) * 4;
+        if (tb + i < p.T_store) {
+            float dv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dv[r] = cmf_bload(rd, voff, (((r & 3) + 8 * (r >> 2)) * TP) * 4);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
+                const float q = cmf_is_q(acc[r], nb + cmf_crow(r, h) < p.N);
+                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
+                cmf_bstore(q, ro2, voff, so);
+            }
+        }
+    }
+}
+
+// conv16_epilogue of the Itakura-Saito modes (one 16 x 16 block; lane = 16*kq + j)
+template <int MODE>
+__device__ __forceinline__ void conv16_is_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
+{
+    const int Np = p.Np, TP = p.TP;
+    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
+    if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
+        int rows = p.T_store - tb;
+        rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
+        const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
+        const size_t bytes = rows ? ((size_t)(rows - 1) * Np + 16) * 4 : 0;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * kq * Np + j) * 4;
+        const bool live = nb + j < p.N;
+        float dv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dv[r] = cmf_bload(rd, voff, r * Np * 4);
+        float lsum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float q = cmf_is_q(acc[r], live);
+            if (STORE) {
+                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, r * Np * 4);
+                cmf_bstore(q, ro2, voff, r * Np * 4);
+            }
+            if (LOSS) lsum += (live && 4 * kq + r < rows) ? cmf_is_term(dv[r], q) : 0.f;
+        }
+        if (LOSS) {
+            const float x = cmf_wave_sum63(lsum);
+            if (lane == 63) p.partial[pidx] = (double)x;
+        }
+    } else { // acc[r]: n = nb + 4*kq + r, t = tb + j
+        const size_t origin = (size_t)nb * TP + p.PADL + tb;
+        const size_t bytes = ((size_t)15 * TP + 16) * 4;
+        const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
+        const __amdgpu_buffer_rsrc_t ro2 = cmf_rsrc(p.out2 + origin, bytes);
+        const __amdgpu_buffer_rsrc_t rd = cmf_rsrc(p.data + origin, bytes);
+        const int voff = (4 * kq * TP + j) * 4;
+        if (tb + j < p.T_store) {
+            float dv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dv[r] = cmf_bload(rd, voff, r * TP * 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float q = cmf_is_q(acc[r], nb + 4 * kq + r < p.N);
+                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, r * TP * 4);
+                cmf_bstore(q, ro2, voff, r * TP * 4);
+            }
+        }
+    }
+}
 
 // Every access of the epilogue is a buffer load / store: descriptor on the wave's 64 x 64 sub-tile (a wave-uniform
 // base), one per-lane byte offset, and a scalar offset per element -- no vector address arithmetic (VALU slots are
@@ -153,6 +383,10 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
+    if constexpr (CONV_IS(MODE)) { // the Itakura-Saito modes: two stores per accumulator, an epilogue of their own
+        conv_is_epilogue_<MODE, WAVES, PRE>(acc, p, tw, nw, i, h, lane, wave, tid, pidx, pre);
+        return;
+    }
     if (!CONV_TRANSPOSED(MODE)) {
         // acc[ti][ni][r]: t = tw + ti*32 + crow(r,h), n = nw + ni*32 + i
         int rows = p.T_store - tw; // rows of the sub-tile that exist
@@ -628,7 +862,7 @@ __device__ __forceinline__ void conv3_tile(const ConvParams &p, float *Hs, int t
     // HBM round trip per tile; here it is requested before the loop (64 registers that the few k pairs leave free) with the epilogue's
     // descriptor and offsets, and the epilogue finds it there (protocol shape: 37.8 -> 35.8 us).  On a launch of many rounds (N = 2000:
     // eight tiles per SIMD slot, bandwidth-bound) the W rows of the first lags queue behind these 64 loads and it costs 7 %: not used there.
-    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15 || MODE == 19) && NKP <= 4 && NBL == 2);
+    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15 || MODE == 19 || MODE == 23) && NKP <= 4 && NBL == 2);
     float dpre[2][2][16];
     if (PRE) {
         int rows = p.T_store - t0;
@@ -691,6 +925,10 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
+    if constexpr (CONV_IS(MODE)) {
+        conv_is_epilogue_block<MODE>(acc, p, tb, nb, i, h, lane, pidx);
+        return;
+    }
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
     const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) {
@@ -886,6 +1124,10 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
     constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
+    if constexpr (CONV_IS(MODE)) {
+        conv16_is_epilogue<MODE>(acc, p, tb, nb, j, kq, lane, pidx);
+        return;
+    }
     const bool abs_loss = CONV_PGD(MODE) && p.loss_abs;
     const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs; // wave-uniform: the sum over the held-out entries
     if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
@@ -1503,43 +1745,60 @@ __device__ __forceinline__ float cmf_mu(float x, float num, float den, float l1,
     return (y != y) ? y : fmaxf(CMF_EPS_F, y);
 }
 
+// The Itakura-Saito step (beta < 1: the majorisation-minimisation exponent 1/2):  x <- max(eps, x * sqrt(num / (((den + l1) + (2*l2)*x) + eps)))
+__device__ __forceinline__ float cmf_mu_sqrt(float x, float num, float den, float l1, float two_l2)
+{
+    float d = ((den + l1) + two_l2 * x) + CMF_EPS_F;
+    float y = x * sqrtf(num / d);
+    return (y != y) ? y : fmaxf(CMF_EPS_F, y);
+}
+template <bool SQRT>
+__device__ __forceinline__ float cmf_mu_step(float x, float num, float den, float l1, float two_l2)
+{
+    return SQRT ? cmf_mu_sqrt(x, num, den, l1, two_l2) : cmf_mu(x, num, den, l1, two_l2);
+}
+
 // grid: (Np/64, KB, L), block 256.  num, den: [L][K32][Np] each
 // tail_src / tail_dst (may be NULL): block (0,0,0) also copies `tail_n` (<= 256) floats -- the loss pairs behind the
 // [numW | denomW] all-reduce buffer of a sharded group -- to pinned host memory that the host has filled with a
 // sentinel pattern and polls, so the read-back costs neither a launch nor an event (see loss_reduce_kernel).
-static __global__ __launch_bounds__(256) void w_update_kernel(float *Wt, float *Wn, const float *num_p, const float *den_p,
-                                                        int N, int K, int L, int Np, int K32, float l1, float two_l2,
-                                                        const float *tail_src, float *tail_dst, int tail_n)
-{
-    __shared__ float tile[32][65];
-    const int tid = threadIdx.x;
-    if (tail_dst && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid < tail_n) // relaxed system-scope word stores:
-        __hip_atomic_store(tail_dst + tid, tail_src[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // the host polls every word
-    const int n0 = blockIdx.x * 64, kb = blockIdx.y, l = blockIdx.z;
-    {
-        const int nn = tid & 63;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            int kk = q * 4 + (tid >> 6);
-            int k = kb * 32 + kk, n = n0 + nn;
-            size_t idx = ((size_t)l * K32 + k) * Np + n;
-            const float num = num_p[idx], den = den_p[idx];
-            float w = Wt[idx];
-            float wn = (k < K && n < N) ? cmf_mu(w, num, den, l1, two_l2) : 0.f;
-            Wt[idx] = wn;
-            tile[kk][nn] = wn;
-        }
+// (w_update_sqrt_kernel, the sibling of the Itakura-Saito form, is this text with STEP = cmf_mu_sqrt: stated once as a macro, not as a
+// shared __device__ body, which moved w_update_kernel's registers (19 -> 16 VGPRs) in tools/kernel_resources.py's table)
+#define CMF_W_UPDATE_KERNEL(NAME, STEP)                                                                                                  \
+    static __global__ __launch_bounds__(256) void NAME(float *Wt, float *Wn, const float *num_p, const float *den_p,                     \
+                                                       int N, int K, int L, int Np, int K32, float l1, float two_l2,                     \
+                                                       const float *tail_src, float *tail_dst, int tail_n)                               \
+    {                                                                                                                                    \
+        __shared__ float tile[32][65];                                                                                                   \
+        const int tid = threadIdx.x;                                                                                                     \
+        if (tail_dst && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid < tail_n) /* relaxed system-scope word stores: */   \
+            __hip_atomic_store(tail_dst + tid, tail_src[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); /* the host polls every word */ \
+        const int n0 = blockIdx.x * 64, kb = blockIdx.y, l = blockIdx.z;                                                                 \
+        {                                                                                                                                \
+            const int nn = tid & 63;                                                                                                     \
+            _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                                              \
+                int kk = q * 4 + (tid >> 6);                                                                                             \
+                int k = kb * 32 + kk, n = n0 + nn;                                                                                       \
+                size_t idx = ((size_t)l * K32 + k) * Np + n;                                                                             \
+                const float num = num_p[idx], den = den_p[idx];                                                                          \
+                float w = Wt[idx];                                                                                                       \
+                float wn = (k < K && n < N) ? STEP(w, num, den, l1, two_l2) : 0.f;                                                       \
+                Wt[idx] = wn;                                                                                                            \
+                tile[kk][nn] = wn;                                                                                                       \
+            }                                                                                                                            \
+        }                                                                                                                                \
+        __syncthreads();                                                                                                                 \
+        {                                                                                                                                \
+            const int kk = tid & 31;                                                                                                     \
+            _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                                              \
+                int nn = q * 8 + (tid >> 5);                                                                                             \
+                Wn[((size_t)l * Np + n0 + nn) * K32 + kb * 32 + kk] = tile[kk][nn];                                                      \
+            }                                                                                                                            \
+        }                                                                                                                                \
     }
-    __syncthreads();
-    {
-        const int kk = tid & 31;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            int nn = q * 8 + (tid >> 5);
-            Wn[((size_t)l * Np + n0 + nn) * K32 + kb * 32 + kk] = tile[kk][nn];
-        }
-    }
-}
+CMF_W_UPDATE_KERNEL(w_update_kernel, cmf_mu)
+CMF_W_UPDATE_KERNEL(w_update_sqrt_kernel, cmf_mu_sqrt)
+#undef CMF_W_UPDATE_KERNEL
 
 // grid: (ceil(Tl/8), KB), block 256.  slabs: [S][2][Tl][K32]
 // A workgroup owns 8 columns x 32 components = 64 float4 elements; its four 64-thread groups each sum every
@@ -1549,9 +1808,10 @@ static __global__ __launch_bounds__(256) void w_update_kernel(float *Wt, float *
 // num / den: Snum / Sden partial-sum slabs of [Tl][K32] floats, `num_stride` / `den_stride` floats apart (the two-source
 // transconv writes [S][2][Tl][K32]: num = slabs, den = slabs + Tl*K32, both strides 2*Tl*K32; the Gram form has the S1
 // slabs of the one-source launch for num and ONE array for den).
-static __global__ __launch_bounds__(256) void h_update_kernel(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
-                                                        const float *denp, size_t den_stride, int Sden,
-                                                        int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
+template <bool SQRT>
+__device__ __forceinline__ void h_update_body(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
+                                              const float *denp, size_t den_stride, int Sden,
+                                              int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
 {
     __shared__ f32x4 red[3][64][2];
     __shared__ float tile[32][HUPD_T + 1];
@@ -1599,7 +1859,7 @@ static __global__ __launch_bounds__(256) void h_update_kernel(float *H, float *H
         f32x4 hn = {0.f, 0.f, 0.f, 0.f};
         if (t < Tl && k < K) { // (the padding stays the zero it is)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) hn[c] = (k + c < K) ? cmf_mu(x[c], num[c], den[c], l1, two_l2) : 0.f;
+            for (int c = 0; c < 4; ++c) hn[c] = (k + c < K) ? cmf_mu_step<SQRT>(x[c], num[c], den[c], l1, two_l2) : 0.f;
             *hp = hn;
         }
 #pragma unroll
@@ -1610,6 +1870,18 @@ static __global__ __launch_bounds__(256) void h_update_kernel(float *H, float *H
         const int kk = tid >> 3, t2 = t0 + (tid & 7);
         if (t2 < Tl) Ht[(size_t)(kb * 32 + kk) * TP + PADL + t2] = tile[kk][tid & 7];
     }
+}
+static __global__ __launch_bounds__(256) void h_update_kernel(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
+                                                        const float *denp, size_t den_stride, int Sden,
+                                                        int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
+{
+    h_update_body<false>(H, Ht, nump, num_stride, Snum, denp, den_stride, Sden, Tl, K, K32, PADL, TP, l1, two_l2);
+}
+static __global__ __launch_bounds__(256) void h_update_sqrt_kernel(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
+                                                             const float *denp, size_t den_stride, int Sden,
+                                                             int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
+{
+    h_update_body<true>(H, Ht, nump, num_stride, Snum, denp, den_stride, Sden, Tl, K, K32, PADL, TP, l1, two_l2);
 }
 
 // A thread's share of the sum of n per-tile loss sums (256 threads; element e goes to thread e % 256, accumulator (e / 256) % 8):
@@ -3672,6 +3944,28 @@ static __global__ __launch_bounds__(256) void kl_data_check_kernel(const float *
         partial[blockIdx.x] = s;
         partial[gridDim.x + blockIdx.x] = bad;
     }
+}
+
+// What the Itakura-Saito form asks of data: partial[b] = how many of the block's entries that exist (time rows [PADL, PADL + Tl), columns
+// n < N of the flat padded [TP][Np]) are not finite and strictly positive -- an exact zero has infinite Itakura-Saito divergence.
+static __global__ __launch_bounds__(256) void is_data_check_kernel(const float *X, size_t n4, int Np, int N, int PADL, int Tl, double *partial)
+{
+    __shared__ double red[256];
+    double bad = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * 256) {
+        const float4 x = reinterpret_cast<const float4 *>(X)[idx];
+        const float xv[4] = {x.x, x.y, x.z, x.w};
+        const size_t row = (idx * 4) / (size_t)Np;
+        const int n = (int)((idx * 4) % (size_t)Np); // (Np is a multiple of 128: the four entries share a row)
+        const bool row_live = row >= (size_t)PADL && row < (size_t)PADL + (size_t)Tl;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool ok = xv[q] > 0.f && xv[q] <= 3.402823466e+38f; // (false for NaN)
+            bad += (row_live && n + q < N && !ok) ? 1.0 : 0.0;
+        }
+    }
+    bad = cmf_block_sum_f64(bad, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = bad;
 }
 
 // cmf_masked_loss under KL: partial[b] = the block's fp64 sum of the entries of the flat padded data [TP][Np] that the mask selects

@@ -126,13 +126,16 @@ def rccl_version():
 # --------------------------------------------------------------------------------------
 # update rules (the plugin boundary: abstract type AbstractCFUpdate, alternating.jl:1-8)
 # --------------------------------------------------------------------------------------
-_DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1}  # CMF_DIV_SQUARE, CMF_DIV_KL (include/cmf_hip.h)
+# CMF_DIV_SQUARE, CMF_DIV_KL, CMF_DIV_IS (include/cmf_hip.h)
+_DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1, ":itakura_saito": 2, "itakura_saito": 2}
+_DIV_IS = 2
+_DIV_NAMES = {0: ":square", 1: ":kl", 2: ":itakura_saito"}
 
 
 def _divergence_kind(kind):
     key = kind if isinstance(kind, str) else (":" + getattr(kind, "name", str(kind)))
     if key not in _DIVERGENCES:
-        raise ValueError(f"divergence must be ':square' or ':kl', got {kind!r}")
+        raise ValueError(f"divergence must be ':square' or ':kl' (or ':itakura_saito', spelled out), got {kind!r}")
     return _DIVERGENCES[key]
 
 
@@ -322,8 +325,16 @@ class MultUpdate(AbstractCFUpdate):
         and of W, and the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative with a positive sum.
         ``":square"`` restores the squared-error rule of mult.jl exactly.  Together with ``set_mask`` (either order) after
         ``set_option("kl_mask", 1)``: R = select(mask, data, 0) ./ (est + eps), the denominators are the contractions of H and of W
-        with the mask, the loss runs over the observed entries, and data need be valid only where observed."""
-        check(self._lib.cmf_mu_set_divergence(self._h, _divergence_kind(kind)))
+        with the mask, the loss runs over the observed entries, and data need be valid only where observed.
+        ``":itakura_saito"``: the multiplicative update of the Itakura-Saito divergence (beta = 0), the scale-invariant objective for
+        power spectrograms: with Q = 1 ./ (est + eps) and P = (data .* Q) .* Q the numerators contract P, the denominators Q, the
+        update takes the square root of their quotient, and the loss is the mean of (r - 1) - log(r), r = data ./ (est + eps), per
+        entry.  Data must be finite and strictly positive (add a floor to the spectrogram).  The library option "is_div" is set
+        here; no mask, no Gram form, one GPU."""
+        code = _divergence_kind(kind)
+        if code == _DIV_IS:
+            self.set_option("is_div", 1)
+        check(self._lib.cmf_mu_set_divergence(self._h, code))
 
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
@@ -1152,7 +1163,7 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
              "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
              "mask",  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
-             "divergence"}  # alg=:mult: ":square" (default) or ":kl" (MultUpdate.set_divergence)
+             "divergence"}  # alg=:mult: ":square" (default), ":kl" or ":itakura_saito" (MultUpdate.set_divergence)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -1207,7 +1218,17 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if not np.isin(mask, (0.0, 1.0)).all():
             raise ValueError("mask must hold 0 and 1 only (1 = observed)")
     divergence = _divergence_kind(kw.get("divergence", ":square"))
-    if divergence:
+    if divergence == _DIV_IS:
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("divergence=':itakura_saito' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
+                                      "fits minimise the squared error (PGD also the absolute error)")
+        if mask is not None:
+            raise NotImplementedError("divergence=':itakura_saito' is not available with mask=: the Itakura-Saito form of the MU rule "
+                                      "has no masked form")
+        if devices is not None:
+            raise NotImplementedError("divergence=':itakura_saito' is not available with devices=[...]: the Itakura-Saito form of the "
+                                      "MU rule runs on one GPU")
+    elif divergence:
         if rule_type is not MultUpdate:
             raise NotImplementedError("divergence=':kl' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable fits "
                                       "minimise the squared error (PGD also the absolute error)")
@@ -1251,7 +1272,7 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if mask is not None:
             rule.set_mask(mask)  # (before the loop: loss_hist[0] is the masked loss too)
         if divergence:
-            rule.set_divergence(":kl")  # (before the loop: loss_hist[0] is the divergence too)
+            rule.set_divergence(_DIV_NAMES[divergence])  # (before the loop: loss_hist[0] is the divergence too)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
         loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence")}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
@@ -1283,7 +1304,8 @@ def evaluate_mse(r, device=None):
 
 def evaluate_divergence(r, kind=":kl", device=None):
     """The loss of the fitted model ``r`` under ``kind`` (cmf_compute_loss): for ``":kl"`` D(data, est + eps) / sum(data), what
-    ``fit_cnmf(divergence=":kl")`` records in ``loss_hist``; for ``":square"`` evaluate_mse's value."""
+    ``fit_cnmf(divergence=":kl")`` records in ``loss_hist``; for ``":itakura_saito"`` the mean Itakura-Saito divergence per entry
+    (what ``fit_cnmf(divergence=":itakura_saito")`` records); for ``":square"`` evaluate_mse's value."""
     rule = MultUpdate(r.data, r.W, r.H, device=device)
     try:
         rule.set_divergence(kind)
@@ -1345,8 +1367,11 @@ def evaluate_heldout(r, mask, device=None, divergence=":square"):
     ``mask == 0``, for the fitted model ``r`` (cmf_masked_loss: one loss-only conv each, sums by select).
     ``divergence=":kl"``: D / sum(data) over the same two sets of entries, D the sum of the divergence terms there (no square
     root): what ``fit_cnmf(divergence=":kl", mask=...)`` records in ``loss_hist``, and its held-out counterpart."""
-    mask = farr(mask, np.shape(r.data))
     kl = _divergence_kind(divergence)
+    if kl == _DIV_IS:
+        raise NotImplementedError("divergence=':itakura_saito' has no held-out score: the Itakura-Saito form of the MU rule has no "
+                                  "masked form")
+    mask = farr(mask, np.shape(r.data))
     rule = MultUpdate(r.data, r.W, r.H, device=device)
     try:
         if kl:
@@ -1387,6 +1412,9 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
     by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
     combinations and the scores gathered on all ranks."""
+    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_IS:
+        raise NotImplementedError("cross_validate(divergence=':itakura_saito') is not available: the Itakura-Saito form of the MU rule "
+                                  "has no masked form, so nothing can be held out")
     data = farr(data)
     N, T = data.shape
     if "mask" in fit_kw or "alg" in fit_kw:

@@ -182,9 +182,15 @@ end
 # set_divergence!(rule, :kl): the rule becomes the multiplicative update of the generalised Kullback-Leibler divergence
 # (cmf_mu_set_divergence): R = data ./ (est + eps) takes the place of data in mult.jl:32 and :47, the denominators are sums of H and
 # of W, the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative.  :square restores mult.jl exactly.
+# :itakura_saito (CMF_DIV_IS, for power spectrograms; data strictly positive): the library option "is_div" is set here first.
+const CMF_DIV_SQUARE = 0
+const CMF_DIV_KL = 1
+const CMF_DIV_IS = 2
 function set_divergence!(rule::HIPMultUpdate, kind::Symbol)
-    kind in (:square, :kl) || throw(ArgumentError("divergence must be :square or :kl"))
-    check(ccall((:cmf_mu_set_divergence, LIBCMF), Cint, (Ptr{Cvoid}, Cint), rule.handle, kind === :kl ? 1 : 0))
+    kind in (:square, :kl, :itakura_saito) || throw(ArgumentError("divergence must be :square, :kl or :itakura_saito"))
+    kind === :itakura_saito && set_option!(rule, "is_div", 1)
+    check(ccall((:cmf_mu_set_divergence, LIBCMF), Cint, (Ptr{Cvoid}, Cint), rule.handle,
+                kind === :kl ? CMF_DIV_KL : kind === :itakura_saito ? CMF_DIV_IS : CMF_DIV_SQUARE))
     return rule
 end
 

@@ -456,6 +456,27 @@ int cmf_mu_set_divergence(cmf_handle h, int kind);
  * of data) over the selected entries.  Turning the option off while both are installed: CMF_ERR_STATE.  Off (the default), every
  * call answers as documented above: CMF_ERR_UNSUPPORTED for the combination.  Groups, the Gram forms, the HALS and PGD entries and
  * real-valued weights stay refused as above. */
+/* CMF_DIV_IS: the multiplicative update of the Itakura-Saito divergence (beta = 0; beta_loss="itakura-saito" elsewhere), the
+ * scale-invariant objective for POWER spectrograms: a quiet harmonic weighs as much as a loud one.  It is taken by
+ * cmf_mu_set_divergence only after cmf_set_option(h, "is_div", 1) (default 0; values other than 0 and 1: CMF_ERR_ARG; single-GPU
+ * handles only; cmf_option_names does not list it, like "kl_mask" above; turning it off while CMF_DIV_IS is installed:
+ * CMF_ERR_STATE).  With the option off every call answers as documented above, kind 2 with CMF_ERR_ARG.  With e as above,
+ * Q = 1 ./ e and P = (data .* Q) .* Q, the MU entries run
+ *   update_motifs!:        numW[:, :, l] = shift_cols(H, l) * P[:, 1+l:T]';  denomW[:, :, l] = shift_cols(H, l) * Q[:, 1+l:T]'
+ *                          (mult.jl:32-33 with data -> P, est -> Q);
+ *                          W .*= sqrt.(numW ./ (denomW + l1W + 2 l2W W + eps));  W = max(eps, W)
+ *   update_feature_maps!:  P, Q from the new W;  numH = tensor_transconv(W, P);  denomH = tensor_transconv(W, Q);  the same
+ *                          square-root update of H
+ * -- the exponent 1/2 is the majorisation-minimisation step for beta < 1 (Fevotte & Idier 2011): with l1 = l2 = 0 the loss does not
+ * increase.  LOSS: D / (N T), D = sum over entries of (r - 1) - log(r), r = data ./ e, with e from the new H: the mean divergence
+ * per entry, dimensionless, unchanged when data and the estimate are scaled together, 0 for a perfect fit, no square root.
+ * Data must be finite and STRICTLY positive (an exact zero has infinite divergence): checked in one pass when the divergence is
+ * installed, CMF_ERR_ARG with a text that starts "Itakura-Saito divergence needs" -- add a small floor to the spectrogram.
+ * Every option is honoured except "gram"; the few-component fusions are not taken, so results do not depend on "small_k_fuse",
+ * "speculate" or "reuse_est".  CMF_ERR_UNSUPPORTED on group handles, with the Gram forms and together with cmf_mu_set_mask (in
+ * either order: the form has no masked form); the HALS and PGD entries answer CMF_ERR_STATE while it is installed.  Switching
+ * between the three kinds on one handle voids est, the speculated contraction and a deferred loss each time. */
+#define CMF_DIV_IS 2
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
