@@ -21,7 +21,7 @@ LIB = os.path.join(HERE, "libcmf_hip.so")
 # rule + C ABI, the HALS / Gram / PGD rules, the T-sharded groups, the launchers of the few-component kernels, the fp64 ADMM and
 # ANLS rules, and the separable fit
 SOURCES = [os.path.join(CSRC, f) for f in ("cmf_api.hip", "cmf_rules.hip", "cmf_groups.hip", "cmf_small.hip", "cmf_admm.hip", "cmf_anls.hip", "cmf_sep.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("cmf_internal.h", "cmf_kernels.h", "cmf_small_k.h", "cmf_workers.h", "cmf_writeback.h", "cmf_rng.h",
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("cmf_internal.h", "cmf_kernels.h", "cmf_conv_modes.h", "cmf_small_k.h", "cmf_workers.h", "cmf_writeback.h", "cmf_rng.h",
                                                   "cmf_fp64.h", "cmf_admm.h", "cmf_anls.h", "cmf_nnls_large.h", "cmf_sep.h")] + [
     os.path.join(ROOT, "include", "cmf_hip.h")]
 

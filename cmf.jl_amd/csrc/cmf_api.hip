@@ -427,9 +427,7 @@ int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, i
 int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, int nsrc, float *slabs, int nchunks, int chunk_len,
                          int main_rows)
 {
-    const bool x0_data = X0 == mu_X(h);
-    ProfScope prof_(h, (nsrc == 2 && x0_data) ? PROF_HXT : (nsrc == 1 && x0_data) ? PROF_HXT_NUM : (nsrc == 1 && X0 == h->est && h->est_kind == mu_est_kind(h)) ? PROF_HXT_DEN
-                          : (nsrc == 1 && X0 == h->est) ? PROF_HXT_RESID : (X0 == h->hals_HX && h->hals_HX) ? PROF_HXT_HH : PROF_OTHER);
+    ProfScope prof_(h, hxt_prof_class(h, X0, nsrc));
     const CmfDims &d = h->d;
     h->spec_gen = -1; // (the slabs of a speculated contraction are being overwritten)
     HxtParams p;
@@ -450,11 +448,6 @@ int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, in
     h->launches[p.Tl < d.Tl ? LA_HXT_TAIL : LA_HXT_NO_TAIL] += 1;
     KCHK("hxt_kernel");
     return CMF_OK;
-}
-
-static int launch_hxt(cmf_handle_s *h)
-{
-    return launch_hxt_on(h, h->X, h->est, h->d.Np, 2, h->wslabs, h->hxt_nchunks, h->hxt_chunk_len, h->hxt_main);
 }
 
 int launch_transconv(cmf_handle_s *h, int nsrc, const float *xt0, bool front_block)
@@ -543,31 +536,70 @@ static int check_ready(cmf_handle_s *h, bool need_data)
     return CMF_OK;
 }
 
+// ---- the MU rule on a single handle: one path for every form, read from the form's row (mu_form, cmf_internal.h) ----
+// Nothing calls this.  It names the launchers in the order this file named them before mu_launch_conv, which is the order of the kernels in the
+// code object: the disassembly then compares as text against the predecessor's (tools/device_code_diff.py).  Deleting it reorders symbols, nothing else.
+[[maybe_unused]] static void conv_kernel_order()
+{
+    (void)&launch_conv<CONV_MUM_EST>, (void)&launch_conv<CONV_EST>, (void)&launch_conv<CONV_KL_R>, (void)&launch_conv<CONV_KL_R_T>, (void)&launch_conv<CONV_IS_PQ>;
+    (void)&launch_conv<CONV_IS_PQ_T>, (void)&launch_conv_rows<CONV_EST_T>, (void)&launch_conv<CONV_MUM_EST_T>, (void)&launch_conv<CONV_EST_T>;
+    (void)&launch_conv<CONV_IS_LOSS>, (void)&launch_conv<CONV_IS_LOSS_PQ>, (void)&launch_conv<CONV_KLM_LOSS>, (void)&launch_conv<CONV_KLM_LOSS_R>;
+    (void)&launch_conv<CONV_KL_LOSS>, (void)&launch_conv<CONV_KL_LOSS_R>, (void)&launch_conv<CONV_MUM_LOSS>, (void)&launch_conv<CONV_MUM_LOSS_EST>;
+    (void)&launch_conv<CONV_LOSS_EST>, (void)&launch_conv<CONV_LOSS>;
+}
+
+// A conv family and base known at run time reach launch_conv's template argument here: exactly the modes the MU rule launches.
+static int mu_launch_conv(cmf_handle_s *h, int family, int base, float *out, int T_store, int gy, const float *data)
+{
+    switch (conv_mode(family, base)) {
+#define CASE(M_) case M_: return launch_conv<M_>(h, out, T_store, gy, data);
+        CASE(CONV_EST) CASE(CONV_EST_T) CASE(CONV_LOSS) CASE(CONV_LOSS_EST)
+        CASE(CONV_MUM_EST) CASE(CONV_MUM_EST_T) CASE(CONV_MUM_LOSS) CASE(CONV_MUM_LOSS_EST)
+        CASE(CONV_KL_R) CASE(CONV_KL_R_T) CASE(CONV_KL_LOSS) CASE(CONV_KL_LOSS_R)
+        CASE(CONV_KLM_LOSS) CASE(CONV_KLM_LOSS_R)
+        CASE(CONV_IS_PQ) CASE(CONV_IS_PQ_T) CASE(CONV_IS_LOSS) CASE(CONV_IS_LOSS_PQ)
+#undef CASE
+    default: return fail(CMF_ERR_STATE, "internal: the MU rule launches no conv mode %d", conv_mode(family, base));
+    }
+}
+
+// the conv of the active form at one of the four bases, on the data operand the form gives that base
+static int mu_conv(cmf_handle_s *h, int base, float *out, int T_store, int gy)
+{
+    const MuForm &f = mu_form(h);
+    return mu_launch_conv(h, base >= CONV_BASE_LOSS ? f.loss_family : f.store_family, base, out, T_store, gy, mu_buf(h, f.conv_data[base]));
+}
+
+static bool mu_est_current(const cmf_handle_s *h) { return h->reuse_est && h->est_kind == mu_est_kind(h); }
+
 // The C2 contraction of update_motifs! has already been enqueued for exactly this state (w_speculate, behind the loss conv of the
 // update_feature_maps! before): est is current and nothing has touched H, W, est or the slabs since.
 static bool w_speculated(cmf_handle_s *h)
 {
-    const bool hit = h->spec_gen >= 0 && h->spec_gen == h->est_gen && h->reuse_est && h->est_kind == mu_est_kind(h) && !h->carry.partial;
+    const bool hit = mu_form(h).square_fusions && h->spec_gen >= 0 && h->spec_gen == h->est_gen && mu_est_current(h) && !h->carry.partial;
     h->spec_gen = -1;
     if (hit) h->spec_hits += 1;
     return hit;
 }
 
-// est = tensor_conv(W, H) in the [t][n] layout (mult.jl:28); under the MU rule's mask: mask .* est
-static int mu_conv_est(cmf_handle_s *h)
+// the C2 contraction of the form (mult.jl:31-34) -> [numW | denomW] in h->numden (+ a loss reduction deferred by cmf_iterate), or,
+// slabs_only (few components), the slabs alone: w_update_small_kernel sums them
+static int mu_contract_c2(cmf_handle_s *h, bool slabs_only)
 {
-    return h->mu_mask ? launch_conv<8>(h, h->est, h->d.Tl, h->conv_gy) : launch_conv<0>(h, h->est, h->d.Tl, h->conv_gy);
+    const MuForm &f = mu_form(h);
+    return hxt_contract(h, mu_buf(h, f.c2_src[0]), mu_buf(h, f.c2_src[1]), f.c2_nsrc, slabs_only ? nullptr : h->numden, !slabs_only, slabs_only);
 }
 
-int w_partial_impl(cmf_handle_s *h)
+// est of the form (mult.jl:28; skipped when est is still current) and its C2 contraction, unless w_speculate has enqueued it already
+static int mu_contract_w(cmf_handle_s *h, bool slabs_only)
 {
-    const CmfDims &d = h->d;
     if (w_speculated(h)) return CMF_OK;
-    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)))
-        CMFTRY(mu_conv_est(h)); // mult.jl:28 (skipped when est is still current)
+    if (!mu_est_current(h)) CMFTRY(mu_conv(h, CONV_BASE_STORE, h->est, h->d.Tl, h->conv_gy));
     set_est(h, mu_est_kind(h));
-    return hxt_contract(h, mu_X(h), h->est, 2, h->numden, true); // mult.jl:31-34
+    return mu_contract_c2(h, slabs_only);
 }
+
+int w_partial_impl(cmf_handle_s *h) { return mu_contract_w(h, false); }
 
 // The two halves of w_partial_impl as separate steps (same arithmetic, the sources contracted one at a time): the
 // numerator needs H only, so a sharded host can compute and all-reduce it while the loss conv and the denominator
@@ -577,126 +609,48 @@ int w_partial_half_impl(cmf_handle_s *h, int den)
     const CmfDims &d = h->d;
     const size_t LKN = (size_t)d.L * d.K32 * d.Np;
     if (den) {
-        if (!(h->reuse_est && h->est_kind == 1))
-            CMFTRY(launch_conv<0>(h, h->est, d.Tl, h->conv_gy)); // mult.jl:28 (skipped when est is still current)
-        set_est(h, 1);
+        if (!(h->reuse_est && h->est_kind == EST_CONV))
+            CMFTRY(launch_conv<CONV_EST>(h, h->est, d.Tl, h->conv_gy)); // mult.jl:28 (skipped when est is still current)
+        set_est(h, EST_CONV);
     }
     const float *src = den ? h->est : h->X;
     return hxt_contract(h, src, src, 1, h->numden + (den ? LKN : 0), den != 0); // mult.jl:31-34, one source
 }
 
+// The element-wise update of W (mult.jl:37-38; the square root of the quotient where the form says so).
 // den == NULL: denomW lies behind numW in h->numden (the layout of the [numW | denomW] all-reduce buffer)
-static int w_apply_impl_(cmf_handle_s *h, double l1W, double l2W, const float *tail_src, float *tail_dst, int tail_n, const float *den);
-int w_apply_impl(cmf_handle_s *h, double l1W, double l2W, const float *tail_src, float *tail_dst, int tail_n,
-                        const float *den)
-{
-    return w_apply_impl_(h, l1W, l2W, tail_src, tail_dst, tail_n, den);
-}
-
-// update_motifs! of the KL form (cmf_mu_set_divergence): R = data ./ (est + eps) where the squared-error rule forms est (kept from the
-// loss conv when est is reused), numW = the C2 contraction of R alone (mult.jl:32 with data -> R), denomW from the row sums of H, and
-// the element-wise update as it is (mult.jl:37-38).  One path for every K: the few-component fusions (the slab sum inside
-// w_update_small_kernel, the speculated contraction) are not taken.
-static int kl_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
+int w_apply_impl(cmf_handle_s *h, double l1W, double l2W, const float *tail_src, float *tail_dst, int tail_n, const float *den)
 {
     const CmfDims &d = h->d;
-    if (h->mu_mask) { // under a mask (option "kl_mask"): R = Xm ./ e, and the denominator is the same contraction on the mask itself
-        // (mode 12 with data = Xm stores 0 / (v + eps) = 0 at the held-out entries: the store-only form needs no masked mode)
-        if (!(h->reuse_est && h->est_kind == 8)) CMFTRY(launch_conv<12>(h, h->est, d.Tl, h->conv_gy, h->Xm));
-        set_est(h, 8);
-        CMFTRY(hxt_contract(h, h->est, h->M, 2, h->numden, true)); // [numW | denomW] (+ a loss reduction deferred by cmf_iterate)
-        return w_apply_impl(h, l1W, l2W, nullptr, nullptr, 0, nullptr);
-    }
-    if (!(h->reuse_est && h->est_kind == 7)) CMFTRY(launch_conv<12>(h, h->est, d.Tl, h->conv_gy));
-    set_est(h, 7);
-    CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden, true)); // (+ a loss reduction deferred by cmf_iterate)
-    float *den = h->numden + (size_t)d.L * d.K32 * d.Np;
-    hipLaunchKernelGGL(kl_hsum_kernel, dim3(d.K, KL_HCHUNKS), dim3(256), 0, h->stream, h->Ht, d.TP, d.PADL, d.Tl, h->kl_sums);
-    KCHK("kl_hsum_kernel");
-    hipLaunchKernelGGL(kl_den_w_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Ht, h->kl_sums, den, d.TP, d.PADL, d.Tl, d.K32, d.Np);
-    KCHK("kl_den_w_kernel");
-    return w_apply_impl(h, l1W, l2W, nullptr, nullptr, 0, den);
-}
-
-// update_feature_maps! of the KL form up to the loss: R' with the new W, numH = tensor_transconv(W, R) (one source), denomH from the
-// sums of W over n, and the element-wise update as it is (mult.jl:51-52).  The few-component fusion of the update into the C3 launch
-// (sk_can_fuse_h) is not taken.
-static int kl_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
-{
-    const CmfDims &d = h->d;
-    if (h->mu_mask) { // under a mask: R' from Xm' (mode 13 with data = XmT), then the two-source C3 on (mask', R') = [denomH | numH]
-        CMFTRY(launch_conv<13>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext, h->XmT));
-        CMFTRY(launch_transconv(h, 2, h->MT));
-        const size_t TKm = (size_t)d.Tl * d.K32;
-        hipLaunchKernelGGL(h_update_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs + TKm, 2 * TKm, h->tc_S,
-                           h->hslabs, 2 * TKm, h->tc_S, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52 (numerator second)
-        KCHK("h_update_kernel");
-        set_est(h, 0);
-        return wb_after_H(h);
-    }
-    CMFTRY(launch_conv<13>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext));
-    CMFTRY(launch_transconv(h, 1, h->estT));
-    hipLaunchKernelGGL(kl_wsum_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Wt, d.K32, d.Np, h->kl_sums);
-    KCHK("kl_wsum_kernel");
-    const size_t TK = (size_t)d.Tl * d.K32;
-    hipLaunchKernelGGL(kl_den_h_kernel, dim3((unsigned)((TK + 255) / 256)), dim3(256), 0, h->stream, h->kl_sums, h->kl_denH, d.Tl, d.K, d.K32, d.L);
-    KCHK("kl_den_h_kernel");
-    hipLaunchKernelGGL(h_update_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs, TK, h->tc_S1,
-                       h->kl_denH, (size_t)0, 1, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52
-    KCHK("h_update_kernel");
-    set_est(h, 0);
-    return wb_after_H(h);
-}
-
-// update_motifs! of the Itakura-Saito form: one conv stores P = (data ./ e) ./ e into est and Q = 1 ./ e into est2 (kept from the loss
-// conv when est is reused), the two-source C2 contraction on (P, Q) is [numW | denomW] (mult.jl:32-33 with data -> P, est -> Q), and the
-// element-wise update takes the square root of the quotient.  One path for every K, as under KL: the few-component fusions (the slab
-// sum inside w_update_small_kernel, the speculated contraction) are not taken.
-static int is_w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
-{
-    const CmfDims &d = h->d;
-    if (!(h->reuse_est && h->est_kind == 9)) CMFTRY(launch_conv<20>(h, h->est, d.Tl, h->conv_gy));
-    set_est(h, 9);
-    CMFTRY(hxt_contract(h, h->est, h->est2, 2, h->numden, true)); // [numW | denomW] (+ a loss reduction deferred by cmf_iterate)
-    hipLaunchKernelGGL(w_update_sqrt_kernel, dim3(d.Np / 64, d.KB, d.L), dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, h->numden + (size_t)d.L * d.K32 * d.Np,
-                       d.N, d.K, d.L, d.Np, d.K32, (float)l1W, (float)(2.0 * l2W), (const float *)nullptr, (float *)nullptr, 0);
-    KCHK("w_update_sqrt_kernel");
-    set_est(h, 0);
+    dim3 grid(d.Np / 64, d.KB, d.L);
+    if (!den) den = h->numden + (size_t)d.L * d.K32 * d.Np;
+    const bool root = mu_form(h).sqrt_update;
+    hipLaunchKernelGGL(root ? w_update_sqrt_kernel : w_update_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, den,
+                       d.N, d.K, d.L, d.Np, d.K32, (float)l1W, (float)(2.0 * l2W), tail_src, tail_dst, tail_n);
+    KCHK(root ? "w_update_sqrt_kernel" : "w_update_kernel");
+    set_est(h, EST_NONE);
     return CMF_OK;
 }
 
-// update_feature_maps! of the Itakura-Saito form up to the loss: P' and Q' with the new W from one conv, the two-source C3 on
-// (Q', P') = [denomH | numH], and the square-root update.  The few-component fusion of the update into the C3 launch is not taken.
-static int is_h_update_impl(cmf_handle_s *h, double l1H, double l2H)
-{
-    const CmfDims &d = h->d;
-    CMFTRY(launch_conv<21>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext));
-    CMFTRY(launch_transconv(h, 2, h->est2T));
-    const size_t TK = (size_t)d.Tl * d.K32;
-    hipLaunchKernelGGL(h_update_sqrt_kernel, dim3((d.Tl + HUPD_T - 1) / HUPD_T, d.KB), dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs + TK, 2 * TK, h->tc_S,
-                       h->hslabs, 2 * TK, h->tc_S, d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // (numerator second)
-    KCHK("h_update_sqrt_kernel");
-    set_est(h, 0);
-    return wb_after_H(h);
-}
-
-// update_motifs! of the MU rule on a single handle (mult.jl:23-39).  Few components: conv (unless est is current), the C2
-// kernel, and ONE launch that sums its slabs, updates W and packs the C3 operand (w_update_small_kernel).
+// update_motifs! of the MU rule on a single handle (mult.jl:23-39): est of the form unless it is current, the C2 contraction, the KL
+// denominators where the form takes them from sums, the element-wise update.  Few components under the squared error: the C2 kernel
+// and ONE launch that sums its slabs, updates W and packs the C3 operand (w_update_small_kernel).
 static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 {
     const CmfDims &d = h->d;
-    if (h->mu_div == CMF_DIV_IS) return is_w_phase_impl(h, l1W, l2W);
-    if (h->mu_div) return kl_w_phase_impl(h, l1W, l2W);
-    if (!h->small_k) {
+    const MuForm &f = mu_form(h);
+    if (!(h->small_k && f.square_fusions)) {
         CMFTRY(w_partial_impl(h));
+        if (f.kl_den()) { // KL: denomW[l][k] broadcast over n from the row sums of H, behind numW in h->numden
+            hipLaunchKernelGGL(kl_hsum_kernel, dim3(d.K, KL_HCHUNKS), dim3(256), 0, h->stream, h->Ht, d.TP, d.PADL, d.Tl, h->kl_sums);
+            KCHK("kl_hsum_kernel");
+            hipLaunchKernelGGL(kl_den_w_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Ht, h->kl_sums, h->numden + (size_t)d.L * d.K32 * d.Np, d.TP, d.PADL, d.Tl,
+                               d.K32, d.Np);
+            KCHK("kl_den_w_kernel");
+        }
         return w_apply_impl(h, l1W, l2W);
     }
-    if (!w_speculated(h)) {
-        if (!(h->reuse_est && h->est_kind == mu_est_kind(h)))
-            CMFTRY(mu_conv_est(h)); // mult.jl:28 (skipped when est is still current)
-        set_est(h, mu_est_kind(h));
-        CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, nullptr, false, true)); // mult.jl:31-34: the slabs only
-    }
+    CMFTRY(mu_contract_w(h, true));
     CmfLossCarry carry{};
     if (h->carry.partial) { // a loss reduction deferred by cmf_iterate rides on this launch
         carry = h->carry;
@@ -706,23 +660,27 @@ static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
                        h->sk_ngroups, d.N, d.K, d.L, d.Np, d.K32, h->sk_JP, h->sk3_Kg, h->sk3_GR, h->sk3_JP,
                        (float)l1W, (float)(2.0 * l2W), carry); // mult.jl:37-38
     KCHK("w_update_small_kernel");
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     h->sk_wj_gen = h->sk_tc ? h->est_gen : -1;
     return CMF_OK;
 }
 
-static int w_apply_impl_(cmf_handle_s *h, double l1W, double l2W, const float *tail_src, float *tail_dst, int tail_n, const float *den)
+// The element-wise update of H (mult.jl:51-52) on `rows` columns from padded row `padl` on: numerator and denominator are the sums of
+// n_num / n_den slabs `stride` apart (a stride of 0 with one slab: a finished table).  H is final behind it.
+static int launch_h_update(cmf_handle_s *h, bool sqrt_update, const float *num, size_t num_stride, int n_num, const float *den, size_t den_stride, int n_den,
+                           int rows, int padl, double l1H, double l2H)
 {
     const CmfDims &d = h->d;
-    dim3 grid(d.Np / 64, d.KB, d.L);
-    if (!den) den = h->numden + (size_t)d.L * d.K32 * d.Np;
-    hipLaunchKernelGGL(w_update_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, den,
-                       d.N, d.K, d.L, d.Np, d.K32, (float)l1W, (float)(2.0 * l2W), tail_src, tail_dst, tail_n); // mult.jl:37-38
-    KCHK("w_update_kernel");
-    set_est(h, 0);
-    return CMF_OK;
+    const dim3 grid((rows + HUPD_T - 1) / HUPD_T, d.KB);
+    hipLaunchKernelGGL(sqrt_update ? h_update_sqrt_kernel : h_update_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, num, num_stride, n_num, den, den_stride,
+                       n_den, rows, d.K, d.K32, padl, d.TP, (float)l1H, (float)(2.0 * l2H));
+    KCHK(sqrt_update ? "h_update_sqrt_kernel" : "h_update_kernel");
+    set_est(h, EST_NONE);
+    return wb_after_H(h);
 }
 
+// update_feature_maps! of the MU rule up to the loss (mult.jl:44-52): est' of the form with the new W, the C3 contraction, the KL
+// denominators where the form takes them from sums, the element-wise update.
 // front: a shard whose group carries the halo of H in the W-phase all-reduce (cmf_groups.hip) also updates the hx = L-1 columns in
 // FRONT of its own -- its left neighbour's last ones, which its loss conv and its next W phase read -- from an H that is valid 2 hx
 // columns out: one more conv tile row (columns [-64, 0)), one more transconv block ([-128, 0)), the element-wise update from -hx on.
@@ -734,71 +692,42 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         // mult.jl:44 on columns [-64, Tl + halo_r): ONE launch of the one-wave tiles from tile row -1 on (a launch of its own for the
         // row in front cost 10 us per shard and iteration: profiles/r06_halo_in_allreduce_cost.txt)
         int np = 0;
-        CMFTRY(launch_conv_rows<1>(h, h->estT, -1, 1 + (d.Tl + h->halo_r + 63) / 64, 0, h->n_cu, nullptr, nullptr, nullptr, &np, d.Tl + h->halo_r));
+        CMFTRY(launch_conv_rows<CONV_EST_T>(h, h->estT, -1, 1 + (d.Tl + h->halo_r + 63) / 64, 0, h->n_cu, nullptr, nullptr, nullptr, &np, d.Tl + h->halo_r));
         CMFTRY(launch_transconv(h, 2, nullptr, true));                    // mult.jl:47-48 on columns [-128, Tl)
         const int hx = h->halo_ext, R = d.Tl + 128;
-        dim3 gridx((d.Tl + hx + HUPD_T - 1) / HUPD_T, d.KB);
         const float *num = h->hslabs + (size_t)(128 - hx) * d.K32;        // slab row r holds column r - 128: the update starts at column -hx
-        hipLaunchKernelGGL(h_update_kernel, gridx, dim3(256), 0, h->stream, h->H, h->Ht, num, (size_t)2 * R * d.K32, h->tc_S2, num + (size_t)R * d.K32,
-                           (size_t)2 * R * d.K32, h->tc_S2, d.Tl + hx, d.K, d.K32, d.PADL - hx, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52
-        KCHK("h_update_kernel");
-        set_est(h, 0);
-        return wb_after_H(h);
+        return launch_h_update(h, false, num, (size_t)2 * R * d.K32, h->tc_S2, num + (size_t)R * d.K32, (size_t)2 * R * d.K32, h->tc_S2, d.Tl + hx, d.PADL - hx,
+                               l1H, l2H);
     }
-    if (h->mu_div == CMF_DIV_IS) return is_h_update_impl(h, l1H, l2H);
-    if (h->mu_div) return kl_h_update_impl(h, l1H, l2H);
-    if (h->mu_mask) CMFTRY(launch_conv<9>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // (mask .* est)' under the MU rule's mask
-    else CMFTRY(launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
-    if (sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
-        CMFTRY(launch_transconv_small(h, 2, mu_XT(h), true, (float)l1H, (float)(2.0 * l2H)));
+    const MuForm &f = mu_form(h);
+    CMFTRY(mu_conv(h, CONV_BASE_STORE_T, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
+    if (f.square_fusions && sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
+        CMFTRY(launch_transconv_small(h, 2, mu_buf(h, f.c3_first), true, (float)l1H, (float)(2.0 * l2H)));
         ++h->sk_fused_h;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return wb_after_H(h);
     }
-    CMFTRY(launch_transconv(h, 2, mu_XT(h)));                               // mult.jl:47-48
-    dim3 grid((d.Tl + HUPD_T - 1) / HUPD_T, d.KB);
-    const size_t TK = (size_t)d.Tl * d.K32;
-    hipLaunchKernelGGL(h_update_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, h->hslabs, 2 * TK, h->tc_S, h->hslabs + TK, 2 * TK, h->tc_S,
-                       d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52
-    KCHK("h_update_kernel");
-    set_est(h, 0);
-    return wb_after_H(h);
+    CMFTRY(launch_transconv(h, f.c3_nsrc, mu_buf(h, f.c3_first)));          // mult.jl:47-48
+    const size_t TK = (size_t)d.Tl * d.K32, stride = f.c3_nsrc * TK;
+    if (f.kl_den()) { // KL: denomH[k][t] from the sums of W over n
+        hipLaunchKernelGGL(kl_wsum_kernel, dim3(d.L, d.K), dim3(256), 0, h->stream, h->Wt, d.K32, d.Np, h->kl_sums);
+        KCHK("kl_wsum_kernel");
+        hipLaunchKernelGGL(kl_den_h_kernel, dim3((unsigned)((TK + 255) / 256)), dim3(256), 0, h->stream, h->kl_sums, h->kl_denH, d.Tl, d.K, d.K32, d.L);
+        KCHK("kl_den_h_kernel");
+    }
+    const int S = f.c3_nsrc == 2 ? h->tc_S : h->tc_S1;
+    if (f.kl_den()) return launch_h_update(h, f.sqrt_update, h->hslabs + f.h_num * TK, stride, S, h->kl_denH, (size_t)0, 1, d.Tl, d.PADL, l1H, l2H);
+    return launch_h_update(h, f.sqrt_update, h->hslabs + f.h_num * TK, stride, S, h->hslabs + f.h_den * TK, stride, S, d.Tl, d.PADL, l1H, l2H);
 }
 
-// the conv of mult.jl:55-57 with the loss fused: per-tile sums of (est - data)^2 -> h->partial
+// the conv of mult.jl:55-57 with the loss fused: per-tile sums of the form's loss terms -> h->partial; est of the form is kept for the
+// next update_motifs! when est is reused (the Gram form never reads est: nothing to keep)
 int launch_loss_conv(cmf_handle_s *h)
 {
-    const CmfDims &d = h->d;
-    if (h->mu_div == CMF_DIV_IS) { // the sum of the Itakura-Saito terms; P and Q kept for the next update_motifs! when est is reused
-        if (!h->reuse_est) return launch_conv<22>(h, nullptr, d.Tl, h->conv_gy);
-        CMFTRY(launch_conv<23>(h, h->est, d.Tl, h->conv_gy));
-        set_est(h, 9);
-        return CMF_OK;
-    }
-    if (h->mu_div && h->mu_mask) { // the divergence over the observed entries; R = Xm ./ (est + eps) kept when est is reused
-        if (!h->reuse_est) return launch_conv<18>(h, nullptr, d.Tl, h->conv_gy, h->Xm);
-        CMFTRY(launch_conv<19>(h, h->est, d.Tl, h->conv_gy, h->Xm));
-        set_est(h, 8);
-        return CMF_OK;
-    }
-    if (h->mu_div) { // the sum of the divergence terms; R = data ./ (est + eps) kept for the next update_motifs! when est is reused
-        if (!h->reuse_est) return launch_conv<14>(h, nullptr, d.Tl, h->conv_gy);
-        CMFTRY(launch_conv<15>(h, h->est, d.Tl, h->conv_gy));
-        set_est(h, 7);
-        return CMF_OK;
-    }
-    if (h->mu_mask) { // the sum of (mask .* (est - data))^2; mask .* est kept when est is reused
-        if (!h->reuse_est) return launch_conv<10>(h, nullptr, d.Tl, h->conv_gy);
-        CMFTRY(launch_conv<11>(h, h->est, d.Tl, h->conv_gy));
-        set_est(h, 6);
-        return CMF_OK;
-    }
-    if (h->reuse_est && !h->gram) { // (the Gram form never reads est: nothing to keep)
-        CMFTRY(launch_conv<3>(h, h->est, d.Tl, h->conv_gy)); // est kept for the next update_motifs!
-        set_est(h, 1);
-        return CMF_OK;
-    }
-    return launch_conv<2>(h, nullptr, d.Tl, h->conv_gy);
+    if (!(h->reuse_est && !h->gram)) return mu_conv(h, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy);
+    CMFTRY(mu_conv(h, CONV_BASE_LOSS_STORE, h->est, h->d.Tl, h->conv_gy));
+    set_est(h, mu_est_kind(h));
+    return CMF_OK;
 }
 
 // Behind the loss conv of update_feature_maps! (est is current, H final): enqueue the C2 contraction the NEXT update_motifs! starts
@@ -808,9 +737,8 @@ int launch_loss_conv(cmf_handle_s *h)
 // (the call before this one was update_motifs!); a caller that stops pays one contraction nobody reads.
 static int w_speculate(cmf_handle_s *h)
 {
-    if (!(h->reuse_est && h->est_kind == mu_est_kind(h)) || h->gram || h->group || h->carry.partial || h->mu_div) return CMF_OK;
-    if (h->small_k) CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, nullptr, false, true));
-    else CMFTRY(hxt_contract(h, mu_X(h), h->est, 2, h->numden, true));
+    if (!mu_est_current(h) || h->gram || h->group || h->carry.partial || !mu_form(h).square_fusions) return CMF_OK;
+    CMFTRY(mu_contract_c2(h, h->small_k));
     h->spec_gen = h->est_gen;
     return CMF_OK;
 }
@@ -820,7 +748,6 @@ static int ensure_ring(cmf_handle_s *h) // pinned words a loss reduction stores 
     if (!h->h_ring) HIPCHK(hipHostMalloc(&h->h_ring, 3 * sizeof(double), hipHostMallocCoherent));
     return CMF_OK;
 }
-
 
 // The loss conv (mult.jl:55-57) and the reduction of its per-tile sums.  readback: the calling thread returns with the sum -- the
 // reduction stores it into a pinned word that the host polls (no copy operation and no stream synchronisation behind the last
@@ -871,7 +798,7 @@ int set_factors_impl(cmf_handle_s *h, const double *W, const double *H)
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     h->factors_set = true;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     return CMF_OK;
 }
 
@@ -1453,7 +1380,7 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
                 if (value && i < g->red.size() && g->red[i])
                     HIPCHK(hipMemsetAsync(g->red[i] + g->LKN2 / 2, 0, (size_t)g->HHsz * sizeof(float), s->stream));
                 s->gram = value;
-                set_est(s, 0);
+                set_est(s, EST_NONE);
                 s->carry = CmfLossCarry{};
             }
             g->gram = value;
@@ -1481,18 +1408,18 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
                                                                   "which is not a product of Gram matrices): clear the mask of cmf_mu_set_mask first");
         h->gram = value;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "conv_kernel") == 0) { // K % 32 == 0 only: 0 = chosen per mode (default), 3 = one-wave workgroups, 2 = 128 x 128 tiles
         if (value != 0 && value != 2 && value != 3) return fail(CMF_ERR_ARG, "conv_kernel must be 0 (per mode), 2 or 3");
         h->conv_variant = value;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "hals_gram") == 0) { // HALS projections as differences of the MU quantities: 2 (default) = H phase, 1 = both phases, 0 = neither
         h->hals_gram = (value == 1 || value == 2) ? value : 0; // 2 = the H phase only
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "hals_persist") == 0 || std::strcmp(name, "hals_general") == 0 || std::strcmp(name, "hals_seg") == 0 ||
@@ -1525,7 +1452,7 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
     }
     if (std::strcmp(name, "conv_split") == 0) { // 0 = never cut the one-wave conv kernel's last round into quarter tiles
         h->conv_split = value;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "small_k_fuse") == 0) { // few components: 1 (default) = the element-wise update of H inside the C3 launch, 0 = a launch of its own
@@ -1541,12 +1468,12 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         h->sk_tc = h->small_k && (h->sk_tc_ok || value == 2); // (2: the few-component C3 form whatever T is -- tests, measurements)
         h->tc_S = h->sk_tc ? 2 * h->sk3_NS : h->tc_S_full; // (own block | the spill of the next block, per piece of the reduction: g_gemm_fold_small_kernel)
         h->tc_S1 = h->sk_tc ? 2 * h->sk3_NS : h->tc_S1_full;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "reuse_est") == 0) {
         h->reuse_est = value != 0;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     if (std::strcmp(name, "speculate") == 0) { // 1 (default): update_feature_maps! enqueues the next update_motifs!'s contraction behind its loss conv when the caller alternates the two calls
@@ -1751,9 +1678,9 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
         // out behind the loss reduction, so that the device works while the loss travels and the caller's loop comes round
         if (speculate && attempt == 0 && h->hals_gram != 1) h->after_reduce = [h]() { return hals_w_speculate(h); };
         if (h->hals_gram == 1) { // hals.jl:41: norm(resids)/data_norm -- the conv with the loss fused in its epilogue, nothing stored
-            CMFTRY(launch_conv<2>(h, nullptr, h->d.Tl, h->conv_gy));
+            CMFTRY(launch_conv<CONV_LOSS>(h, nullptr, h->d.Tl, h->conv_gy));
             CMFTRY(reduce_partials(h, h->partial, h->conv_partials, 0, &ss));
-            set_est(h, 0);
+            set_est(h, EST_NONE);
         } else {
             CMFTRY(hals_resid_and_loss(h, &ss)); // ... and the residual kept for the next W phase (part of it may have chased the sweep)
         }
@@ -1772,27 +1699,48 @@ int cmf_hals_update_feature_maps(cmf_handle h, double l1H, double l2H, double *l
     return wb_finish(h, hals_update_feature_maps_body(h, l1H, l2H, loss));
 }
 
-// What the KL form asks of the data it reads (X, or Xm under a mask): finite and non-negative with a positive sum.  One pass over the
-// flat padded array (its padding is zero); *sum is what the divergence is divided by.
-static int kl_check_data(cmf_handle_s *h, const float *X, double *sum_out)
+// A reduction over the flat padded [TP][Np] array (its padding is zero) into h->partial, read back: `launch(nb, n4)` starts nb
+// workgroups over n4 float4s that leave nsums sums each as [nsums][nb] doubles; sums[j] is their total.  Synchronises the stream.
+template <typename Launch>
+static int flat_reduce(cmf_handle_s *h, const char *name, int nsums, double *sums, Launch launch)
 {
-    const CmfDims &d = h->d;
-    const size_t n4 = (size_t)d.TP * d.Np / 4;
-    const int nb = (int)std::min<size_t>(n_partial(h) / 2, std::min<size_t>(1024, (n4 + 255) / 256));
+    const size_t n4 = (size_t)h->d.TP * h->d.Np / 4;
+    const int nb = (int)std::min<size_t>(n_partial(h) / nsums, std::min<size_t>(1024, (n4 + 255) / 256));
     if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
-    hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, X, n4, h->partial);
-    KCHK("kl_data_check_kernel");
-    std::vector<double> part((size_t)2 * nb);
+    launch(nb, n4);
+    KCHK(name);
+    std::vector<double> part((size_t)nsums * nb);
     HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    double sum = 0.0, bad = 0.0;
-    for (int b = 0; b < nb; ++b) {
-        sum += part[(size_t)b];
-        bad += part[(size_t)nb + b];
+    for (int j = 0; j < nsums; ++j) {
+        sums[j] = 0.0;
+        for (int b = 0; b < nb; ++b) sums[j] += part[(size_t)j * nb + b];
     }
-    if (bad > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", bad);
-    if (!(sum > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
-    *sum_out = sum;
+    return CMF_OK;
+}
+
+// What the KL form asks of the data it reads (X, or Xm under a mask): finite and non-negative with a positive sum.  One pass;
+// *sum_out is what the divergence is divided by.
+static int kl_check_data(cmf_handle_s *h, const float *X, double *sum_out)
+{
+    double sb[2]; // sum | bad entries
+    CMFTRY(flat_reduce(h, "kl_data_check_kernel", 2, sb, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, X, n4, h->partial);
+    }));
+    if (sb[1] > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", sb[1]);
+    if (!(sb[0] > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
+    *sum_out = sb[0];
+    return CMF_OK;
+}
+
+// the tables of the KL denominators go when the KL form is left (towards either other divergence)
+static int kl_free_tables(cmf_handle_s *h)
+{
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->kl_denH) (void)hipFree(h->kl_denH);
+    if (h->kl_sums) (void)hipFree(h->kl_sums);
+    h->kl_denH = nullptr;
+    h->kl_sums = nullptr;
     return CMF_OK;
 }
 
@@ -1808,7 +1756,7 @@ static int mu_mask_off(cmf_handle_s *h)
     }
     drop_carry(h);
     h->spec_gen = -1;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     if (!h->mu_mask && !h->Xm && !h->XmT) return CMF_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->Xm) (void)hipFree(h->Xm);
@@ -1822,19 +1770,10 @@ static int mu_mask_off(cmf_handle_s *h)
 // sum over the flat [TP][Np] array of select(mask, data, 0)^2 (comp: mask == 0), optionally writing the masked copies (mask_select_kernel)
 static int mask_select(cmf_handle_s *h, bool write, int comp, double *sumsq)
 {
-    const CmfDims &d = h->d;
-    const size_t n4 = (size_t)d.TP * d.Np / 4;
-    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
-    hipLaunchKernelGGL(mask_select_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, write ? h->Xm : nullptr, write ? h->XT : nullptr,
-                       write ? h->MT : nullptr, write ? h->XmT : nullptr, n4, comp, h->partial);
-    KCHK("mask_select_kernel");
-    std::vector<double> part((size_t)nb);
-    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    double s = 0.0;
-    for (double v : part) s += v;
-    *sumsq = s;
-    return CMF_OK;
+    return flat_reduce(h, "mask_select_kernel", 1, sumsq, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(mask_select_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, write ? h->Xm : nullptr, write ? h->XT : nullptr,
+                           write ? h->MT : nullptr, write ? h->XmT : nullptr, n4, comp, h->partial);
+    });
 }
 
 // the mask and the masked copies of data, into whichever of h->M, h->MT is not there yet and into fresh h->Xm, h->XmT
@@ -1850,7 +1789,7 @@ static int mu_install_mask(cmf_handle_s *h, const double *mask)
     CMFTRY(mask_select(h, true, 0, &h->xm_sumsq));
     h->xm_norm = std::sqrt(h->xm_sumsq);
     h->mu_mask = true;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     return CMF_OK;
 }
 
@@ -1861,7 +1800,7 @@ static int kl_install_mask(cmf_handle_s *h, const double *mask)
 {
     drop_carry(h);
     h->spec_gen = -1;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     HIPCHK(hipStreamSynchronize(h->stream));
     float *const old[4] = {h->M, h->MT, h->Xm, h->XmT};
     const bool old_on = h->mu_mask;
@@ -1924,16 +1863,10 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
 static int is_check_data(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
-    const size_t n4 = (size_t)d.TP * d.Np / 4;
-    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
-    if (nb < 1) return fail(CMF_ERR_STATE, "internal: no loss partials");
-    hipLaunchKernelGGL(is_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, d.Np, d.N, d.PADL, d.Tl, h->partial);
-    KCHK("is_data_check_kernel");
-    std::vector<double> part((size_t)nb);
-    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     double bad = 0.0;
-    for (double v : part) bad += v;
+    CMFTRY(flat_reduce(h, "is_data_check_kernel", 1, &bad, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(is_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, d.Np, d.N, d.PADL, d.Tl, h->partial);
+    }));
     if (bad > 0.0)
         return fail(CMF_ERR_ARG, "Itakura-Saito divergence needs finite, strictly positive data (%.0f entries are zero, negative, NaN or infinite): "
                                  "add a small floor to the spectrogram, e.g. data + 1e-6 * max(data)", bad);
@@ -1950,13 +1883,7 @@ static int is_install(cmf_handle_s *h)
     const CmfDims &d = h->d;
     if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
     if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
-    if (h->mu_div == CMF_DIV_KL) { // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->kl_denH) (void)hipFree(h->kl_denH);
-        if (h->kl_sums) (void)hipFree(h->kl_sums);
-        h->kl_denH = nullptr;
-        h->kl_sums = nullptr;
-    }
+    if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
     h->data_sum = (double)d.N * (double)d.Tl;
     h->mu_div = CMF_DIV_IS;
     return CMF_OK;
@@ -1975,13 +1902,9 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
     if (h->wb && h->wb->armed) wb_disarm(h);
     drop_carry(h);
     h->spec_gen = -1;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     if (kind == CMF_DIV_SQUARE) { // today's rule again, launch for launch
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->kl_denH) (void)hipFree(h->kl_denH);
-        if (h->kl_sums) (void)hipFree(h->kl_sums);
-        h->kl_denH = nullptr;
-        h->kl_sums = nullptr;
+        CMFTRY(kl_free_tables(h));
         h->mu_div = CMF_DIV_SQUARE;
         return CMF_OK;
     }
@@ -2012,26 +1935,18 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
     // One loss-only conv (nothing stored: est, the factors and the rule's state stay as they are) on the raw data with the mask as a
     // select, then the same select on data^2.  Both use the loss partials, one after the other on the stream.
     // Under the KL form with its mask (option "kl_mask") the pair is (sum of the divergence terms, sum of data) over the selected entries.
-    const bool kl = h->mu_div && h->mu_mask;
+    const MuForm &f = mu_form(h);
     h->mask_complement_now = comp ? 1 : 0;
-    const int rc = kl ? launch_conv<18>(h, nullptr, h->d.Tl, h->conv_gy) : launch_conv<10>(h, nullptr, h->d.Tl, h->conv_gy);
+    const int rc = mu_launch_conv(h, f.held_out_family, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy, nullptr);
     h->mask_complement_now = 0;
     CMFTRY(rc);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, h->conv_partials, h->d_scalar + 1, (double *)nullptr);
     KCHK("loss_reduce_kernel");
     CMFTRY(read_scalar(h, 1, resid_sumsq));
-    if (!kl) return mask_select(h, false, comp ? 1 : 0, data_sumsq);
-    const size_t n4 = (size_t)h->d.TP * h->d.Np / 4;
-    const int nb = (int)std::min<size_t>(n_partial(h), std::min<size_t>(1024, (n4 + 255) / 256));
-    hipLaunchKernelGGL(kl_masked_sum_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, n4, comp ? 1 : 0, h->partial);
-    KCHK("kl_masked_sum_kernel");
-    std::vector<double> part((size_t)nb);
-    HIPCHK(hipMemcpyAsync(part.data(), h->partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    double s = 0.0;
-    for (double v : part) s += v;
-    *data_sumsq = s;
-    return CMF_OK;
+    if (f.held_out_family != CONV_FAM_KL_MASKED) return mask_select(h, false, comp ? 1 : 0, data_sumsq);
+    return flat_reduce(h, "kl_masked_sum_kernel", 1, data_sumsq, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(kl_masked_sum_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, n4, comp ? 1 : 0, h->partial);
+    });
 }
 
 int cmf_set_mask(cmf_handle h, const double *mask)
@@ -2041,7 +1956,7 @@ int cmf_set_mask(cmf_handle h, const double *mask)
     HIPCHK(hipSetDevice(h->device));
     if (h->sharded) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
     const CmfDims &d = h->d;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     CMFTRY(mu_mask_off(h)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
     if (!mask) { // back to the plain SquareLoss
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -2069,9 +1984,9 @@ int cmf_pgd_set_loss(cmf_handle h, int loss_kind)
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
     if (loss_kind != 0 && loss_kind != 1) return fail(CMF_ERR_ARG, "loss_kind must be 0 (SquareLoss) or 1 (AbsoluteLoss)");
     if (h->pgd_loss_abs != loss_kind) {
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         if (h->group)
-            for (cmf_handle_s *s : h->group->sh) set_est(s, 0);
+            for (cmf_handle_s *s : h->group->sh) set_est(s, EST_NONE);
     }
     h->pgd_loss_abs = loss_kind;
     return CMF_OK;
@@ -2293,7 +2208,7 @@ int cmf_tensor_conv(int device, int64_t N, int64_t T, int64_t K, int64_t L, cons
         cmf_handle h = nullptr;
         CMFTRY(create_impl(&h, device, N, Tb, K, L, nullptr, 0, Tb, false));
         int rc = set_factors_impl(h, W, H + (size_t)(t0 - skip) * K);
-        if (rc == CMF_OK) rc = launch_conv<0>(h, h->est, h->d.Tl, h->conv_gy);
+        if (rc == CMF_OK) rc = launch_conv<CONV_EST>(h, h->est, h->d.Tl, h->conv_gy);
         if (rc == CMF_OK) rc = download_rows(h, est + (size_t)t0 * N, h->est, h->d.PADL + (int)skip, t1 - t0, (int)N, h->d.Np);
         destroy_impl(h);
         CMFTRY(rc);
@@ -2405,7 +2320,7 @@ int cmf_init_rand(int device, int64_t N, int64_t T, int64_t K, int64_t L, uint64
         double *part = nullptr;
         double dot_b = 0.0, nn_b = 0.0;
         int rc = set_factors_impl(hh, W, H + (size_t)(t0 - skip) * K);
-        if (rc == CMF_OK) rc = launch_conv<0>(hh, hh->est, d.Tl, hh->conv_gy);
+        if (rc == CMF_OK) rc = launch_conv<CONV_EST>(hh, hh->est, d.Tl, hh->conv_gy);
         if (rc == CMF_OK && hipMalloc(&part, (size_t)2 * nb * sizeof(double)) != hipSuccess) rc = fail(CMF_ERR_HIP, "hipMalloc failed in cmf_init_rand");
         if (rc == CMF_OK) {
             const size_t off = (size_t)(d.PADL + skip) * d.Np, n4 = (size_t)(d.Tl - skip) * d.Np / 4; // the block's own rows, all columns
@@ -2563,7 +2478,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
                 HIPCHK(hipEventRecord(fork, keep));
                 HIPCHK(hipStreamWaitEvent(aux, fork, 0));
             }
-            CMFTRY(first ? launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext) : launch_conv<3>(h, h->est, d.Tl, h->conv_gy));
+            CMFTRY(first ? launch_conv<CONV_EST_T>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext) : launch_conv<CONV_LOSS_EST>(h, h->est, d.Tl, h->conv_gy));
             h->stream = pair ? aux : keep;
             int rc = first ? launch_transconv(h, 1, h->XT)
                            : h->small_k ? hxt_contract(h, h->X, h->X, 1, h->numden) // (few components: kernel + its slab sum)
@@ -2591,7 +2506,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
         (void)hipStreamDestroy(aux);
         (void)hipEventDestroy(fork);
         (void)hipEventDestroy(join);
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return rc;
     }
     if (nm.rfind("hals_overlap", 0) == 0) {
@@ -2618,7 +2533,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
         auto once = [&]() -> int {
             if (ra == 0) {
                 CMFTRY(hals_persist_launch(h, q));
-                return launch_conv<4>(h, h->est, d.Tl, h->conv_gy);
+                return launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy);
             }
             HIPCHK(hipEventRecord(fork, keep));
             HIPCHK(hipStreamWaitEvent(sb, fork, 0));
@@ -2626,13 +2541,13 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
             h->stream = mode == 0 ? sa : keep;
             int rc = hals_persist_launch(h, q);
             h->stream = sb;
-            if (rc == CMF_OK) rc = launch_conv<4>(h, h->est, std::min(d.Tl, ra * 64), h->conv_gy);
+            if (rc == CMF_OK) rc = launch_conv<CONV_RESID>(h, h->est, std::min(d.Tl, ra * 64), h->conv_gy);
             h->stream = keep;
             CMFTRY(rc);
             if (mode == 0) { HIPCHK(hipEventRecord(ja, sa)); HIPCHK(hipStreamWaitEvent(keep, ja, 0)); }
             HIPCHK(hipEventRecord(jb, sb));
             HIPCHK(hipStreamWaitEvent(keep, jb, 0));
-            if (ra < rows_t) CMFTRY(launch_conv<4>(h, h->est, d.Tl - ra * 64, h->conv_gy));
+            if (ra < rows_t) CMFTRY(launch_conv<CONV_RESID>(h, h->est, d.Tl - ra * 64, h->conv_gy));
             return CMF_OK;
         };
         int rc = once();
@@ -2655,7 +2570,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
         (void)hipEventDestroy(ja);
         (void)hipEventDestroy(jb);
         if (h->hals_status) *h->hals_status = 0;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return rc;
     }
     int which = nm == "conv" ? 0 : nm == "hxt" ? 1 : nm == "transconv" ? 2 : nm == "conv_t" ? 3 : nm == "conv_loss" ? 4
@@ -2663,12 +2578,13 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
     if (which < 0) return fail(CMF_ERR_ARG, "unknown kernel '%s'", name);
     auto run = [&]() -> int {
         switch (which) {
-        case 0: return launch_conv<0>(h, h->est, d.Tl, h->conv_gy);
-        case 1: return h->small_k ? hxt_contract(h, h->X, h->est, 2, h->numden) : launch_hxt(h); // (few components: kernel + its slab sum)
+        case 0: return launch_conv<CONV_EST>(h, h->est, d.Tl, h->conv_gy);
+        case 1: return h->small_k ? hxt_contract(h, h->X, h->est, 2, h->numden) // (few components: kernel + its slab sum)
+                                : launch_hxt_on(h, h->X, h->est, d.Np, 2, h->wslabs, h->hxt_nchunks, h->hxt_chunk_len, h->hxt_main);
         case 2: return launch_transconv(h, 2);
-        case 3: return launch_conv<1>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext);
-        case 4: return launch_conv<2>(h, nullptr, d.Tl, h->conv_gy);
-        default: return launch_conv<3>(h, h->est, d.Tl, h->conv_gy);
+        case 3: return launch_conv<CONV_EST_T>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext);
+        case 4: return launch_conv<CONV_LOSS>(h, nullptr, d.Tl, h->conv_gy);
+        default: return launch_conv<CONV_LOSS_EST>(h, h->est, d.Tl, h->conv_gy);
         }
     };
     CMFTRY(run()); // warm-up
@@ -2679,7 +2595,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *avg_ms = (double)ms / reps;
-    if (which == 0 || which == 5) set_est(h, 1); // est now holds plain tensor_conv(W, H), whatever it held before (a residual on HALS / PGD handles)
+    if (which == 0 || which == 5) set_est(h, EST_CONV); // est now holds plain tensor_conv(W, H), whatever it held before (a residual on HALS / PGD handles)
     *flops = (which == 1 || which == 2) ? 2.0 * f1 : f1;
     return CMF_OK;
 }

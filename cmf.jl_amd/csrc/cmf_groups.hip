@@ -1248,7 +1248,7 @@ static int comm_attach(cmf_handle_s *h, int nranks, int rank, int transport, con
         g->halos_current = false;
         g->halos_pending = false;
         g->halo_wide = false;
-        set_est(h, 0);
+        set_est(h, EST_NONE);
     }
     return CMF_OK;
 }
@@ -1408,7 +1408,7 @@ int group_pgd_w(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs,
                            d.N, d.K, d.Np, d.K32, (float)st->pgd_stepW, nonneg == 1);                    // pgd.jl:237-241
         KCHK("pgd_w_apply_kernel");
         if (nonneg == 2) CMFTRY(pgd_unit_norm(s, true));                                                 // pgd.jl:100-110 (W is replicated)
-        set_est(s, 0);
+        set_est(s, EST_NONE);
     }
     return group_pgd_finish(st, g, &st->pgd_stepW);
 }
@@ -1425,7 +1425,7 @@ int group_pgd_h(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs,
         CMFTRY(group_use(s));
         if (!s->pgd_gradH) CMFTRY(dalloc_zero(&s->pgd_gradH, (size_t)d.Tl * d.K32));
         // the transposed residual on the shard's columns AND its right lag halo (transconv reads est[:, t .. t+L-1])
-        if (s->est_kind == 2 + (s->M ? 1 : 0) + (st->pgd_loss_abs ? 2 : 0)) {
+        if (s->est_kind == pgd_est_kind(s->M != nullptr, st->pgd_loss_abs != 0)) {
             // the shard's own columns are in est already (the conv that closed the W phase): transposed, not convolved again;
             // the <= L-1 halo columns are formed directly (resid_halo_kernel)
             hipLaunchKernelGGL(transpose_rows_kernel, dim3(d.Np / 64, (d.Tl + 63) / 64), dim3(256), 0, s->stream, s->est, s->estT, d.Tl, d.Np, d.TP, d.PADL);
@@ -1437,8 +1437,8 @@ int group_pgd_h(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs,
             }
         } else {
             s->pgd_loss_abs_now = st->pgd_loss_abs;
-            int rc_conv = s->MT ? launch_conv<7>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT)
-                                : launch_conv<5>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT);
+            int rc_conv = s->MT ? launch_conv<CONV_MASKED_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT)
+                                : launch_conv<CONV_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT);
             s->pgd_loss_abs_now = 0;
             CMFTRY(rc_conv);
         }
@@ -1468,7 +1468,7 @@ int group_pgd_h(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs,
             KCHK("pgd_h_knorm_kernel");
             kn.push_back(s->pgd_knorm);
         }
-        set_est(s, 0);
+        set_est(s, EST_NONE);
     }
     if (nonneg == 2) {
         CMFTRY(group_sum_doubles(g, kn, g->sh[0]->d.K));
@@ -1498,7 +1498,7 @@ int group_set_mask(cmf_group_s *g, const double *mask)
         cmf_handle_s *s = g->sh[i];
         const CmfDims &d = s->d;
         CMFTRY(group_use(s));
-        set_est(s, 0);
+        set_est(s, EST_NONE);
         if (!mask) {
             if (s->M) (void)hipFree(s->M);
             if (s->MT) (void)hipFree(s->MT);

@@ -165,6 +165,23 @@ static const char *const kLaunchNames[] = {
     "halo_pack2_kernel", "halo_unpack2_kernel", "halo_pack3_kernel", "halo_unpack3_kernel"};
 static_assert(sizeof(kLaunchNames) / sizeof(kLaunchNames[0]) == LA_NCLS, "one name per launch path");
 
+// What est / estT hold for the resident W, H (cmf_handle_s::est_kind): a reader recomputes on a mismatch, every writer passes through set_est.
+enum EstKind : int {
+    EST_NONE = 0,            // nothing
+    EST_CONV = 1,            // tensor_conv(W,H)
+    EST_RESID = 2,           // tensor_conv(W,H) - data
+    EST_RESID_MASKED = 3,    // mask .* (tensor_conv(W,H) - data)
+    EST_SIGN = 4,            // sign(tensor_conv(W,H) - data)  (the AbsoluteLoss gradient)
+    EST_SIGN_MASKED = 5,     // mask .* sign(...)
+    EST_MU_MASKED = 6,       // mask .* tensor_conv(W,H)  (the MU rule under a mask)
+    EST_KL_R = 7,            // data ./ (tensor_conv(W,H) + eps)  (the KL form of the MU rule)
+    EST_KL_R_MASKED = 8,     // Xm ./ (tensor_conv(W,H) + eps)  (R of the KL form under a mask: exactly 0 where the mask is 0)
+    EST_IS_PQ = 9            // P of the Itakura-Saito form (and est2 holds Q)
+};
+// the residual the PGD rule keeps (resid_and_loss): masked by MaskedLoss, its sign under AbsoluteLoss
+static inline int pgd_est_kind(bool masked, bool loss_abs) { return EST_RESID + (masked ? 1 : 0) + (loss_abs ? 2 : 0); }
+static_assert(EST_RESID_MASKED == EST_RESID + 1 && EST_SIGN == EST_RESID + 2 && EST_SIGN_MASKED == EST_RESID + 3, "pgd_est_kind");
+
 struct cmf_handle_s {
     int device = 0;
     CmfDims d{};
@@ -265,23 +282,18 @@ struct cmf_handle_s {
     int pgd_loss_abs = 0;      // 0 SquareLoss (pgd.jl:29-36), 1 AbsoluteLoss (pgd.jl:41-47)
     double *pgd_knorm = nullptr; // [K32] per-component sums of squares of UnitNormConstraint (pgd.jl:100-110)
     float *M = nullptr, *MT = nullptr; // mask of MaskedLoss (pgd.jl:58-70) in the layouts of X and XT; null = no mask
-    // the MU rule under that mask (cmf_mu_set_mask): M / MT hold 0 and 1, Xm / XmT = select(mask, data, 0) in the layouts of X and XT,
-    // and the MU entries contract Xm and mask .* est (est_kind 6) where they contract data and est; cmf_set_mask switches it off again
+    // the forms of the MU rule (kMuForms below says what each contracts).  Under a mask of cmf_mu_set_mask: M / MT hold 0 and 1,
+    // Xm / XmT = select(mask, data, 0) in the layouts of X and XT; cmf_set_mask switches it off again
     bool mu_mask = false;
     float *Xm = nullptr, *XmT = nullptr;
     double xm_sumsq = 0.0, xm_norm = 0.0; // sum of Xm^2 and its root: what the masked MU loss is divided by
-    // the KL form of the MU rule (cmf_mu_set_divergence): est / estT hold R = data ./ (est + eps) (est_kind 7) where the squared-error
-    // rule keeps est, the contractions run on that one source, and the denominators come from two small tables (kl_den_w / kl_den_h)
-    int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL
-    double data_sum = 0.0;       // sum(data): what the divergence is divided by (under a mask: sum(Xm))
+    int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL / CMF_DIV_IS (cmf_mu_set_divergence)
+    double data_sum = 0.0;       // what the divergence is divided by: sum(data) (under a mask: sum(Xm)); Itakura-Saito: N * Tl, the mean per entry
     int kl_mask = 0;             // cmf_set_option "kl_mask": 1 lets the KL form and a mask of cmf_mu_set_mask be installed together
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
     double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
-    // the Itakura-Saito form (option "is_div", then cmf_mu_set_divergence(CMF_DIV_IS)): est / estT hold P = (data ./ e) ./ e and the second
-    // pair est2 / est2T holds Q = 1 ./ e, e = tensor_conv(W,H) + eps (est_kind 9); both contractions run on the pair (P, Q) in their
-    // two-source forms.  data_sum is then N * Tl: the loss is the mean divergence per entry.
     int is_div = 0;              // cmf_set_option "is_div": 1 lets cmf_mu_set_divergence take CMF_DIV_IS
-    float *est2 = nullptr, *est2T = nullptr; // [TP][Np] / [Np][TP], zero-filled; allocated when the form is first installed, kept until the handle goes
+    float *est2 = nullptr, *est2T = nullptr; // Q = 1 ./ e of the Itakura-Saito form beside P in est / estT: [TP][Np] / [Np][TP], zero-filled; allocated when the form is first installed, kept until the handle goes
 
     double data_sumsq = 0.0, data_norm = 0.0;
     bool factors_set = false;
@@ -298,10 +310,7 @@ struct cmf_handle_s {
     unsigned prof_mask = 0; // option "profile_mask"
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
-    int est_kind = 0;       // what est[t][n] holds for the resident W, H: 0 nothing, 1 tensor_conv(W,H), 2 tensor_conv(W,H) - data, 3 mask .* (tensor_conv(W,H) - data),
-                            // 4 sign(tensor_conv(W,H) - data), 5 mask .* sign(...)  (the AbsoluteLoss gradient), 6 mask .* tensor_conv(W,H) (the MU rule
-                            // under a mask: mu_est_kind), 7 data ./ (tensor_conv(W,H) + eps) (the KL form of the MU rule), 8 Xm ./ (tensor_conv(W,H) + eps)
-                            // (R of the KL form under a mask: exactly 0 where the mask is 0), 9 P of the Itakura-Saito form (and est2 holds Q)
+    int est_kind = EST_NONE; // what est[t][n] holds for the resident W, H (EstKind)
     void *arena = nullptr;  // the small buffers of the handle as ONE device allocation (cmf_create): 21 hipFree calls cost 1.3 ms, one 0.16
     size_t arena_bytes = 0;
     bool streams_may_hang = false;  // set on the shards of a FAILED group: their streams are not waited for when they are given back
@@ -497,15 +506,60 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
     h->est_kind = kind;
     ++h->est_gen;
 }
-// What the MU entries read for data / data' / "est is current", and what their loss is divided by: the masked copies while a mask of
-// cmf_mu_set_mask is installed.  reuse_est, the speculated C2 contraction and the deferred loss carry all compare against mu_est_kind.
-static inline const float *mu_X(const cmf_handle_s *h) { return h->mu_mask ? h->Xm : h->X; }
-static inline const float *mu_XT(const cmf_handle_s *h) { return h->mu_mask ? h->XmT : h->XT; }
-static inline int mu_est_kind(const cmf_handle_s *h) { return h->mu_div == 2 ? 9 : h->mu_mask ? (h->mu_div ? 8 : 6) : h->mu_div ? 7 : 1; }
-static inline double mu_norm(const cmf_handle_s *h) { return h->mu_mask ? h->xm_norm : h->data_norm; }
+// ---- the forms of the MU rule: one row each ----
+// The single-handle MU path (cmf_api.hip: w_phase_impl, h_update_impl, launch_loss_conv, w_speculate, cmf_masked_loss) reads the active form from
+// mu_form(h).  A new form: a row here, its conv modes in mu_launch_conv (cmf_api.hip), its install / refusal entry (cmf_mu_set_mask, cmf_mu_set_divergence).
+using MuBuf = float *cmf_handle_s::*; // a buffer of the handle
+constexpr MuBuf MU_NONE = nullptr, MU_X = &cmf_handle_s::X, MU_XT = &cmf_handle_s::XT, MU_XM = &cmf_handle_s::Xm, MU_XMT = &cmf_handle_s::XmT, MU_M = &cmf_handle_s::M,
+                MU_MT = &cmf_handle_s::MT, MU_EST = &cmf_handle_s::est, MU_EST_T = &cmf_handle_s::estT, MU_EST2 = &cmf_handle_s::est2, MU_EST2_T = &cmf_handle_s::est2T;
+struct MuForm {
+    int store_family, loss_family;  // conv family (cmf_conv_modes.h) of the bases store / store' and of loss / loss + store
+    int est_kind;                   // what the storing convs leave in est
+    MuBuf data;                     // the data the form fits: raw, or select(mask, data, 0)
+    MuBuf conv_data[4];             // data operand per conv base (MU_NONE: launch_conv's default, the raw data in the base's layout)
+    int c2_nsrc; MuBuf c2_src[2];   // C2 (update_motifs!): sources contracted with H_shift -> [numW | denomW] (one source: the same buffer named twice)
+    int c3_nsrc; MuBuf c3_first;    // C3 (update_feature_maps!): source count and first source; the second (or only) one is estT
+    int h_num, h_den;               // positions of numH and denomH among the c3_nsrc slabs of hslabs; h_den < 0, kl_den(): the denominators
+                                    // come from the sums of H / W (kl_hsum / kl_den_w / kl_wsum / kl_den_h), not from a contraction
+    bool sqrt_update;               // the element-wise updates take the square root of the quotient
+    bool square_fusions;            // the few-component fusions (w_update_small_kernel, the H update inside the C3 launch) and the speculated C2 apply
+    bool loss_is_mean;              // mu_loss: sum / data_sum (a divergence) instead of sqrt(sum) / norm(data)
+    int held_out_family;            // cmf_masked_loss: family of its loss-only conv on the raw data.  KL under its own mask scores by its divergence;
+                                    // every other row by squared error under the handle's mask, which may be the PGD entries' (cmf_set_mask)
+    constexpr bool kl_den() const { return h_den < 0; }
+};
+enum { MU_SQUARE = 0, MU_SQUARE_MASKED, MU_KL, MU_KL_MASKED, MU_IS, MU_NFORMS };
+constexpr MuForm kMuForms[MU_NFORMS] = { // (in the order of the enum)
+    {CONV_FAM_PLAIN, CONV_FAM_PLAIN, EST_CONV, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
+     2, {MU_X, MU_EST}, 2, MU_XT, 0, 1, false, true, false, CONV_FAM_MU_MASKED},
+    {CONV_FAM_MU_MASKED, CONV_FAM_MU_MASKED, EST_MU_MASKED, MU_XM, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
+     2, {MU_XM, MU_EST}, 2, MU_XMT, 0, 1, false, true, false, CONV_FAM_MU_MASKED},
+    {CONV_FAM_KL, CONV_FAM_KL, EST_KL_R, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
+     1, {MU_EST, MU_EST}, 1, MU_EST_T, 0, -1, false, false, true, CONV_FAM_MU_MASKED},
+    // (the KL family's store modes given Xm / Xm' store 0 / e = 0 at the held-out entries: only the loss bases need the masked family;
+    //  the denominators are the same contractions on the mask itself, which lands in FRONT of the numerator in hslabs)
+    {CONV_FAM_KL, CONV_FAM_KL_MASKED, EST_KL_R_MASKED, MU_XM, {MU_XM, MU_XMT, MU_XM, MU_XM},
+     2, {MU_EST, MU_M}, 2, MU_MT, 1, 0, false, false, true, CONV_FAM_KL_MASKED},
+    // (P and Q from one conv; C3 contracts (Q', P'): the numerator second)
+    {CONV_FAM_IS, CONV_FAM_IS, EST_IS_PQ, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
+     2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, true, false, true, CONV_FAM_MU_MASKED},
+};
+static inline const MuForm &mu_form(const cmf_handle_s *h)
+{
+    return kMuForms[h->mu_div == CMF_DIV_IS ? MU_IS : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
+}
+static inline float *mu_buf(const cmf_handle_s *h, MuBuf b) { return b ? h->*b : nullptr; }
+// What the MU entries read for data / "est is current".  reuse_est, the speculated C2 contraction and the deferred loss carry all
+// compare against mu_est_kind.
+static inline const float *mu_X(const cmf_handle_s *h) { return mu_buf(h, mu_form(h).data); }
+static inline int mu_est_kind(const cmf_handle_s *h) { return mu_form(h).est_kind; }
 // the loss of the MU entries from the sum its loss conv leaves: norm(est - data) / norm(data), or D(data, est) / sum(data) under KL
 // (Itakura-Saito: data_sum holds N * T, the mean divergence per entry)
-static inline double mu_loss(const cmf_handle_s *h, double ss) { return h->mu_div ? ss / h->data_sum : std::sqrt(ss) / mu_norm(h); }
+static inline double mu_loss(const cmf_handle_s *h, double ss)
+{
+    const MuForm &f = mu_form(h);
+    return f.loss_is_mean ? ss / h->data_sum : std::sqrt(ss) / (f.data == MU_XM ? h->xm_norm : h->data_norm);
+}
 int wb_after_H(cmf_handle_s *h); // hook: the kernels that make H final have been enqueued (cmf_writeback.h)
 int gram_ensure(cmf_handle_s *h);
 int hals_w_impl(cmf_handle_s *h, double l1W, double l2W);
@@ -618,6 +672,15 @@ static const char *kProfNames[PROF_NCLS] = {"conv", "conv_t", "conv_loss", "conv
                                             "conv_resid", "hxt_resid", "hxt_hh", "transconv_1src", "gram_denom_h", "gram_tables", "gram_w"};
 static_assert(PROF_NCLS <= 32, "cmf_handle_s::prof_seen holds 32 classes");
 
+// the "profile" class of a C2 launch, from what it contracts: data (and est) of the MU rule, est of the active form alone (a
+// denominator), a stored residual, the HALS rule's HX
+static inline int hxt_prof_class(const cmf_handle_s *h, const float *X0, int nsrc)
+{
+    const bool x0_data = X0 == mu_X(h);
+    return (nsrc == 2 && x0_data) ? PROF_HXT : (nsrc == 1 && x0_data) ? PROF_HXT_NUM : (nsrc == 1 && X0 == h->est && h->est_kind == mu_est_kind(h)) ? PROF_HXT_DEN
+           : (nsrc == 1 && X0 == h->est) ? PROF_HXT_RESID : (X0 == h->hals_HX && h->hals_HX) ? PROF_HXT_HH : PROF_OTHER;
+}
+
 struct ProfScope {
     cmf_handle_s *h;
     hipEvent_t b = nullptr;
@@ -638,92 +701,82 @@ struct ProfScope {
     ~ProfScope() { if (b) (void)hipEventRecord(b, h->stream); }
 };
 
+// The tiles at the end of the one-wave conv grid (conv3_kernel, conv3_chase_kernel) are cut into one-wave pieces: the remainder of the
+// last round when it is thin, and, from kConvSplitMinRounds rounds on, kConvSplitExtraPerCu tiles per CU more -- after several rounds
+// of dynamic dispatch the waves of a SIMD are out of step and the launch ends in a ragged drain one tile long; small pieces at the end
+// of the queue fill it (config 2, 8.1 rounds: -1.5 % in every mode; below 4 rounds it costs +1-4 %: profiles/r02*_conv_split*).
+constexpr int kConvWaveSlotsPerCu = 12;  // one-wave workgroups resident on a CU
+constexpr int kConvThinTilesPerCu = 3;   // a remainder of at most this many tiles per CU is cut; a larger one is left as whole tiles
+constexpr int kConvSplitMinRounds = 4, kConvSplitExtraPerCu = 3;
+struct ConvTailCut { int cut, n_full, pieces; }; // tiles cut | whole tiles in front | pieces per cut tile: 4, or 16 below one cut tile per CU
+static inline ConvTailCut conv_tail_cut(const cmf_handle_s *h, int tiles, int n_cu)
+{
+    const int slots = kConvWaveSlotsPerCu * n_cu, rem = tiles % slots;
+    int cut = 0;
+    if (h->conv_split) {
+        if (rem > 0 && rem <= kConvThinTilesPerCu * n_cu) cut = rem;
+        if (tiles / slots >= kConvSplitMinRounds) cut += kConvSplitExtraPerCu * n_cu;
+        cut = std::min(cut, tiles);
+    }
+    return {cut, tiles - cut, (cut > 0 && cut < n_cu && h->conv_split != 4) ? 16 : 4};
+}
+
+// data == NULL: the handle's data in the layout the mode reads (the masked rules pass Xm / XmT, cmf_masked_loss the raw data)
 template <int MODE>
 static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
 {
-    // modes 8 .. 11: modes 0 .. 3 under the MU rule's mask; modes 12 .. 15: their KL forms; 18, 19: modes 14, 15 under the mask;
-    // modes 20 .. 23: the Itakura-Saito forms of modes 0 .. 3, which store P through out and Q through the handle's second pair (cmf_kernels.h)
-    constexpr int BASE = MODE >= 20 ? MODE - 20 : MODE >= 16 ? MODE - 16 : MODE >= 12 ? MODE - 12 : MODE >= 8 ? MODE - 8 : MODE;
-    constexpr bool KLM = CONV_KL_MASKED(MODE);
-    ProfScope prof_(h, BASE == 0 ? PROF_CONV : BASE == 1 ? PROF_CONV_T : BASE == 2 ? PROF_CONV_LOSS : BASE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
+    ProfScope prof_(h, conv_pgd(MODE) ? PROF_CONV_RESID : conv_base(MODE) == CONV_BASE_STORE ? PROF_CONV : conv_base(MODE) == CONV_BASE_STORE_T ? PROF_CONV_T
+                       : conv_base(MODE) == CONV_BASE_LOSS ? PROF_CONV_LOSS : PROF_CONV_LOSS_STORE);
     const CmfDims &d = h->d;
-    if (((MODE >= 8 && MODE <= 11) || KLM) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
+    if ((conv_mu_masked(MODE) || conv_kl_masked(MODE)) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
-    if (CONV_IS(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito conv without its second pair of buffers");
-    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : ((MODE == 13 || MODE == 21) ? h->XT : h->X); p.partial = h->partial;
-    p.out2 = MODE == 21 ? h->est2T : CONV_IS(MODE) ? h->est2 : nullptr;
-    p.mask = (MODE == 7 || MODE == 9) ? h->MT : h->M;
+    if (conv_is(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito conv without its second pair of buffers");
+    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (conv_data_transposed(MODE) ? h->XT : h->X); p.partial = h->partial;
+    p.out2 = !conv_is(MODE) ? nullptr : conv_transposed(MODE) ? h->est2T : h->est2; // (Q; out takes P)
+    p.mask = conv_mask_transposed(MODE) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
-    p.loss_abs = (MODE >= 4 && MODE <= 7) ? h->pgd_loss_abs_now : ((MODE == 10 || MODE == 18) ? h->mask_complement_now : 0);
+    p.loss_abs = conv_loss_abs_is_absolute_loss(MODE) ? h->pgd_loss_abs_now : (conv_loss_abs_is_complement(MODE) ? h->mask_complement_now : 0);
     dim3 grid(h->conv_gx, gy), block(256);
-    // measured at config 2 (tools/time_kernels.py): the one-wave kernel wins for the epilogues that read data
-    // (0.924 vs 0.931 ms loss only, 0.936 vs 0.943 ms loss + store), the 128 x 128 tiles for the store-only ones
-    // (0.911 vs 0.932 ms est, 0.910 vs 0.924 ms est')
-    constexpr bool reads_data = (MODE >= 2); // every mode but the two plain stores loads a data (and mask) tile in its epilogue
-    // The one-wave kernel can cut the tiles of its thin last round into quarter tiles (conv3_kernel).  That pays when
-    // the remainder is small against the 12 wave slots per CU -- short shards: 3136 tiles on 3072 slots at T/8 -- and
-    // then decides the variant for every mode; a remainder above 3 tiles per CU is left as whole tiles.
-    const int gx3 = d.Np / 64, tiles3 = gx3 * ((T_store + 63) / 64), slots3 = 12 * h->n_cu;
-    const int rem3 = tiles3 % slots3;
-    // The tiles at the end of the grid are cut into one-wave pieces: the remainder of the last round when it is thin
-    // (at most 3 tiles per CU), and, from `split_min_rounds` rounds on, `split_extra` more -- after several rounds of
-    // dynamic dispatch the waves of a SIMD are out of step and the launch ends in a ragged drain one tile long; small
-    // pieces at the end of the queue fill it (measured at config 2, 8.1 rounds: -1.5 % in every mode).
-    // Below 4 rounds the extra cut costs more than it fills (T/4 and T/8 shards: +1-4 %).
-    const int split_min_rounds = 4, split_extra = 3 * h->n_cu; // (profiles/r02*_conv_split*: the sweep these came from)
-    int cut = 0;
-    if (h->conv_split) {
-        if (rem3 > 0 && rem3 <= 3 * h->n_cu) cut = rem3;
-        if (tiles3 / slots3 >= split_min_rounds) cut += split_extra;
-        cut = std::min(cut, tiles3);
-    }
-    {
-        if (h->small_k) { // few components: one-wave tiles over the ceil(K/2) live k pairs per lag (conv_small_kernel)
-            const int nkp = (d.K + 1) / 2;
-            // the tiles beyond whole rounds of one tile per SIMD slot-triple (3 per SIMD) go out as quarter pieces at the end of the
-            // grid, when they are few (at most one tile per SIMD: otherwise whole tiles balance well enough)
-            const int per_round = 4 * h->n_cu;                          // one tile per SIMD
-            const int remq = tiles3 % per_round;
-            int cutq = (h->conv_split && tiles3 >= per_round && remq > 0 && remq <= per_round / 4) ? remq : 0;
-            if (h->conv_split && tiles3 < per_round) cutq = tiles3; // fewer tiles than SIMDs (short recordings): quarter pieces only (configs[0]: 9-12 -> 5-8 us)
-            const int n_full = tiles3 - cutq;
-            grid = dim3(n_full + 4 * cutq);
-            // (loss + store on a short launch: the data tile is requested before the MFMA loop, conv3_tile)
-            const bool pre = BASE == 3 && nkp <= 4 && tiles3 <= 4 * per_round;
-#define CASE(NKP_) do { if (pre) hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_, (BASE == 3 && NKP_ <= 4)>), grid, dim3(64), 0, h->stream, p, gx3, n_full); \
+    const int gx3 = d.Np / 64, tiles3 = gx3 * ((T_store + 63) / 64);
+    if (h->small_k) { // few components: one-wave tiles over the ceil(K/2) live k pairs per lag (conv_small_kernel)
+        const int nkp = (d.K + 1) / 2;
+        // the tiles beyond whole rounds of one tile per SIMD slot-triple (3 per SIMD) go out as quarter pieces at the end of the
+        // grid, when they are few (at most one tile per SIMD: otherwise whole tiles balance well enough)
+        const int per_round = 4 * h->n_cu;                          // one tile per SIMD
+        const int remq = tiles3 % per_round;
+        int cutq = (h->conv_split && tiles3 >= per_round && remq > 0 && remq <= per_round / 4) ? remq : 0;
+        if (h->conv_split && tiles3 < per_round) cutq = tiles3; // fewer tiles than SIMDs (short recordings): quarter pieces only (configs[0]: 9-12 -> 5-8 us)
+        const int n_full = tiles3 - cutq;
+        grid = dim3(n_full + 4 * cutq);
+        // (loss + store on a short launch: the data tile is requested before the MFMA loop, conv3_tile)
+        const bool pre = conv_has_pre(MODE) && nkp <= 4 && tiles3 <= 4 * per_round;
+#define CASE(NKP_) do { if (pre) hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_, (conv_has_pre(MODE) && NKP_ <= 4)>), grid, dim3(64), 0, h->stream, p, gx3, n_full); \
                         else hipLaunchKernelGGL((conv_small_kernel<MODE, NKP_>), grid, dim3(64), 0, h->stream, p, gx3, n_full); } while (0)
-            if (nkp <= 1) CASE(1); else if (nkp == 2) CASE(2); else if (nkp == 3) CASE(3); else if (nkp == 4) CASE(4);
-            else if (nkp <= 6) CASE(6); else CASE(8);
+        if (nkp <= 1) CASE(1); else if (nkp == 2) CASE(2); else if (nkp == 3) CASE(3); else if (nkp == 4) CASE(4);
+        else if (nkp <= 6) CASE(6); else CASE(8);
 #undef CASE
-            h->launches[LA_CONV_SMALL + (nkp <= 4 ? std::max(nkp, 1) - 1 : nkp <= 6 ? 4 : 5)] += 1;
-            if (cutq > 0) h->launches[LA_CONV_SMALL_Q] += 1;
-            if (pre) h->launches[LA_CONV_SMALL_PRE] += 1;
-            h->conv_partials = (int)grid.x;
-            KCHK("conv_small_kernel");
-            return CMF_OK;
-        }
+        h->launches[LA_CONV_SMALL + (nkp <= 4 ? std::max(nkp, 1) - 1 : nkp <= 6 ? 4 : 5)] += 1;
+        if (cutq > 0) h->launches[LA_CONV_SMALL_Q] += 1;
+        if (pre) h->launches[LA_CONV_SMALL_PRE] += 1;
+        h->conv_partials = (int)grid.x;
+        KCHK("conv_small_kernel");
+        return CMF_OK;
     }
-    const bool split = cut > 0;
-    const int variant = (h->conv_variant && BASE <= 2 && MODE != 12 && MODE != 13 && !KLM && MODE != 20 && MODE != 21) ? h->conv_variant : ((reads_data || split) ? 3 : 2);
+    // measured at config 2 (tools/time_kernels.py): the one-wave kernel wins for the epilogues that read data (0.924 vs 0.931 ms loss
+    // only, 0.936 vs 0.943 ms loss + store), the 128 x 128 tiles for the store-only ones (0.911 vs 0.932 ms est, 0.910 vs 0.924 ms est').
+    // A cut tail (short shards: 3136 tiles on 3072 slots at T/8) decides for the one-wave kernel in every mode, and so does a mode
+    // without 128 x 128 tiles (conv_on_tiles128), whatever option "conv_kernel" says: the one-wave kernel won those modes anyway.
+    const ConvTailCut tc = conv_tail_cut(h, tiles3, h->n_cu);
+    const int variant = (h->conv_variant && conv_on_tiles128(MODE)) ? h->conv_variant : ((conv_reads_tile(MODE) || tc.cut > 0) ? 3 : 2);
     if (d.K % 32 == 0 && variant == 3) {
-        const int n_full = tiles3 - cut;
-        // quarter tiles reach every SIMD only from one tile per CU on; below that, sixteenth tiles
-        const int pieces = (split && cut < h->n_cu && h->conv_split != 4) ? 16 : 4;
-        grid = dim3(n_full + pieces * (tiles3 - n_full));
-        hipLaunchKernelGGL((conv3_kernel<MODE>), grid, dim3(64), 0, h->stream, p, gx3, n_full, pieces);
-        h->launches[n_full == tiles3 ? LA_CONV3_WHOLE : n_full > 0 ? (pieces == 4 ? LA_CONV3_WHOLE_P4 : LA_CONV3_WHOLE_P16)
-                                                         : (pieces == 4 ? LA_CONV3_P4 : LA_CONV3_P16)] += 1;
+        grid = dim3(tc.n_full + tc.pieces * tc.cut);
+        hipLaunchKernelGGL((conv3_kernel<MODE>), grid, dim3(64), 0, h->stream, p, gx3, tc.n_full, tc.pieces);
+        h->launches[tc.cut == 0 ? LA_CONV3_WHOLE : tc.n_full > 0 ? (tc.pieces == 4 ? LA_CONV3_WHOLE_P4 : LA_CONV3_WHOLE_P16)
+                                                 : (tc.pieces == 4 ? LA_CONV3_P4 : LA_CONV3_P16)] += 1;
     } else if (d.K % 32 == 0) {
-        // the 128 x 128 kernel exists for the epilogues that only store or only sum (est, est', loss): with a data tile
-        // read AND a store in the epilogue (mode 3 and the residual modes) it needs more than the 168 registers three
-        // workgroups per CU leave (it spilled to scratch), and the one-wave kernel won those modes anyway
-        // (KL: the loss-only mode alone -- modes 12 and 13 read a data tile and store, and run on the one-wave kernel like mode 3;
-        //  mode 18 adds a mask tile to mode 14's operands and is routed to the one-wave tiles whatever option "conv_kernel" says)
-        // (Itakura-Saito: the loss-only mode 22 alone, like KL)
-        constexpr bool TILES128 = BASE <= 2 && MODE != 12 && MODE != 13 && !KLM && MODE != 20 && MODE != 21;
-        if constexpr (TILES128) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
-        if constexpr (TILES128) h->launches[LA_CONV2] += 1;
+        if constexpr (conv_on_tiles128(MODE)) hipLaunchKernelGGL((conv2_kernel<MODE>), grid, block, 0, h->stream, p);
+        if constexpr (conv_on_tiles128(MODE)) h->launches[LA_CONV2] += 1;
     } else {
         hipLaunchKernelGGL((conv_kernel<MODE, 0>), grid, block, 0, h->stream, p);
         h->launches[LA_CONV] += 1;
@@ -740,30 +793,20 @@ template <int MODE>
 static int launch_conv_rows(cmf_handle_s *h, float *out, int row0, int nrows, int pidx0, int n_cu, const int *gate, int *abort_word,
                             int *host_status, int *npartials, int T_store = -1)
 {
-    ProfScope prof_(h, MODE == 1 ? PROF_CONV_T : MODE == 3 ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
+    ProfScope prof_(h, MODE == CONV_EST_T ? PROF_CONV_T : MODE == CONV_LOSS_EST ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
     ConvParams p;
-    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = h->X; p.partial = h->partial; p.mask = h->M;
+    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = conv_data_transposed(MODE) ? h->XT : h->X; p.partial = h->partial; p.mask = h->M;
     p.out2 = nullptr;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store >= 0 ? T_store : d.Tl;
     p.N = d.N;
     p.loss_abs = 0;
-    if (MODE == 5 || MODE == 7) p.data = h->XT;
-    const int gx3 = d.Np / 64, tiles3 = gx3 * nrows, slots3 = 12 * n_cu;
-    const int rem3 = tiles3 % slots3;
-    int cut = 0;
-    if (h->conv_split) {
-        if (rem3 > 0 && rem3 <= 3 * n_cu) cut = rem3;
-        if (tiles3 / slots3 >= 4) cut += 3 * n_cu;
-        cut = std::min(cut, tiles3);
-    }
-    const int n_full = tiles3 - cut;
-    const int pieces = (cut > 0 && cut < n_cu && h->conv_split != 4) ? 16 : 4;
-    const int grid = n_full + pieces * cut;
-    constexpr bool LOSS = (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 6); // (the other modes write no per-tile sums)
-    if (LOSS && (size_t)(pidx0 + grid) > n_partial(h)) return fail(CMF_ERR_STATE, "internal: loss partial buffer too small for a split conv");
-    if (gate) hipLaunchKernelGGL((conv3_chase_kernel<MODE, true>), dim3(grid), dim3(64), 0, h->stream, p, gx3, n_full, pieces, row0, pidx0, gate, abort_word, host_status);
-    else hipLaunchKernelGGL((conv3_chase_kernel<MODE, false>), dim3(grid), dim3(64), 0, h->stream, p, gx3, n_full, pieces, row0, pidx0, gate, abort_word, host_status);
+    const int gx3 = d.Np / 64;
+    const ConvTailCut tc = conv_tail_cut(h, gx3 * nrows, n_cu);
+    const int grid = tc.n_full + tc.pieces * tc.cut;
+    if (conv_writes_loss(MODE) && (size_t)(pidx0 + grid) > n_partial(h)) return fail(CMF_ERR_STATE, "internal: loss partial buffer too small for a split conv");
+    if (gate) hipLaunchKernelGGL((conv3_chase_kernel<MODE, true>), dim3(grid), dim3(64), 0, h->stream, p, gx3, tc.n_full, tc.pieces, row0, pidx0, gate, abort_word, host_status);
+    else hipLaunchKernelGGL((conv3_chase_kernel<MODE, false>), dim3(grid), dim3(64), 0, h->stream, p, gx3, tc.n_full, tc.pieces, row0, pidx0, gate, abort_word, host_status);
     KCHK("conv3_chase_kernel");
     *npartials = grid;
     return CMF_OK;

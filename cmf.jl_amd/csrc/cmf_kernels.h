@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+#include "cmf_conv_modes.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -57,52 +58,38 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 // 64x64 sub-tile = 2x2 MFMA blocks.  The K-row H strip of the tile (with its left lag halo) is
 // staged once per 32-lag block in LDS; the W slab streams through a double-buffered LDS chunk,
 // one lag at a time (reduction order: k-block, lag, k).
-//   MODE 0: store est[t][n]      (A operand = H, B = W)
-//   MODE 1: store estT[n][t]     (A operand = W, B = H; same registers, swapped MFMA roles)
-//   MODE 2: no store; per-workgroup sum of (est - data)^2 -> partial[]  (mult.jl:55-57 fused)
-//   MODE 3: MODE 0 + MODE 2
-//   MODE 4: store est - data (the residual of hals.jl / pgd.jl) in the [t][n] layout + the loss sum
-//   MODE 5: store (est - data)^T in the [n][t] layout (p.data = dataT)
-//   MODE 6: MODE 4 with the residual multiplied by p.mask [t][n]  (MaskedLoss, pgd.jl:58-70)
-//   MODE 7: MODE 5 with the residual multiplied by p.mask = maskT [n][t]
-//   (modes 4-7 with p.loss_abs: the stored quantity is the AbsoluteLoss gradient sign(est - data) [.* mask] and the
-//    loss sum is sum |mask .* (est - data)|, pgd.jl:41-47)
-//   MODE 8 .. 11: modes 0 .. 3 of the MU rule under a 0/1 mask (p.mask in the layout of the store: [t][n], MODE 9: maskT [n][t]):
-//     what is stored is mask .* est, what is summed is (mask .* (est - data))^2.  The mask acts as a SELECT (an entry with mask == 0
-//     contributes 0 whatever data holds there, NaN included).  MODE 10 with p.loss_abs != 0 sums over the entries with mask == 0
-//     instead (cmf_masked_loss: the held-out score).
-//   MODE 12 .. 15: the KL form of the MU rule (cmf_mu_set_divergence), e = est + eps:
-//     MODE 12: store R[t][n] = data / e                    MODE 13: store R'[n][t] (p.data = dataT [Np][TP])
-//     MODE 14: no store; per-workgroup sum of the divergence terms (data > 0 ? data log(data / e) : 0) - data + est -> partial[]
-//     MODE 15: MODE 12 + MODE 14
-//     Padding (n >= N, where data and est are 0) stores 0 / eps = 0 and adds 0 to the sum.
-//   MODE 18, 19: modes 14 and 15 under the MU rule's 0/1 mask (p.mask [t][n], the mask tile of modes 10 and 11): the summed term is
-//     obs ? term : 0, a SELECT.  MODE 19 is given p.data = Xm = select(mask, data, 0) and stores R = Xm / e (exactly 0 where mask == 0).
-//     MODE 18 with p.loss_abs != 0 sums over the entries with mask == 0 instead and is then given the raw data (cmf_masked_loss).
-//     The store-only forms under a mask need no mode of their own: modes 12 and 13 with p.data = Xm / XmT store 0 / (v + eps) = 0 at
-//     the held-out entries (16 and 17 stay unassigned).  Padding (mask == 0) adds exactly 0.
-//   MODE 20 .. 23: the Itakura-Saito form of the MU rule (option "is_div"), e = est + eps, Q = 1 / e, P = (data * Q) * Q.  ONE accumulator
-//     tile stores TWO arrays: P through p.out, Q through p.out2.
-//     MODE 20: store P[t][n], Q[t][n]                      MODE 21: store P'[n][t], Q'[n][t] (p.data = dataT [Np][TP])
-//     MODE 22: no store; per-workgroup sum of the divergence terms (r - 1) - log(r), r = data * Q -> partial[]
-//     MODE 23: MODE 20 + MODE 22
-//     Padding: Q = 1 / (0 + eps) is NOT 0 there, so columns n >= N are stored as exact 0 and add 0 to the sum by a SELECT on n < p.N
-//     (in partly live 32-column blocks and in the wholly dead ones whose MFMAs are skipped alike).
+// MODE = family + base (cmf_conv_modes.h has the names, the table and the predicates the code asks).  Per family:
+//   plain (0 .. 3): est[t][n] (A operand = H, B = W), estT[n][t] (A = W, B = H; same registers, swapped MFMA roles), the per-workgroup
+//     sum of (est - data)^2 -> partial[] (mult.jl:55-57 fused), and store + sum.
+//   PGD (4 .. 7): est - data (the residual of hals.jl / pgd.jl) [t][n] + the loss sum, its transpose [n][t] (p.data = dataT), and both
+//     multiplied by p.mask (MaskedLoss, pgd.jl:58-70; the transposed one reads maskT).  With p.loss_abs the stored quantity is the
+//     AbsoluteLoss gradient sign(est - data) [.* mask] and the sum is sum |mask .* (est - data)| (pgd.jl:41-47).
+//   MU under a 0/1 mask (8 .. 11): the plain modes with p.mask in the layout of the store: mask .* est stored, (mask .* (est - data))^2
+//     summed.  The mask acts as a SELECT (an entry with mask == 0 contributes 0 whatever data holds there, NaN included).  The loss-only
+//     mode with p.loss_abs != 0 sums over the entries with mask == 0 instead (cmf_masked_loss: the held-out score).
+//   KL (12 .. 15), e = est + eps: R = data / e stored ([t][n], or [n][t] from p.data = dataT), the divergence terms
+//     (data > 0 ? data log(data / e) : 0) - data + est summed.  Padding (n >= N, where data and est are 0) stores 0 and adds 0.
+//   KL under the mask (18, 19): KL's two loss modes with the mask tile: the summed term is obs ? term : 0, a SELECT.  The storing one is
+//     given p.data = Xm = select(mask, data, 0) and stores R = Xm / e (exactly 0 where mask == 0); the loss-only one with p.loss_abs
+//     sums over mask == 0 on the raw data.  Store only: the KL modes given Xm / XmT store 0 / e = 0 there (16, 17 stay unassigned).
+//   Itakura-Saito (20 .. 23), Q = 1 / e, P = (data * Q) * Q: ONE accumulator tile stores TWO arrays, P through p.out and Q through
+//     p.out2 ([t][n], or [n][t] from dataT); the summed terms are (r - 1) - log(r), r = data * Q.  Q = 1 / (0 + eps) is NOT 0 in the
+//     padding: columns n >= N are stored as exact 0 and add 0 by a SELECT on n < p.N (partly live and wholly dead 32-column blocks alike).
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
     const float *Wt;
     float *out;
-    const float *data; // X [TP][Np] (modes 2, 3, 4, 6, 10 - 12, 14, 15, 18, 19) or XT [Np][TP] (modes 5, 7, 13)
-    const float *mask; // same layout as data (modes 6 - 11, 18, 19)
+    const float *data; // X [TP][Np], or XT [Np][TP] (conv_data_transposed); read by the modes of conv_reads_data
+    const float *mask; // same layout as data (conv_reads_mask)
     double *partial;   // [gridDim.x * gridDim.y]
     int Np, TP, PADL, K, KB, L;
     int T_store; // rows t < T_store are stored / counted
     int N;       // columns n >= N are padding: a 32-column MFMA block that lies wholly behind N is not computed (its sums are 0)
-    int loss_abs; // residual modes (4-7): 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
-                  // MODE 10, 18: 1 = the sum runs over the entries with mask == 0 (the complement)
-    float *out2; // modes 20, 21, 23: the second array stored from the same accumulators (Q; out takes P), in the layout of out.  (Last, so
-                 // that no other field moves: the kernels of the other modes compile to what they were.)
+    int loss_abs; // PGD family: 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
+                  // the masked loss-only modes (conv_loss_abs_is_complement): 1 = the sum runs over the entries with mask == 0
+    float *out2; // Itakura-Saito storing modes: the second array stored from the same accumulators (Q; out takes P), in the layout of out.
+                 // (Last, so that no other field moves.)
 };
 
 // agent-scope accesses (global_load / global_store ... sc1): the hand-off forms of MI355X_MICROARCH.md "inter-workgroup visibility"
@@ -119,15 +106,6 @@ __device__ __forceinline__ f32x4 cmf_load4_sc1(const float *p)
     return v;
 }
 
-#define CONV_TRANSPOSED(MODE) ((MODE) == 1 || (MODE) == 5 || (MODE) == 7 || (MODE) == 9 || (MODE) == 13 || (MODE) == 21)
-#define CONV_MU_MASKED(MODE) ((MODE) >= 8 && (MODE) <= 11)       // the masked forms of modes 0 .. 3
-#define CONV_KL_MASKED(MODE) ((MODE) == 18 || (MODE) == 19)      // modes 14 and 15 under the MU rule's mask: the summed term is a select
-#define CONV_KL(MODE) (((MODE) >= 12 && (MODE) <= 15) || CONV_KL_MASKED(MODE)) // the KL forms: R = data / (est + eps) stored, the divergence summed
-#define CONV_KL_STORE(MODE) ((MODE) == 12 || (MODE) == 15 || (MODE) == 19)
-#define CONV_IS(MODE) ((MODE) >= 20 && (MODE) <= 23)             // the Itakura-Saito forms: P and Q stored, the divergence summed
-#define CONV_IS_STORE(MODE) ((MODE) == 20 || (MODE) == 21 || (MODE) == 23)
-#define CONV_LOSS(MODE) ((MODE) == 2 || (MODE) == 3 || (MODE) == 4 || (MODE) == 6 || (MODE) == 10 || (MODE) == 11 || (MODE) == 14 || (MODE) == 15 || CONV_KL_MASKED(MODE) || (MODE) == 22 || (MODE) == 23)
-#define CONV_PGD(MODE) ((MODE) >= 4 && (MODE) <= 7)              // the residual modes (the only ones p.loss_abs = AbsoluteLoss applies to)
 #define CONV_HS_STRIDE 160
 #define CONV_HS_FLOATS (32 * CONV_HS_STRIDE)
 #define CONV_WS_FLOATS (32 * 128)
@@ -180,8 +158,8 @@ __device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const Con
                                                   int tid, int pidx, const float (&pre)[2][2][16])
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
-    if (!CONV_TRANSPOSED(MODE)) {
+    constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    if (!conv_transposed(MODE)) {
         // acc[ti][ni][r]: t = tw + ti*32 + crow(r,h), n = nw + ni*32 + i
         int rows = p.T_store - tw; // rows of the sub-tile that exist
         rows = rows < 0 ? 0 : (rows > 64 ? 64 : rows);
@@ -258,8 +236,8 @@ template <int MODE>
 __device__ __forceinline__ void conv_is_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
-    if (!CONV_TRANSPOSED(MODE)) {
+    constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    if (!conv_transposed(MODE)) {
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
         const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
@@ -314,8 +292,8 @@ template <int MODE>
 __device__ __forceinline__ void conv16_is_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE), STORE = CONV_IS_STORE(MODE);
-    if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
+    constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    if (!conv_transposed(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
         const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
@@ -374,20 +352,20 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 {
     if (pidx < 0) pidx = blockIdx.y * gridDim.x + blockIdx.x; // slot of this tile's loss partial
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE);
-    constexpr bool RESID = (MODE == 4 || MODE == 6);
-    constexpr bool MASKED = (MODE == 6 || MODE == 7);
-    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
-    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
-    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
+    constexpr bool LOSS = conv_writes_loss(MODE);
+    constexpr bool RESID = (conv_pgd(MODE) && conv_writes_loss(MODE));
+    constexpr bool MASKED = (conv_pgd(MODE) && conv_reads_mask(MODE));
+    constexpr bool MUM = conv_mu_masked(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = conv_kl(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = conv_kl_masked(MODE); // ... under the MU rule's mask: the term enters by a select
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
-    if constexpr (CONV_IS(MODE)) { // the Itakura-Saito modes: two stores per accumulator, an epilogue of their own
+    if constexpr (conv_is(MODE)) { // the Itakura-Saito modes: two stores per accumulator, an epilogue of their own
         conv_is_epilogue_<MODE, WAVES, PRE>(acc, p, tw, nw, i, h, lane, wave, tid, pidx, pre);
         return;
     }
-    if (!CONV_TRANSPOSED(MODE)) {
+    if (!conv_transposed(MODE)) {
         // acc[ti][ni][r]: t = tw + ti*32 + crow(r,h), n = nw + ni*32 + i
         int rows = p.T_store - tw; // rows of the sub-tile that exist
         rows = rows < 0 ? 0 : (rows > 64 ? 64 : rows);
@@ -406,7 +384,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
             // queued behind stores would wait for them on the in-order vmcnt.  A group is the whole 64 x 64 sub-tile,
             // or one 32 x 32 block when the mask doubles the operands (the registers do not stretch further).
             constexpr int GT = (MASKED || ((MUM || KLM) && LOSS)) ? 1 : 2; // blocks per group along t and n
-            const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs; // wave-uniform: the sum over the held-out entries
+            const bool comp = conv_loss_abs_is_complement(MODE) && p.loss_abs; // wave-uniform: the sum over the held-out entries
 #pragma unroll
             for (int gt = 0; gt < 2; gt += GT)
 #pragma unroll
@@ -456,15 +434,15 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
                                 const int so = (((gt + ti) * 32 + (r & 3) + 8 * (r >> 2)) * Np + (gn + ni) * 32) * 4;
                                 const float v = acc[gt + ti][gn + ni][r];
                                 float d = MASKED ? (v - dv[ti][ni][r]) * mv[ti][ni][r] : v - dv[ti][ni][r];
-                                if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, so);
+                                if (conv_plain(MODE) && conv_stores_tn(MODE)) cmf_bstore(v, ro, voff, so);
                                 if (MUM) {
                                     const bool obs = mv[ti][ni][r] != 0.f;
-                                    if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
+                                    if (conv_stores_tn(MODE)) cmf_bstore(obs ? v : 0.f, ro, voff, so);
                                     d = (obs != comp) ? d : 0.f;
                                 }
                                 if (KL) {
                                     const float q = cmf_kl_ratio(dv[ti][ni][r], v);
-                                    if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
+                                    if (conv_stores_tn(MODE)) cmf_bstore(q, ro, voff, so);
                                     if (LOSS) d = cmf_kl_term(dv[ti][ni][r], v, q);
                                     if (KLM) d = ((mv[ti][ni][r] != 0.f) != comp) ? d : 0.f;
                                 }
@@ -519,7 +497,7 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
         const __amdgpu_buffer_rsrc_t rm = cmf_rsrc(p.mask + origin, bytes);
         const int voff = (4 * h * TP + i) * 4;
         const bool full = (tw + 64 <= p.T_store); // wave-uniform
-        const bool abs_t = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; MODE 1 (the MU path) compiles to the plain store loop
+        const bool abs_t = conv_loss_abs_is_absolute_loss(MODE) && p.loss_abs; // wave-uniform; MODE 1 (the MU path) compiles to the plain store loop
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -529,10 +507,10 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                        dv[r] = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
+                        dv[r] = (conv_pgd(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
                         mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
                     }
-                    if (CONV_PGD(MODE) && abs_t) { // AbsoluteLoss: the stored quantity is the gradient sign(est - data)
+                    if (conv_pgd(MODE) && abs_t) { // AbsoluteLoss: the stored quantity is the gradient sign(est - data)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
@@ -637,7 +615,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvParams p)
                 const float *hsb = Hs + h * CONV_HS_STRIDE + 32 + wt * 64 + i - (l - lbeg);
                 const float *wsb = Ws + buf * CONV_WS_FLOATS + h * 128 + wn * 64 + i;
 #define CONV_MFMA4(A0, A1, B0, B1)                                                                  \
-    if (CONV_TRANSPOSED(MODE)) {                                                                   \
+    if (conv_transposed(MODE)) {                                                                   \
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(B0, A0, acc[0][0], 0, 0, 0);               \
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(B0, A1, acc[0][1], 0, 0, 0);               \
         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(B1, A0, acc[1][0], 0, 0, 0);               \
@@ -726,7 +704,7 @@ __device__ __forceinline__ void conv2_lag(f32x16 (&acc)[2][2], const float *hsb,
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
         const bool zc = FIRST && kp == 0;
-        if (CONV_TRANSPOSED(MODE)) {
+        if (conv_transposed(MODE)) {
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[kp][0], a0, zc ? zero16 : acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[kp][0], a1, zc ? zero16 : acc[0][1], 0, 0, 0);
             if (NBL == 2) {
@@ -777,7 +755,7 @@ __device__ __forceinline__ void conv2_clear_dead(f32x16 (&acc)[2][2])
 {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        if (CONV_TRANSPOSED(MODE)) { acc[1][0][q] = 0.f; acc[1][1][q] = 0.f; }
+        if (conv_transposed(MODE)) { acc[1][0][q] = 0.f; acc[1][1][q] = 0.f; }
         else { acc[0][1][q] = 0.f; acc[1][1][q] = 0.f; }
     }
 }
@@ -862,7 +840,7 @@ __device__ __forceinline__ void conv3_tile(const ConvParams &p, float *Hs, int t
     // HBM round trip per tile; here it is requested before the loop (64 registers that the few k pairs leave free) with the epilogue's
     // descriptor and offsets, and the epilogue finds it there (protocol shape: 37.8 -> 35.8 us).  On a launch of many rounds (N = 2000:
     // eight tiles per SIMD slot, bandwidth-bound) the W rows of the first lags queue behind these 64 loads and it costs 7 %: not used there.
-    constexpr bool PRE = (PREQ && (MODE == 3 || MODE == 11 || MODE == 15 || MODE == 19 || MODE == 23) && NKP <= 4 && NBL == 2);
+    constexpr bool PRE = (PREQ && conv_has_pre(MODE) && NKP <= 4 && NBL == 2);
     float dpre[2][2][16];
     if (PRE) {
         int rows = p.T_store - t0;
@@ -919,19 +897,19 @@ template <int MODE>
 __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE);
-    constexpr bool RESID = (MODE == 4 || MODE == 6);
-    constexpr bool MASKED = (MODE == 6 || MODE == 7);
-    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
-    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
-    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
-    if constexpr (CONV_IS(MODE)) {
+    constexpr bool LOSS = conv_writes_loss(MODE);
+    constexpr bool RESID = (conv_pgd(MODE) && conv_writes_loss(MODE));
+    constexpr bool MASKED = (conv_pgd(MODE) && conv_reads_mask(MODE));
+    constexpr bool MUM = conv_mu_masked(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = conv_kl(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = conv_kl_masked(MODE); // ... under the MU rule's mask: the term enters by a select
+    if constexpr (conv_is(MODE)) {
         conv_is_epilogue_block<MODE>(acc, p, tb, nb, i, h, lane, pidx);
         return;
     }
-    const bool abs_loss = CONV_PGD(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
-    const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
-    if (!CONV_TRANSPOSED(MODE)) {
+    const bool abs_loss = conv_loss_abs_is_absolute_loss(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
+    const bool comp = conv_loss_abs_is_complement(MODE) && p.loss_abs;       // wave-uniform: the sum over the held-out entries
+    if (!conv_transposed(MODE)) {
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
         const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
@@ -953,15 +931,15 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
             const float v = acc[r];
             float d = MASKED ? (v - dv[r]) * mv[r] : v - dv[r];
-            if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, so);
+            if (conv_plain(MODE) && conv_stores_tn(MODE)) cmf_bstore(v, ro, voff, so);
             if (MUM) {
                 const bool obs = mv[r] != 0.f;
-                if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, so);
+                if (conv_stores_tn(MODE)) cmf_bstore(obs ? v : 0.f, ro, voff, so);
                 d = (obs != comp) ? d : 0.f;
             }
             if (KL) {
                 const float q = cmf_kl_ratio(dv[r], v);
-                if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, so);
+                if (conv_stores_tn(MODE)) cmf_bstore(q, ro, voff, so);
                 if (LOSS) d = cmf_kl_term(dv[r], v, q);
                 if (KLM) d = ((mv[r] != 0.f) != comp) ? d : 0.f;
             }
@@ -996,7 +974,7 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
-                dv[r] = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
+                dv[r] = (conv_pgd(MODE) || KL) ? cmf_bload(rd, voff, so) : 0.f;
                 mv[r] = (MASKED || MUM) ? cmf_bload(rm, voff, so) : 1.f;
             }
 #pragma unroll
@@ -1028,7 +1006,7 @@ __device__ __forceinline__ void convq_lag(f32x16 &acc, const float *hsb, const f
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
         const bool zc = FIRST && kp == 0;
-        if (CONV_TRANSPOSED(MODE)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[kp], a0, zc ? zero16 : acc, 0, 0, 0);
+        if (conv_transposed(MODE)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[kp], a0, zc ? zero16 : acc, 0, 0, 0);
         else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, w[kp], zc ? zero16 : acc, 0, 0, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         a0 = na0;
@@ -1118,19 +1096,19 @@ template <int MODE>
 __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
-    constexpr bool LOSS = CONV_LOSS(MODE);
-    constexpr bool RESID = (MODE == 4 || MODE == 6);
-    constexpr bool MASKED = (MODE == 6 || MODE == 7);
-    constexpr bool MUM = CONV_MU_MASKED(MODE); // 0/1 mask of the MU rule: a select
-    constexpr bool KL = CONV_KL(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
-    constexpr bool KLM = CONV_KL_MASKED(MODE); // ... under the MU rule's mask: the term enters by a select
-    if constexpr (CONV_IS(MODE)) {
+    constexpr bool LOSS = conv_writes_loss(MODE);
+    constexpr bool RESID = (conv_pgd(MODE) && conv_writes_loss(MODE));
+    constexpr bool MASKED = (conv_pgd(MODE) && conv_reads_mask(MODE));
+    constexpr bool MUM = conv_mu_masked(MODE); // 0/1 mask of the MU rule: a select
+    constexpr bool KL = conv_kl(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
+    constexpr bool KLM = conv_kl_masked(MODE); // ... under the MU rule's mask: the term enters by a select
+    if constexpr (conv_is(MODE)) {
         conv16_is_epilogue<MODE>(acc, p, tb, nb, j, kq, lane, pidx);
         return;
     }
-    const bool abs_loss = CONV_PGD(MODE) && p.loss_abs;
-    const bool comp = (MODE == 10 || MODE == 18) && p.loss_abs; // wave-uniform: the sum over the held-out entries
-    if (!CONV_TRANSPOSED(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
+    const bool abs_loss = conv_loss_abs_is_absolute_loss(MODE) && p.loss_abs;
+    const bool comp = conv_loss_abs_is_complement(MODE) && p.loss_abs; // wave-uniform: the sum over the held-out entries
+    if (!conv_transposed(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
         const size_t origin = (size_t)(p.PADL + tb) * Np + nb;
@@ -1150,15 +1128,15 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
         for (int r = 0; r < 4; ++r) {
             const float v = acc[r];
             float d = MASKED ? (v - dv[r]) * mv[r] : v - dv[r];
-            if (MODE == 0 || MODE == 3) cmf_bstore(v, ro, voff, r * Np * 4);
+            if (conv_plain(MODE) && conv_stores_tn(MODE)) cmf_bstore(v, ro, voff, r * Np * 4);
             if (MUM) {
                 const bool obs = mv[r] != 0.f;
-                if (MODE == 8 || MODE == 11) cmf_bstore(obs ? v : 0.f, ro, voff, r * Np * 4);
+                if (conv_stores_tn(MODE)) cmf_bstore(obs ? v : 0.f, ro, voff, r * Np * 4);
                 d = (obs != comp) ? d : 0.f;
             }
             if (KL) {
                 const float q = cmf_kl_ratio(dv[r], v);
-                if (CONV_KL_STORE(MODE)) cmf_bstore(q, ro, voff, r * Np * 4);
+                if (conv_stores_tn(MODE)) cmf_bstore(q, ro, voff, r * Np * 4);
                 if (LOSS) d = cmf_kl_term(dv[r], v, q);
                 if (KLM) d = ((mv[r] != 0.f) != comp) ? d : 0.f;
             }
@@ -1191,7 +1169,7 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
         if (tb + j < p.T_store) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float dvr = (CONV_PGD(MODE) || KL) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
+                const float dvr = (conv_pgd(MODE) || KL) ? cmf_bload(rd, voff, r * TP * 4) : 0.f;
                 const float mvr = (MASKED || MUM) ? cmf_bload(rm, voff, r * TP * 4) : 1.f;
                 float d = acc[r] - dvr;
                 if (abs_loss) d = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
@@ -1210,7 +1188,7 @@ __device__ __forceinline__ void conv16_lag(f32x4 &acc, const float *hsb, const f
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
         const float na = (ks + 1 < 8) ? hsb[(ks + 1) * 4 * CONV16_STRIDE] : 0.f;
-        if (CONV_TRANSPOSED(MODE)) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ks], a, acc, 0, 0, 0);
+        if (conv_transposed(MODE)) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ks], a, acc, 0, 0, 0);
         else acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w[ks], acc, 0, 0, 0);
         a = na;
     }
@@ -1346,7 +1324,7 @@ __global__ __launch_bounds__(64, 3) void conv3_chase_kernel(ConvParams p, int gx
 // reference's protocol shape is 3128 tiles on 1024 SIMDs -- 3.05 per SIMD, so that a handful of SIMDs ran a fourth whole tile
 // while the chip waited (36 us for 19.5 us of MFMA issue per SIMD); in quarters the excess is a quarter tile on a quarter of the SIMDs.
 template <int MODE, int NKP, bool PREQ = false>
-__global__ __launch_bounds__(64, (NKP <= 4 && (MODE <= 1 || MODE == 5)) ? 4 : 3) void conv_small_kernel(ConvParams p, int gx, int n_full)
+__global__ __launch_bounds__(64, (NKP <= 4 && conv_small_four_per_simd(MODE)) ? 4 : 3) void conv_small_kernel(ConvParams p, int gx, int n_full)
 {
     __shared__ __attribute__((aligned(16))) float Hs[32 * CONV3_STRIDE];
     const int b = blockIdx.x;

@@ -6,17 +6,17 @@ int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked, bool loss_abs)
 {
     const CmfDims &d = h->d;
     h->pgd_loss_abs_now = loss_abs ? 1 : 0;
-    int rc = masked ? launch_conv<6>(h, h->est, d.Tl, h->conv_gy) // pgd.jl:64-70
-                    : launch_conv<4>(h, h->est, d.Tl, h->conv_gy);
+    int rc = masked ? launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy) // pgd.jl:64-70
+                    : launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy);
     h->pgd_loss_abs_now = 0;
     CMFTRY(rc);
-    set_est(h, 2 + (masked ? 1 : 0) + (loss_abs ? 2 : 0));
+    set_est(h, pgd_est_kind(masked, loss_abs));
     return reduce_partials(h, h->partial, h->conv_partials, 0, sumsq);
 }
 
 int ensure_resid(cmf_handle_s *h, bool masked, bool loss_abs)
 {
-    return h->est_kind == 2 + (masked ? 1 : 0) + (loss_abs ? 2 : 0) ? CMF_OK : resid_and_loss(h, nullptr, masked, loss_abs);
+    return h->est_kind == pgd_est_kind(masked, loss_abs) ? CMF_OK : resid_and_loss(h, nullptr, masked, loss_abs);
 }
 
 // ---- HALS (src/algs/hals.jl) -------------------------------------------------------------------
@@ -167,7 +167,7 @@ static int compute_hh(cmf_handle_s *h, float *out = nullptr)
 // update_motifs! (hals.jl:56-60, 104-110), like the MU rule's w_speculate.  Taken by hals_w_impl if nothing has passed set_est since.
 int hals_w_speculate(cmf_handle_s *h)
 {
-    if (h->est_kind != 2 || h->hals_gram == 1 || h->group) return CMF_OK;
+    if (h->est_kind != EST_RESID || h->hals_gram == 1 || h->group) return CMF_OK;
     CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden));
     CMFTRY(compute_hh(h));
     h->hals_spec_gen = h->est_gen;
@@ -193,7 +193,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
         Gsub = h->numden;
     } else {
         // (both already enqueued behind the loss of the update_feature_maps! before, for exactly this state: hals_w_speculate)
-        const bool spec = h->hals_spec_gen >= 0 && h->hals_spec_gen == h->est_gen && h->est_kind == 2;
+        const bool spec = h->hals_spec_gen >= 0 && h->hals_spec_gen == h->est_gen && h->est_kind == EST_RESID;
         h->hals_spec_gen = -1;
         if (spec) h->spec_hits += 1;
         else {
@@ -210,7 +210,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
         hipLaunchKernelGGL(hals_w_sweep_gen_kernel, dim3(d.N), dim3(256), lds_g, h->stream, h->Wt, h->Wn, G, Gsub, h->hals_HH,
                            d.N, d.K, d.L, d.Np, d.K32, h->hals_NpH, (float)l1W, (float)l2W);
         KCHK("hals_w_sweep_gen_kernel");
-        set_est(h, 0);
+        set_est(h, EST_NONE);
         return CMF_OK;
     }
     const int nq = (d.L * d.K32 + 63) / 64; // <= 32 here (hals_ensure)
@@ -232,7 +232,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
     else SWEEP(32, 4);
 #undef SWEEP
     KCHK("hals_w_sweep_reg_kernel");
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     return CMF_OK;
 }
 
@@ -267,7 +267,7 @@ static int hals_h_project(cmf_handle_s *h, bool contract, bool snapshot = false)
                            h->tc_S1, d.Tl, d.K32, h->hals_TPp, h->H, h->Ht, snap, d.TP, d.PADL, flags, nflags);
     } else {
         if (contract) {
-            CMFTRY(launch_conv<5>(h, h->estT, d.Tl, h->conv_gy, h->XT));
+            CMFTRY(launch_conv<CONV_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT));
             CMFTRY(launch_transconv(h, 1, h->estT));
         }
         hipLaunchKernelGGL(hals_p_init_kernel, dim3((d.Tl + 63) / 64, d.KB), dim3(256), 0, h->stream, h->hals_PT, h->hslabs, (const float *)nullptr,
@@ -414,7 +414,7 @@ static int hals_persist_chased(cmf_handle_s *h, const HalsRowParams &q, int ra)
     int rc = hals_persist_launch(h, q, h->hals_debug, false);
     h->stream = h->hals_sB;
     int nA = 0;
-    if (rc == CMF_OK) rc = launch_conv_rows<4>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA);
+    if (rc == CMF_OK) rc = launch_conv_rows<CONV_RESID>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA);
     h->stream = keep;
     CMFTRY(rc);
     HIPCHK(hipEventRecord(h->hals_ev[1], h->hals_sA));
@@ -435,10 +435,10 @@ int hals_resid_and_loss(cmf_handle_s *h, double *sumsq)
     h->hals_chased_rows = h->hals_chased_partials = 0;
     if (ra <= 0) return resid_and_loss(h, sumsq);
     int nB = 0;
-    if (ra < rows_t) CMFTRY(launch_conv_rows<4>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
+    if (ra < rows_t) CMFTRY(launch_conv_rows<CONV_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
     HIPCHK(hipStreamWaitEvent(h->stream, h->hals_ev[2], 0));
     h->conv_partials = nA + nB;
-    set_est(h, 2);
+    set_est(h, EST_RESID);
     return reduce_partials(h, h->partial, h->conv_partials, 0, sumsq);
 }
 
@@ -452,7 +452,7 @@ static int hals_h_enqueue(cmf_handle_s *h, double l1H, double l2H)
     CMFTRY(hals_h_project(h, true, persist)); // (+ the snapshot the persistent pipeline starts from, and its flags cleared)
     const HalsRowParams q = hals_row_params(h, l1H, l2H);
     h->hals_l1 = l1H; h->hals_l2 = l2H;
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     if (h->hals_h_general) {
         ProfScope prof_(h, PROF_HALS_PIPE);
         return hals_h_sweep_general(h, q);
@@ -491,7 +491,7 @@ int hals_h_rerun(cmf_handle_s *h)
     HIPCHK(hipMemcpyAsync(h->H, h->hals_snap, nH * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->Ht, h->hals_snap + nH, nH * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     CMFTRY(hals_h_project(h, false));
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     CMFTRY(hals_h_sweep_stage(h, hals_row_params(h, h->hals_l1, h->hals_l2)));
     return wb_after_H(h); // (an armed write-back has taken the half-finished H: take it again)
 }
@@ -595,7 +595,7 @@ int gram_h_update(cmf_handle_s *h, double l1H, double l2H)
                        h->hslabs, TK, h->tc_S1, h->gram_numden_h + TK, (size_t)0, 1,
                        d.Tl, d.K, d.K32, d.PADL, d.TP, (float)l1H, (float)(2.0 * l2H)); // mult.jl:51-52
     KCHK("h_update_kernel");
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     return wb_after_H(h);
 }
 
@@ -687,7 +687,7 @@ int pgd_w_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg)
                        d.N, d.K, d.Np, d.K32, (float)h->pgd_stepW, nonneg == 1);                         // pgd.jl:237-241
     KCHK("pgd_w_apply_kernel");
     if (nonneg == 2) CMFTRY(pgd_unit_norm(h, true));                                                     // pgd.jl:100-110
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     return pgd_finish(h, &h->pgd_stepW);
 }
 
@@ -698,15 +698,15 @@ int pgd_h_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg, doubl
     if (nonneg < 0 || nonneg > 2) return fail(CMF_ERR_ARG, "constraint must be 0 (none), 1 (NonnegConstraint) or 2 (UnitNormConstraint)");
     const float gscale = h->pgd_loss_abs ? 1.f : 2.f;
     if (!h->pgd_gradH) CMFTRY(dalloc_zero(&h->pgd_gradH, (size_t)d.Tl * d.K32));
-    if (h->est_kind == 2 + (h->M ? 1 : 0) + (h->pgd_loss_abs ? 2 : 0)) {
+    if (h->est_kind == pgd_est_kind(h->M != nullptr, h->pgd_loss_abs != 0)) {
         // est already holds this residual for the resident W, H (stored by the conv that closed the W phase, pgd.jl:245): the
         // H phase's est of pgd.jl:230 is the same array, only tensor_transconv wants it transposed
         hipLaunchKernelGGL(transpose_rows_kernel, dim3(d.Np / 64, (d.Tl + 63) / 64), dim3(256), 0, h->stream, h->est, h->estT, d.Tl, d.Np, d.TP, d.PADL);
         KCHK("transpose_rows_kernel");
     } else {
         h->pgd_loss_abs_now = h->pgd_loss_abs;
-        int rc_conv = h->MT ? launch_conv<7>(h, h->estT, d.Tl, h->conv_gy, h->XT) // (mask .* resid)^T (pgd.jl:64-67)
-                            : launch_conv<5>(h, h->estT, d.Tl, h->conv_gy, h->XT); // resid^T (pgd.jl:230), or its sign (pgd.jl:42-44)
+        int rc_conv = h->MT ? launch_conv<CONV_MASKED_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT) // (mask .* resid)^T (pgd.jl:64-67)
+                            : launch_conv<CONV_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT); // resid^T (pgd.jl:230), or its sign (pgd.jl:42-44)
         h->pgd_loss_abs_now = 0;
         CMFTRY(rc_conv);
     }
@@ -723,7 +723,7 @@ int pgd_h_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg, doubl
                        d.Tl, d.K, d.K32, d.PADL, d.TP, (float)h->pgd_stepH, nonneg == 1);
     KCHK("pgd_h_apply_kernel");
     if (nonneg == 2) CMFTRY(pgd_unit_norm(h, false)); // pgd.jl:100-110
-    set_est(h, 0);
+    set_est(h, EST_NONE);
     CMFTRY(wb_after_H(h));
     CMFTRY(pgd_finish(h, &h->pgd_stepH));
     *loss = std::sqrt(h->pgd_cur_loss / (h->data_norm * h->data_norm)); // pgd.jl:201

@@ -7,9 +7,7 @@
 int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only)
 {
     const CmfDims &d = h->d;
-    const bool x0_data = X0 == mu_X(h);
-    ProfScope prof_(h, (nsrc == 2 && x0_data) ? PROF_HXT : (nsrc == 1 && x0_data) ? PROF_HXT_NUM : (nsrc == 1 && X0 == h->est && h->est_kind == mu_est_kind(h)) ? PROF_HXT_DEN
-                      : (nsrc == 1 && X0 == h->est) ? PROF_HXT_RESID : (X0 == h->hals_HX && h->hals_HX) ? PROF_HXT_HH : PROF_OTHER);
+    ProfScope prof_(h, hxt_prof_class(h, X0, nsrc));
     SkHxtParams p;
     p.Ht = h->Ht; p.X0 = X0; p.X1 = X1; p.slabs = h->sk_slabs;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.L = d.L; p.J = h->sk_J; p.JP = h->sk_JP; p.MG = h->sk_MG; p.Tl = d.Tl;

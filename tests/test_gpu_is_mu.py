@@ -346,3 +346,50 @@ def test_mid_size_fit_against_restatement(cmf, N, T, K, L):
     data, W0, H0 = (np.asarray(a, dtype=np.float64) for a in ir.positive_problem(N, T, K, L, seed=3))
     ref = ir.fit_is(data, W0, H0, max_itr=100)
     check_against(gpu_fit(cmf, data, W0, H0, 100), ref, f"mid-size {(N, T, K, L)}")
+
+
+@pytest.mark.parametrize("N,T,K,L", [(48, 300, 4, 8), (96, 1000, 32, 12), (37, 150, 33, 7)])
+def test_a_walk_through_every_form_on_one_handle(cmf, N, T, K, L):
+    """square -> mask -> KL under the mask -> mask cleared -> Itakura-Saito -> KL -> square on ONE handle.  After every switch
+    update_motifs! is called at once (an est of the previous form that the switch had not voided would be consumed), then
+    update_feature_maps! and two more iterations: W, H and the losses of every segment are bitwise those of a fresh handle that was
+    given the segment's starting factors and put directly into that form."""
+    data, W0, H0 = (np.asarray(a, dtype=np.float64) for a in ir.positive_problem(N, T, K, L, seed=11))
+    mask = cmf.holdout_mask(N, T, frac=0.2, block=L, seed=1)
+
+    def segment(rule):
+        rule.update_motifs()
+        lh = [rule.update_feature_maps()] + list(rule.iterate(2))
+        return rule.download() + (np.asarray(lh),)
+
+    #        form            what the walk does on its handle                      a fresh handle, put directly into the form
+    walk = [("square", lambda r: None, lambda r: None),
+            ("square + mask", lambda r: r.set_mask(mask), lambda r: r.set_mask(mask)),
+            ("KL + mask", lambda r: r.set_divergence(":kl"), lambda r: (r.set_divergence(":kl"), r.set_mask(mask))),
+            ("KL", lambda r: r.set_mask(None), lambda r: r.set_divergence(":kl")),
+            ("Itakura-Saito", lambda r: r.set_divergence(IS), lambda r: r.set_divergence(IS)),
+            ("KL again", lambda r: r.set_divergence(":kl"), lambda r: r.set_divergence(":kl")),
+            ("square again", lambda r: r.set_divergence(":square"), lambda r: None)]
+    rule = cmf.MultUpdate(data, W0, H0)
+    rule.set_option("kl_mask", 1)
+    try:
+        W, H = W0, H0
+        seen = []
+        for form, switch, install in walk:
+            switch(rule)
+            got = segment(rule)
+            fresh = cmf.MultUpdate(data, W, H)
+            try:
+                fresh.set_option("kl_mask", 1)
+                install(fresh)
+                want = segment(fresh)
+            finally:
+                fresh.close()
+            for x, y, what in zip(got, want, ("W", "H", "losses")):
+                assert np.isfinite(x).all()
+                np.testing.assert_array_equal(x, y, err_msg=f"{form}: {what} of the walked handle and of a fresh one differ")
+            seen.append(got[2][-1])
+            W, H = got[0].copy(), got[1].copy()
+        assert len({float(v) for v in seen}) == len(seen)  # (every segment reported a loss of its own)
+    finally:
+        rule.close()

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Are the gfx950 code objects of two checkouts the same device code?  (no GPU needed)
+
+    python tools/device_code_diff.py <checkout A> <checkout B>
+
+Per csrc/*.hip translation unit: the device-only compile line of tools/kernel_resources.py, clang-offload-bundler
+--unbundle, then `llvm-objdump -d` (without its file-name lines) and `llvm-readelf --notes` of both code objects.  Two
+builds of one source differ in a few bytes of the object file, but not in these two texts: equal texts mean the same
+kernels under the same names with the same instructions, registers, LDS and scratch.  Prints `equal` per translation
+unit, or the first kernel whose instructions or metadata differ; exits 1 if anything differs.
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+SYMBOL, SYMBOL_NAME = r"(?m)^(?=[0-9a-f]+ <)", r"^[0-9a-f]+ <([^>]+)>:"      # a symbol of the disassembly
+NOTE, NOTE_NAME = r"(?m)^(?=\s+- \.agpr_count:)", r"\.name:\s+(\S+)"          # a kernel of the metadata note
+
+
+def start(root, tmp):
+    csrc = os.path.join(root, "cmf.jl_amd", "csrc")
+    jobs = {}
+    for src in sorted(f for f in os.listdir(csrc) if f.endswith(".hip")):
+        obj = os.path.join(tmp, src + ".o")
+        jobs[src] = (obj, subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-c", "--cuda-device-only",
+                                            "-I", os.path.join(root, "include"), "-I", csrc, os.path.join(csrc, src), "-o", obj]))
+    return jobs
+
+
+def texts(src, obj, proc):
+    if proc.wait() != 0:
+        raise RuntimeError(f"hipcc failed on {src}")
+    co = obj + ".co"
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={obj}",
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+    dis = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", co]).decode()
+    dis = "\n".join(ln for ln in dis.split("\n") if co not in ln)  # the file-name lines
+    return dis, subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", co]).decode()
+
+
+def demangle(name):
+    try:
+        return subprocess.run(["c++filt", name], stdout=subprocess.PIPE).stdout.decode().strip() or name
+    except OSError:
+        return name
+
+
+def first_difference(a, b, split, name_of):
+    """The name of the first block (of `split`) that differs between the two texts."""
+    for x, y in zip(re.split(split, a), re.split(split, b)):
+        if x != y:
+            m = re.search(name_of, x) or re.search(name_of, y)
+            return demangle(m.group(1)) if m else "(before the first kernel)"
+    return "(one text is a prefix of the other: a kernel was added or removed at the end)"
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    differ = False
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        ja, jb = start(sys.argv[1], ta), start(sys.argv[2], tb)
+        for src in sorted(set(ja) | set(jb)):
+            if src not in ja or src not in jb:
+                print(f"{src}: only in {sys.argv[1] if src in ja else sys.argv[2]}")
+                differ = True
+                continue
+            (da, na), (db, nb) = texts(src, *ja[src]), texts(src, *jb[src])
+            n_kernels = len(re.findall(r"\.agpr_count:", na))
+            if da == db and na == nb:
+                print(f"{src}: equal ({n_kernels} kernels, {da.count(chr(10))} lines of disassembly, {na.count(chr(10))} lines of notes)")
+                continue
+            differ = True
+            if da != db:
+                print(f"{src}: instructions differ, first in {first_difference(da, db, SYMBOL, SYMBOL_NAME)}")
+            if na != nb:
+                print(f"{src}: metadata differs, first in {first_difference(na, nb, NOTE, NOTE_NAME)}")
+    sys.exit(1 if differ else 0)
