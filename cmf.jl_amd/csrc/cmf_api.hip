@@ -558,6 +558,7 @@ static int mu_launch_conv(cmf_handle_s *h, int family, int base, float *out, int
         CASE(CONV_KL_R) CASE(CONV_KL_R_T) CASE(CONV_KL_LOSS) CASE(CONV_KL_LOSS_R)
         CASE(CONV_KLM_LOSS) CASE(CONV_KLM_LOSS_R)
         CASE(CONV_IS_PQ) CASE(CONV_IS_PQ_T) CASE(CONV_IS_LOSS) CASE(CONV_IS_LOSS_PQ)
+        CASE(CONV_BETA_PQ) CASE(CONV_BETA_PQ_T) CASE(CONV_BETA_LOSS) CASE(CONV_BETA_LOSS_PQ)
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: the MU rule launches no conv mode %d", conv_mode(family, base));
     }
@@ -617,14 +618,23 @@ int w_partial_half_impl(cmf_handle_s *h, int den)
     return hxt_contract(h, src, src, 1, h->numden + (den ? LKN : 0), den != 0); // mult.jl:31-34, one source
 }
 
-// The element-wise update of W (mult.jl:37-38; the square root of the quotient where the form says so).
+// The element-wise update of W (mult.jl:37-38; the square root or the power gamma of the quotient where the form says so).
 // den == NULL: denomW lies behind numW in h->numden (the layout of the [numW | denomW] all-reduce buffer)
 int w_apply_impl(cmf_handle_s *h, double l1W, double l2W, const float *tail_src, float *tail_dst, int tail_n, const float *den)
 {
     const CmfDims &d = h->d;
     dim3 grid(d.Np / 64, d.KB, d.L);
     if (!den) den = h->numden + (size_t)d.L * d.K32 * d.Np;
-    const bool root = mu_form(h).sqrt_update;
+    const int step = mu_step_kind(h, mu_form(h));
+    if (step == 2) {
+        hipLaunchKernelGGL(w_update_pow_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, den, d.N, d.K, d.L, d.Np, d.K32, (float)l1W,
+                           (float)(2.0 * l2W), tail_src, tail_dst, tail_n, h->mu_gamma);
+        KCHK("w_update_pow_kernel");
+        h->pow_launches += 1;
+        set_est(h, EST_NONE);
+        return CMF_OK;
+    }
+    const bool root = step == 1;
     hipLaunchKernelGGL(root ? w_update_sqrt_kernel : w_update_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden, den,
                        d.N, d.K, d.L, d.Np, d.K32, (float)l1W, (float)(2.0 * l2W), tail_src, tail_dst, tail_n);
     KCHK(root ? "w_update_sqrt_kernel" : "w_update_kernel");
@@ -667,11 +677,20 @@ static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 
 // The element-wise update of H (mult.jl:51-52) on `rows` columns from padded row `padl` on: numerator and denominator are the sums of
 // n_num / n_den slabs `stride` apart (a stride of 0 with one slab: a finished table).  H is final behind it.
-static int launch_h_update(cmf_handle_s *h, bool sqrt_update, const float *num, size_t num_stride, int n_num, const float *den, size_t den_stride, int n_den,
+static int launch_h_update(cmf_handle_s *h, int step, const float *num, size_t num_stride, int n_num, const float *den, size_t den_stride, int n_den,
                            int rows, int padl, double l1H, double l2H)
 {
     const CmfDims &d = h->d;
     const dim3 grid((rows + HUPD_T - 1) / HUPD_T, d.KB);
+    if (step == 2) { // (cmf_mu_step: the power gamma of the quotient)
+        hipLaunchKernelGGL(h_update_pow_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, num, num_stride, n_num, den, den_stride, n_den, rows, d.K, d.K32, padl,
+                           d.TP, (float)l1H, (float)(2.0 * l2H), h->mu_gamma);
+        KCHK("h_update_pow_kernel");
+        h->pow_launches += 1;
+        set_est(h, EST_NONE);
+        return wb_after_H(h);
+    }
+    const bool sqrt_update = step == 1;
     hipLaunchKernelGGL(sqrt_update ? h_update_sqrt_kernel : h_update_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, num, num_stride, n_num, den, den_stride,
                        n_den, rows, d.K, d.K32, padl, d.TP, (float)l1H, (float)(2.0 * l2H));
     KCHK(sqrt_update ? "h_update_sqrt_kernel" : "h_update_kernel");
@@ -696,7 +715,7 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         CMFTRY(launch_transconv(h, 2, nullptr, true));                    // mult.jl:47-48 on columns [-128, Tl)
         const int hx = h->halo_ext, R = d.Tl + 128;
         const float *num = h->hslabs + (size_t)(128 - hx) * d.K32;        // slab row r holds column r - 128: the update starts at column -hx
-        return launch_h_update(h, false, num, (size_t)2 * R * d.K32, h->tc_S2, num + (size_t)R * d.K32, (size_t)2 * R * d.K32, h->tc_S2, d.Tl + hx, d.PADL - hx,
+        return launch_h_update(h, 0, num, (size_t)2 * R * d.K32, h->tc_S2, num + (size_t)R * d.K32, (size_t)2 * R * d.K32, h->tc_S2, d.Tl + hx, d.PADL - hx,
                                l1H, l2H);
     }
     const MuForm &f = mu_form(h);
@@ -716,8 +735,8 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         KCHK("kl_den_h_kernel");
     }
     const int S = f.c3_nsrc == 2 ? h->tc_S : h->tc_S1;
-    if (f.kl_den()) return launch_h_update(h, f.sqrt_update, h->hslabs + f.h_num * TK, stride, S, h->kl_denH, (size_t)0, 1, d.Tl, d.PADL, l1H, l2H);
-    return launch_h_update(h, f.sqrt_update, h->hslabs + f.h_num * TK, stride, S, h->hslabs + f.h_den * TK, stride, S, d.Tl, d.PADL, l1H, l2H);
+    if (f.kl_den()) return launch_h_update(h, mu_step_kind(h, f), h->hslabs + f.h_num * TK, stride, S, h->kl_denH, (size_t)0, 1, d.Tl, d.PADL, l1H, l2H);
+    return launch_h_update(h, mu_step_kind(h, f), h->hslabs + f.h_num * TK, stride, S, h->hslabs + f.h_den * TK, stride, S, d.Tl, d.PADL, l1H, l2H);
 }
 
 // the conv of mult.jl:55-57 with the loss fused: per-tile sums of the form's loss terms -> h->partial; est of the form is kept for the
@@ -1241,6 +1260,7 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
     if (std::strcmp(name, "writeback_calls") == 0) { *value = h->wb ? h->wb->armed_calls : 0; return CMF_OK; }            // cmf_arm_writeback calls
     if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
+    if (std::strcmp(name, "pow_update_launches") == 0) { *value = h->pow_launches; return CMF_OK; }                          // launches of w_update_pow_kernel / h_update_pow_kernel (the beta form outside 1 < beta <= 2)
     if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
     if (sep_counter(h, name, value)) return CMF_OK;                                                      // pivoting rounds of the last NNLS step of the separable fit
     if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
@@ -1403,6 +1423,8 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
         if (value && h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no Itakura-Saito form: "
                                                                                "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
+        if (value && h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no beta-divergence form: "
+                                                                                 "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no KL form: "
                                                                  "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
@@ -1656,6 +1678,7 @@ int cmf_hals_update_motifs(cmf_handle h, double l1W, double l2W)
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
     if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     h->last_rule_call = 1;
     return hals_w_impl(h, l1W, l2W);
@@ -1668,6 +1691,7 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     CMFTRY(check_ready(h, true));
     if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
     if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates (alternating.jl:51-54): update_motifs! comes next
     h->last_rule_call = 2;
@@ -1840,6 +1864,8 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
         h->M = h->MT = nullptr;
         return CMF_OK;
     }
+    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form (its Q = e.^(beta - 1) would need the mask tile in the "
+                                                                     "storing epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form (its Q = 1 ./ e would need the mask tile in the storing "
                                                                    "epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->mu_div && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
@@ -1923,6 +1949,60 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
     return CMF_OK;
 }
 
+// What the beta form asks of data: finite and non-negative.  The KL form's pass (its sum is not asked for: the padding of X is zero and passes).
+static int beta_check_data(cmf_handle_s *h)
+{
+    double sb[2]; // sum | bad entries
+    CMFTRY(flat_reduce(h, "kl_data_check_kernel", 2, sb, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, h->partial);
+    }));
+    if (sb[1] > 0.0) return fail(CMF_ERR_ARG, "the beta-divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", sb[1]);
+    return CMF_OK;
+}
+
+int cmf_mu_set_beta_divergence(cmf_handle h, double beta)
+{
+    if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
+    // the accepted set (include/cmf_hip.h; the window's edges are accepted, whatever rounding made of 1 - 0.01)
+    const double w = CMF_BETA_WINDOW * (1.0 - 1e-9);
+    if (!std::isfinite(beta)) return fail(CMF_ERR_ARG, "beta must be finite");
+    if (beta == 0.0 || beta == 1.0)
+        return fail(CMF_ERR_ARG, "beta = %g is CMF_DIV_IS (beta = 0) or CMF_DIV_KL (beta = 1): the beta formula is 0/0 there, use cmf_mu_set_divergence with those kinds", beta);
+    if (beta < 0.0 || beta > CMF_BETA_MAX) return fail(CMF_ERR_ARG, "beta must lie in (0, %g], got %.17g", (double)CMF_BETA_MAX, beta);
+    if (beta < w || std::fabs(beta - 1.0) < w)
+        return fail(CMF_ERR_ARG, "beta = %.17g lies within %g of 0 or 1, where the float32 loss loses its digits to the factor 1 / (beta (beta - 1)): use CMF_DIV_IS / CMF_DIV_KL, "
+                                 "or a beta at least %g away", beta, (double)CMF_BETA_WINDOW, (double)CMF_BETA_WINDOW);
+    if (h->group || h->root_only || h->sharded)
+        return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->mu_div == CMF_DIV_BETA && beta == h->mu_beta) return CMF_OK;
+    if (h->wb && h->wb->armed) wb_disarm(h);
+    drop_carry(h);
+    h->spec_gen = -1;
+    set_est(h, EST_NONE);
+    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
+    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no beta-divergence form; set gram = 0 first");
+    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
+    if (h->mu_div != CMF_DIV_BETA) CMFTRY(beta_check_data(h)); // (a failure leaves the divergence the handle had)
+    const CmfDims &d = h->d;
+    if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
+    if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
+    if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
+    float *c = h->beta_consts; // ConvParams::beta_m1 .. beta_c: the exponents and phi's constants (cmf_beta_term), rounded once from fp64
+    c[0] = (float)(beta - 1.0); c[1] = (float)(beta - 2.0); c[2] = (float)beta; c[3] = (float)(1.0 / beta); c[4] = (float)(1.0 / (beta * (beta - 1.0)));
+    double prod = 1.0, fact = 2.0; // c_k = 2 (beta - 2) ... (beta - k - 1) / (k + 2)!
+    for (int k = 1; k <= 6; ++k) {
+        prod *= beta - (double)(k + 1);
+        fact *= (double)(k + 2);
+        c[4 + k] = (float)(2.0 * prod / fact);
+    }
+    h->mu_beta = beta;
+    h->mu_gamma = (float)(beta < 1.0 ? 1.0 / (2.0 - beta) : beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); // Fevotte & Idier 2011
+    h->data_sum = (double)d.N * (double)d.Tl;
+    h->mu_div = CMF_DIV_BETA;
+    return CMF_OK;
+}
+
 int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *data_sumsq)
 {
     if (!h || !resid_sumsq || !data_sumsq) return fail(CMF_ERR_ARG, "NULL argument");
@@ -2000,6 +2080,7 @@ int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int nonne
     }
     CMFTRY(check_ready(h, true));
     if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_w_impl(h, pen_sq, pen_abs, nonneg);
 }
@@ -2014,6 +2095,7 @@ static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_
     }
     CMFTRY(check_ready(h, true));
     if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
     return pgd_h_impl(h, pen_sq, pen_abs, nonneg, loss);
 }

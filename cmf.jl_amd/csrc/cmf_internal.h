@@ -165,6 +165,9 @@ static const char *const kLaunchNames[] = {
     "halo_pack2_kernel", "halo_unpack2_kernel", "halo_pack3_kernel", "halo_unpack3_kernel"};
 static_assert(sizeof(kLaunchNames) / sizeof(kLaunchNames[0]) == LA_NCLS, "one name per launch path");
 
+// mu_div of a handle under cmf_mu_set_beta_divergence: behind the kinds of cmf_mu_set_divergence, which does not take it
+#define CMF_DIV_BETA 3
+
 // What est / estT hold for the resident W, H (cmf_handle_s::est_kind): a reader recomputes on a mismatch, every writer passes through set_est.
 enum EstKind : int {
     EST_NONE = 0,            // nothing
@@ -176,7 +179,8 @@ enum EstKind : int {
     EST_MU_MASKED = 6,       // mask .* tensor_conv(W,H)  (the MU rule under a mask)
     EST_KL_R = 7,            // data ./ (tensor_conv(W,H) + eps)  (the KL form of the MU rule)
     EST_KL_R_MASKED = 8,     // Xm ./ (tensor_conv(W,H) + eps)  (R of the KL form under a mask: exactly 0 where the mask is 0)
-    EST_IS_PQ = 9            // P of the Itakura-Saito form (and est2 holds Q)
+    EST_IS_PQ = 9,           // P of the Itakura-Saito form (and est2 holds Q)
+    EST_BETA_PQ = 10         // P of the beta form for the installed beta (and est2 holds Q); a change of beta voids it
 };
 // the residual the PGD rule keeps (resid_and_loss): masked by MaskedLoss, its sign under AbsoluteLoss
 static inline int pgd_est_kind(bool masked, bool loss_abs) { return EST_RESID + (masked ? 1 : 0) + (loss_abs ? 2 : 0); }
@@ -287,7 +291,11 @@ struct cmf_handle_s {
     bool mu_mask = false;
     float *Xm = nullptr, *XmT = nullptr;
     double xm_sumsq = 0.0, xm_norm = 0.0; // sum of Xm^2 and its root: what the masked MU loss is divided by
-    int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL / CMF_DIV_IS (cmf_mu_set_divergence)
+    int mu_div = 0;              // CMF_DIV_SQUARE / CMF_DIV_KL / CMF_DIV_IS (cmf_mu_set_divergence), CMF_DIV_BETA (cmf_mu_set_beta_divergence)
+    double mu_beta = 0.0;        // the beta of CMF_DIV_BETA
+    float mu_gamma = 1.f;        // ... and its step exponent (1: the element-wise kernels of the plain rule)
+    int64_t pow_launches = 0;    // launches of w_update_pow_kernel / h_update_pow_kernel (cmf_get_counter "pow_update_launches")
+    float beta_consts[11] = {};  // ... and what its convs read, in the order of ConvParams::beta_m1 .. beta_c
     double data_sum = 0.0;       // what the divergence is divided by: sum(data) (under a mask: sum(Xm)); Itakura-Saito: N * Tl, the mean per entry
     int kl_mask = 0;             // cmf_set_option "kl_mask": 1 lets the KL form and a mask of cmf_mu_set_mask be installed together
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
@@ -526,9 +534,10 @@ struct MuForm {
     bool loss_is_mean;              // mu_loss: sum / data_sum (a divergence) instead of sqrt(sum) / norm(data)
     int held_out_family;            // cmf_masked_loss: family of its loss-only conv on the raw data.  KL under its own mask scores by its divergence;
                                     // every other row by squared error under the handle's mask, which may be the PGD entries' (cmf_set_mask)
+    bool pow_update = false;        // the element-wise updates raise the quotient to the handle's mu_gamma where that is not 1 (last: the older rows do not name it)
     constexpr bool kl_den() const { return h_den < 0; }
 };
-enum { MU_SQUARE = 0, MU_SQUARE_MASKED, MU_KL, MU_KL_MASKED, MU_IS, MU_NFORMS };
+enum { MU_SQUARE = 0, MU_SQUARE_MASKED, MU_KL, MU_KL_MASKED, MU_IS, MU_BETA, MU_NFORMS };
 constexpr MuForm kMuForms[MU_NFORMS] = { // (in the order of the enum)
     {CONV_FAM_PLAIN, CONV_FAM_PLAIN, EST_CONV, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
      2, {MU_X, MU_EST}, 2, MU_XT, 0, 1, false, true, false, CONV_FAM_MU_MASKED},
@@ -543,10 +552,15 @@ constexpr MuForm kMuForms[MU_NFORMS] = { // (in the order of the enum)
     // (P and Q from one conv; C3 contracts (Q', P'): the numerator second)
     {CONV_FAM_IS, CONV_FAM_IS, EST_IS_PQ, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
      2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, true, false, true, CONV_FAM_MU_MASKED},
+    // (the Itakura-Saito row with the beta family's epilogues and the power step)
+    {CONV_FAM_BETA, CONV_FAM_BETA, EST_BETA_PQ, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
+     2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, false, false, true, CONV_FAM_MU_MASKED, true},
 };
+// the element-wise step of the active form: 0 the plain quotient, 1 its square root, 2 its power mu_gamma (cmf_mu_step)
+static inline int mu_step_kind(const cmf_handle_s *h, const MuForm &f) { return (f.pow_update && h->mu_gamma != 1.f) ? 2 : f.sqrt_update ? 1 : 0; }
 static inline const MuForm &mu_form(const cmf_handle_s *h)
 {
-    return kMuForms[h->mu_div == CMF_DIV_IS ? MU_IS : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
+    return kMuForms[h->mu_div == CMF_DIV_BETA ? MU_BETA : h->mu_div == CMF_DIV_IS ? MU_IS : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
 }
 static inline float *mu_buf(const cmf_handle_s *h, MuBuf b) { return b ? h->*b : nullptr; }
 // What the MU entries read for data / "est is current".  reuse_est, the speculated C2 contraction and the deferred loss carry all
@@ -554,7 +568,7 @@ static inline float *mu_buf(const cmf_handle_s *h, MuBuf b) { return b ? h->*b :
 static inline const float *mu_X(const cmf_handle_s *h) { return mu_buf(h, mu_form(h).data); }
 static inline int mu_est_kind(const cmf_handle_s *h) { return mu_form(h).est_kind; }
 // the loss of the MU entries from the sum its loss conv leaves: norm(est - data) / norm(data), or D(data, est) / sum(data) under KL
-// (Itakura-Saito: data_sum holds N * T, the mean divergence per entry)
+// (Itakura-Saito and beta: data_sum holds N * T, the mean divergence per entry)
 static inline double mu_loss(const cmf_handle_s *h, double ss)
 {
     const MuForm &f = mu_form(h);
@@ -730,9 +744,14 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
     const CmfDims &d = h->d;
     if ((conv_mu_masked(MODE) || conv_kl_masked(MODE)) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
-    if (conv_is(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito conv without its second pair of buffers");
+    if (conv_pq(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito or beta conv without its second pair of buffers");
     p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (conv_data_transposed(MODE) ? h->XT : h->X); p.partial = h->partial;
-    p.out2 = !conv_is(MODE) ? nullptr : conv_transposed(MODE) ? h->est2T : h->est2; // (Q; out takes P)
+    p.out2 = !conv_pq(MODE) ? nullptr : conv_transposed(MODE) ? h->est2T : h->est2; // (Q; out takes P)
+    if (conv_beta(MODE)) {
+        const float *c = h->beta_consts;
+        p.beta_m1 = c[0]; p.beta_m2 = c[1]; p.beta = c[2]; p.beta_inv = c[3]; p.beta_inv_bb = c[4];
+        for (int k = 0; k < 6; ++k) p.beta_c[k] = c[5 + k];
+    }
     p.mask = conv_mask_transposed(MODE) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)

@@ -75,6 +75,9 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //   Itakura-Saito (20 .. 23), Q = 1 / e, P = (data * Q) * Q: ONE accumulator tile stores TWO arrays, P through p.out and Q through
 //     p.out2 ([t][n], or [n][t] from dataT); the summed terms are (r - 1) - log(r), r = data * Q.  Q = 1 / (0 + eps) is NOT 0 in the
 //     padding: columns n >= N are stored as exact 0 and add 0 by a SELECT on n < p.N (partly live and wholly dead 32-column blocks alike).
+//   beta-divergence (24 .. 27), lg = log2(e): the Itakura-Saito modes with Q = exp2((beta - 1) lg) and P = data * exp2((beta - 2) lg)
+//     (v_log_f32 / v_exp_f32, no powf), the same two stores and the same SELECT (eps^(beta - 1) is huge for beta < 1 and tiny but not 0
+//     above); the summed terms are e^beta phi(data / e) (cmf_beta_term).  The exponents and phi's constants come in p.beta_*.
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
@@ -88,8 +91,11 @@ struct ConvParams {
     int N;       // columns n >= N are padding: a 32-column MFMA block that lies wholly behind N is not computed (its sums are 0)
     int loss_abs; // PGD family: 1 = AbsoluteLoss (pgd.jl:41-47): store sign(est - data) [.* mask], sum |.|
                   // the masked loss-only modes (conv_loss_abs_is_complement): 1 = the sum runs over the entries with mask == 0
-    float *out2; // Itakura-Saito storing modes: the second array stored from the same accumulators (Q; out takes P), in the layout of out.
-                 // (Last, so that no other field moves.)
+    float *out2; // the storing modes of conv_pq (Itakura-Saito, beta): the second array stored from the same accumulators (Q; out takes
+                 // P), in the layout of out.  (Behind every older field, so that none moves.)
+    // the beta family (read by no other mode; behind out2 for the same reason): beta - 1, beta - 2, beta, 1 / beta, 1 / (beta (beta - 1))
+    // and c_1 .. c_6 of phi's series (cmf_beta_term)
+    float beta_m1 = 0.f, beta_m2 = 0.f, beta = 0.f, beta_inv = 0.f, beta_inv_bb = 0.f, beta_c[6] = {};
 };
 
 // agent-scope accesses (global_load / global_store ... sc1): the hand-off forms of MI355X_MICROARCH.md "inter-workgroup visibility"
@@ -139,6 +145,62 @@ __device__ __forceinline__ float cmf_is_term(float x, float q)
     const float d = r - 1.f;
     return d - logf(r);
 }
+// The beta-divergence epilogue of one element (modes 24 .. 27): lg = log2(e) once, then one v_exp_f32 per power (ocml's powf would cost
+// the 64 x 64 epilogue its registers).  Q = e^(beta - 1) where the column exists and exact 0 in the padding; P = x e^(beta - 2), exact 0
+// where x is (a select, not 0 * something).  The divergence term is NOT (x^beta + (beta - 1) e^beta - beta x e^(beta - 1)) / (beta (beta - 1)),
+// which cancels once the fit is close, but e^beta phi(r), r = x / e, d = r - 1:
+//     |d| < 1/8:  phi = d^2 / 2 (1 + c1 d + ... + c6 d^6)      (the binomial series of the next line, c_k in p.beta_c)
+//     otherwise:  phi = ((r^beta - 1) - beta d) / (beta (beta - 1))
+//     x = 0:      phi = 1 / beta
+// Contraction is off, as in cmf_is_term: modes 26 and 27 sum the same bits.  (The numpy restatement the tests hold the library against states the same composition.)
+__device__ __forceinline__ float cmf_log2(float x) { return __builtin_amdgcn_logf(x); }  // v_log_f32
+__device__ __forceinline__ float cmf_exp2(float x) { return __builtin_amdgcn_exp2f(x); } // v_exp_f32
+__device__ __forceinline__ float cmf_beta_q(float lg, bool live, const ConvParams &p)
+{
+#pragma clang fp contract(off)
+    return live ? cmf_exp2(p.beta_m1 * lg) : 0.f;
+}
+__device__ __forceinline__ float cmf_beta_p(float x, float lg, bool live, const ConvParams &p)
+{
+#pragma clang fp contract(off)
+    return (live && x > 0.f) ? x * cmf_exp2(p.beta_m2 * lg) : 0.f;
+}
+__device__ __forceinline__ float cmf_beta_term(float x, float e, float lg, const ConvParams &p)
+{
+#pragma clang fp contract(off)
+    const float yb = cmf_exp2(p.beta * lg);
+    const float r = x / e;
+    const float d = r - 1.f;
+    float poly = 0.f;
+#pragma unroll
+    for (int k = 5; k >= 0; --k) poly = (poly + p.beta_c[k]) * d;
+    const float near = ((0.5f * d) * d) * (1.f + poly);
+    const float rb = cmf_exp2(p.beta * cmf_log2(r > 0.f ? r : 1.f));
+    const float far = ((rb - 1.f) - p.beta * d) * p.beta_inv_bb;
+    const float phi = (x > 0.f) ? (fabsf(d) < 0.125f ? near : far) : p.beta_inv;
+    return yb * phi;
+}
+
+// One element of the two-array epilogues (conv_pq): what the accumulator v of a column that exists (live) or is padding gives.
+// Q() and P(x) are stored, term(x) summed.  BETA = false: Itakura-Saito; true: the beta-divergence.
+template <bool BETA> struct ConvPQ;
+template <> struct ConvPQ<false> {
+    float q;
+    __device__ __forceinline__ ConvPQ(float v, bool live, const ConvParams &) : q(cmf_is_q(v, live)) {}
+    __device__ __forceinline__ float Q() const { return q; }
+    __device__ __forceinline__ float P(float x) const { return cmf_is_p(x, q); }
+    __device__ __forceinline__ float term(float x) const { return cmf_is_term(x, q); }
+};
+template <> struct ConvPQ<true> {
+    const ConvParams &p;
+    float e, lg;
+    bool live;
+    __device__ __forceinline__ ConvPQ(float v, bool live_, const ConvParams &p_) : p(p_), e(v + CMF_EPS_F), lg(cmf_log2(v + CMF_EPS_F)), live(live_) {}
+    __device__ __forceinline__ float Q() const { return cmf_beta_q(lg, live, p); }
+    __device__ __forceinline__ float P(float x) const { return cmf_beta_p(x, lg, live, p); }
+    __device__ __forceinline__ float term(float x) const { return cmf_beta_term(x, e, lg, p); }
+};
+
 // wave sum on the DPP network (row shifts, then the two row broadcasts): the total lands in lane 63
 __device__ __forceinline__ float cmf_wave_sum63(float x)
 {
@@ -151,10 +213,10 @@ __device__ __forceinline__ float cmf_wave_sum63(float x)
     return x;
 }
 
-// conv_epilogue_ of the Itakura-Saito modes: the same descriptors and offsets, one 32 x 32 block at a time (a block's 16 data values
+// conv_epilogue_ of the two-array modes (conv_pq: Itakura-Saito and beta, the element's arithmetic in ConvPQ): the same descriptors and offsets, one 32 x 32 block at a time (a block's 16 data values
 // before its 32 stores: two stores per accumulator leave no room for a wider group), P through p.out and Q through p.out2.
 template <int MODE, int WAVES, bool PRE>
-__device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const ConvParams &p, int tw, int nw, int i, int h, int lane, int wave,
+__device__ __forceinline__ void conv_pq_epilogue_(f32x16 (&acc)[2][2], const ConvParams &p, int tw, int nw, int i, int h, int lane, int wave,
                                                   int tid, int pidx, const float (&pre)[2][2][16])
 {
     const int Np = p.Np, TP = p.TP;
@@ -183,12 +245,12 @@ __device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const Con
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int so = ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4;
-                    const float q = cmf_is_q(acc[gt][gn][r], live);
+                    const ConvPQ<conv_beta(MODE)> q(acc[gt][gn][r], live, p);
                     if (STORE) {
-                        cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
-                        cmf_bstore(q, ro2, voff, so);
+                        cmf_bstore(q.P(dv[r]), ro, voff, so);
+                        cmf_bstore(q.Q(), ro2, voff, so);
                     }
-                    if (LOSS) lsum += (live && gt * 32 + cmf_crow(r, h) < rows) ? cmf_is_term(dv[r], q) : 0.f;
+                    if (LOSS) lsum += (live && gt * 32 + cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
                 }
             }
         if (LOSS) {
@@ -203,7 +265,7 @@ __device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const Con
             }
         }
     } else {
-        // MODE 21: acc[ni][ti][r]: n = nw + ni*32 + crow(r,h), t = tw + ti*32 + i; p.data is dataT [Np][TP]
+        // MODES 21, 25: acc[ni][ti][r]: n = nw + ni*32 + crow(r,h), t = tw + ti*32 + i; p.data is dataT [Np][TP]
         const size_t origin = (size_t)nw * TP + p.PADL + tw;
         const size_t bytes = ((size_t)63 * TP + 64) * 4;
         const __amdgpu_buffer_rsrc_t ro = cmf_rsrc(p.out + origin, bytes);
@@ -222,18 +284,18 @@ __device__ __forceinline__ void conv_is_epilogue_(f32x16 (&acc)[2][2], const Con
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                        const float q = cmf_is_q(acc[ni][ti][r], nw + ni * 32 + cmf_crow(r, h) < p.N);
-                        cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
-                        cmf_bstore(q, ro2, voff, so);
+                        const ConvPQ<conv_beta(MODE)> q(acc[ni][ti][r], nw + ni * 32 + cmf_crow(r, h) < p.N, p);
+                        cmf_bstore(q.P(dv[r]), ro, voff, so);
+                        cmf_bstore(q.Q(), ro2, voff, so);
                     }
                 }
             }
     }
 }
 
-// conv_epilogue_block of the Itakura-Saito modes (one 32 x 32 block at (tb, nb))
+// conv_epilogue_block of the two-array modes (one 32 x 32 block at (tb, nb))
 template <int MODE>
-__device__ __forceinline__ void conv_is_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
+__device__ __forceinline__ void conv_pq_epilogue_block(const f32x16 &acc, const ConvParams &p, int tb, int nb, int i, int h, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
     constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
@@ -254,12 +316,12 @@ __device__ __forceinline__ void conv_is_epilogue_block(const f32x16 &acc, const 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
-            const float q = cmf_is_q(acc[r], live);
+            const ConvPQ<conv_beta(MODE)> q(acc[r], live, p);
             if (STORE) {
-                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
-                cmf_bstore(q, ro2, voff, so);
+                cmf_bstore(q.P(dv[r]), ro, voff, so);
+                cmf_bstore(q.Q(), ro2, voff, so);
             }
-            if (LOSS) lsum += (live && cmf_crow(r, h) < rows) ? cmf_is_term(dv[r], q) : 0.f;
+            if (LOSS) lsum += (live && cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
         }
         if (LOSS) {
             const float x = cmf_wave_sum63(lsum);
@@ -279,17 +341,17 @@ __device__ __forceinline__ void conv_is_epilogue_block(const f32x16 &acc, const 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
-                const float q = cmf_is_q(acc[r], nb + cmf_crow(r, h) < p.N);
-                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, so);
-                cmf_bstore(q, ro2, voff, so);
+                const ConvPQ<conv_beta(MODE)> q(acc[r], nb + cmf_crow(r, h) < p.N, p);
+                cmf_bstore(q.P(dv[r]), ro, voff, so);
+                cmf_bstore(q.Q(), ro2, voff, so);
             }
         }
     }
 }
 
-// conv16_epilogue of the Itakura-Saito modes (one 16 x 16 block; lane = 16*kq + j)
+// conv16_epilogue of the two-array modes (one 16 x 16 block; lane = 16*kq + j)
 template <int MODE>
-__device__ __forceinline__ void conv16_is_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
+__device__ __forceinline__ void conv16_pq_epilogue(const f32x4 &acc, const ConvParams &p, int tb, int nb, int j, int kq, int lane, int pidx)
 {
     const int Np = p.Np, TP = p.TP;
     constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
@@ -309,12 +371,12 @@ __device__ __forceinline__ void conv16_is_epilogue(const f32x4 &acc, const ConvP
         float lsum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float q = cmf_is_q(acc[r], live);
+            const ConvPQ<conv_beta(MODE)> q(acc[r], live, p);
             if (STORE) {
-                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, r * Np * 4);
-                cmf_bstore(q, ro2, voff, r * Np * 4);
+                cmf_bstore(q.P(dv[r]), ro, voff, r * Np * 4);
+                cmf_bstore(q.Q(), ro2, voff, r * Np * 4);
             }
-            if (LOSS) lsum += (live && 4 * kq + r < rows) ? cmf_is_term(dv[r], q) : 0.f;
+            if (LOSS) lsum += (live && 4 * kq + r < rows) ? q.term(dv[r]) : 0.f;
         }
         if (LOSS) {
             const float x = cmf_wave_sum63(lsum);
@@ -333,9 +395,9 @@ __device__ __forceinline__ void conv16_is_epilogue(const f32x4 &acc, const ConvP
             for (int r = 0; r < 4; ++r) dv[r] = cmf_bload(rd, voff, r * TP * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float q = cmf_is_q(acc[r], nb + 4 * kq + r < p.N);
-                cmf_bstore(cmf_is_p(dv[r], q), ro, voff, r * TP * 4);
-                cmf_bstore(q, ro2, voff, r * TP * 4);
+                const ConvPQ<conv_beta(MODE)> q(acc[r], nb + 4 * kq + r < p.N, p);
+                cmf_bstore(q.P(dv[r]), ro, voff, r * TP * 4);
+                cmf_bstore(q.Q(), ro2, voff, r * TP * 4);
             }
         }
     }
@@ -361,8 +423,8 @@ __device__ __forceinline__ void conv_epilogue_(f32x16 (&acc)[2][2], const ConvPa
     // wave-uniform origin of this wave's 64 x 64 sub-tile
     const int tw = __builtin_amdgcn_readfirstlane(t0 + wt * 64);
     const int nw = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
-    if constexpr (conv_is(MODE)) { // the Itakura-Saito modes: two stores per accumulator, an epilogue of their own
-        conv_is_epilogue_<MODE, WAVES, PRE>(acc, p, tw, nw, i, h, lane, wave, tid, pidx, pre);
+    if constexpr (conv_pq(MODE)) { // the Itakura-Saito and beta modes: two stores per accumulator, an epilogue of their own
+        conv_pq_epilogue_<MODE, WAVES, PRE>(acc, p, tw, nw, i, h, lane, wave, tid, pidx, pre);
         return;
     }
     if (!conv_transposed(MODE)) {
@@ -903,8 +965,8 @@ __device__ __forceinline__ void conv_epilogue_block(const f32x16 &acc, const Con
     constexpr bool MUM = conv_mu_masked(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = conv_kl(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     constexpr bool KLM = conv_kl_masked(MODE); // ... under the MU rule's mask: the term enters by a select
-    if constexpr (conv_is(MODE)) {
-        conv_is_epilogue_block<MODE>(acc, p, tb, nb, i, h, lane, pidx);
+    if constexpr (conv_pq(MODE)) {
+        conv_pq_epilogue_block<MODE>(acc, p, tb, nb, i, h, lane, pidx);
         return;
     }
     const bool abs_loss = conv_loss_abs_is_absolute_loss(MODE) && p.loss_abs; // wave-uniform; a quarter tile's 16-element epilogue takes the selects
@@ -1102,8 +1164,8 @@ __device__ __forceinline__ void conv16_epilogue(const f32x4 &acc, const ConvPara
     constexpr bool MUM = conv_mu_masked(MODE); // 0/1 mask of the MU rule: a select
     constexpr bool KL = conv_kl(MODE);         // the KL rule: data / (est + eps) stored, the divergence summed
     constexpr bool KLM = conv_kl_masked(MODE); // ... under the MU rule's mask: the term enters by a select
-    if constexpr (conv_is(MODE)) {
-        conv16_is_epilogue<MODE>(acc, p, tb, nb, j, kq, lane, pidx);
+    if constexpr (conv_pq(MODE)) {
+        conv16_pq_epilogue<MODE>(acc, p, tb, nb, j, kq, lane, pidx);
         return;
     }
     const bool abs_loss = conv_loss_abs_is_absolute_loss(MODE) && p.loss_abs;
@@ -1730,10 +1792,22 @@ __device__ __forceinline__ float cmf_mu_sqrt(float x, float num, float den, floa
     float y = x * sqrtf(num / d);
     return (y != y) ? y : fmaxf(CMF_EPS_F, y);
 }
-template <bool SQRT>
-__device__ __forceinline__ float cmf_mu_step(float x, float num, float den, float l1, float two_l2)
+// The beta-divergence step outside 1 <= beta <= 2 (the majorisation-minimisation exponent gamma = 1 / (2 - beta) or 1 / (beta - 1)):
+//   x <- max(eps, x * (num / (((den + l1) + (2*l2)*x) + eps))^gamma),  the power as exp2(gamma log2(.)) on v_log_f32 / v_exp_f32.
+// A quotient of 0 gives 0 and then the floor by a select (not through exp2(-inf)); a NaN passes through as in cmf_mu.
+__device__ __forceinline__ float cmf_mu_pow(float x, float num, float den, float l1, float two_l2, float gamma)
 {
-    return SQRT ? cmf_mu_sqrt(x, num, den, l1, two_l2) : cmf_mu(x, num, den, l1, two_l2);
+    float d = ((den + l1) + two_l2 * x) + CMF_EPS_F;
+    float q = num / d;
+    float y = (q > 0.f) ? x * cmf_exp2(gamma * cmf_log2(q)) : x * q;
+    return (y != y) ? y : fmaxf(CMF_EPS_F, y);
+}
+#define CMF_MU_POW_STEP(x, num, den, l1, two_l2) cmf_mu_pow(x, num, den, l1, two_l2, gamma)
+// STEP: 0 the plain quotient, 1 its square root, 2 its power gamma
+template <int STEP>
+__device__ __forceinline__ float cmf_mu_step(float x, float num, float den, float l1, float two_l2, float gamma)
+{
+    return STEP == 2 ? cmf_mu_pow(x, num, den, l1, two_l2, gamma) : STEP == 1 ? cmf_mu_sqrt(x, num, den, l1, two_l2) : cmf_mu(x, num, den, l1, two_l2);
 }
 
 // grid: (Np/64, KB, L), block 256.  num, den: [L][K32][Np] each
@@ -1741,11 +1815,12 @@ __device__ __forceinline__ float cmf_mu_step(float x, float num, float den, floa
 // [numW | denomW] all-reduce buffer of a sharded group -- to pinned host memory that the host has filled with a
 // sentinel pattern and polls, so the read-back costs neither a launch nor an event (see loss_reduce_kernel).
 // (w_update_sqrt_kernel, the sibling of the Itakura-Saito form, is this text with STEP = cmf_mu_sqrt: stated once as a macro, not as a
-// shared __device__ body, which moved w_update_kernel's registers (19 -> 16 VGPRs) in tools/kernel_resources.py's table)
-#define CMF_W_UPDATE_KERNEL(NAME, STEP)                                                                                                  \
+// shared __device__ body, which moved w_update_kernel's registers (19 -> 16 VGPRs) in tools/kernel_resources.py's table;
+// w_update_pow_kernel, the beta form's, has one more argument, gamma: EXTRA)
+#define CMF_W_UPDATE_KERNEL(NAME, STEP, EXTRA)                                                                                                  \
     static __global__ __launch_bounds__(256) void NAME(float *Wt, float *Wn, const float *num_p, const float *den_p,                     \
                                                        int N, int K, int L, int Np, int K32, float l1, float two_l2,                     \
-                                                       const float *tail_src, float *tail_dst, int tail_n)                               \
+                                                       const float *tail_src, float *tail_dst, int tail_n EXTRA)                         \
     {                                                                                                                                    \
         __shared__ float tile[32][65];                                                                                                   \
         const int tid = threadIdx.x;                                                                                                     \
@@ -1774,9 +1849,15 @@ __device__ __forceinline__ float cmf_mu_step(float x, float num, float den, floa
             }                                                                                                                            \
         }                                                                                                                                \
     }
-CMF_W_UPDATE_KERNEL(w_update_kernel, cmf_mu)
-CMF_W_UPDATE_KERNEL(w_update_sqrt_kernel, cmf_mu_sqrt)
+#define CMF_NO_EXTRA
+#define CMF_GAMMA_EXTRA , float gamma
+CMF_W_UPDATE_KERNEL(w_update_kernel, cmf_mu, CMF_NO_EXTRA)
+CMF_W_UPDATE_KERNEL(w_update_sqrt_kernel, cmf_mu_sqrt, CMF_NO_EXTRA)
+CMF_W_UPDATE_KERNEL(w_update_pow_kernel, CMF_MU_POW_STEP, CMF_GAMMA_EXTRA)
 #undef CMF_W_UPDATE_KERNEL
+#undef CMF_NO_EXTRA
+#undef CMF_GAMMA_EXTRA
+#undef CMF_MU_POW_STEP
 
 // grid: (ceil(Tl/8), KB), block 256.  slabs: [S][2][Tl][K32]
 // A workgroup owns 8 columns x 32 components = 64 float4 elements; its four 64-thread groups each sum every
@@ -1786,10 +1867,10 @@ CMF_W_UPDATE_KERNEL(w_update_sqrt_kernel, cmf_mu_sqrt)
 // num / den: Snum / Sden partial-sum slabs of [Tl][K32] floats, `num_stride` / `den_stride` floats apart (the two-source
 // transconv writes [S][2][Tl][K32]: num = slabs, den = slabs + Tl*K32, both strides 2*Tl*K32; the Gram form has the S1
 // slabs of the one-source launch for num and ONE array for den).
-template <bool SQRT>
+template <int STEP> // (cmf_mu_step; false and true name the plain and the square-root step)
 __device__ __forceinline__ void h_update_body(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
                                               const float *denp, size_t den_stride, int Sden,
-                                              int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
+                                              int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2, float gamma = 1.f)
 {
     __shared__ f32x4 red[3][64][2];
     __shared__ float tile[32][HUPD_T + 1];
@@ -1837,7 +1918,7 @@ __device__ __forceinline__ void h_update_body(float *H, float *Ht, const float *
         f32x4 hn = {0.f, 0.f, 0.f, 0.f};
         if (t < Tl && k < K) { // (the padding stays the zero it is)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) hn[c] = (k + c < K) ? cmf_mu_step<SQRT>(x[c], num[c], den[c], l1, two_l2) : 0.f;
+            for (int c = 0; c < 4; ++c) hn[c] = (k + c < K) ? cmf_mu_step<STEP>(x[c], num[c], den[c], l1, two_l2, gamma) : 0.f;
             *hp = hn;
         }
 #pragma unroll
@@ -1860,6 +1941,12 @@ static __global__ __launch_bounds__(256) void h_update_sqrt_kernel(float *H, flo
                                                              int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2)
 {
     h_update_body<true>(H, Ht, nump, num_stride, Snum, denp, den_stride, Sden, Tl, K, K32, PADL, TP, l1, two_l2);
+}
+static __global__ __launch_bounds__(256) void h_update_pow_kernel(float *H, float *Ht, const float *nump, size_t num_stride, int Snum,
+                                                            const float *denp, size_t den_stride, int Sden,
+                                                            int Tl, int K, int K32, int PADL, int TP, float l1, float two_l2, float gamma)
+{
+    h_update_body<2>(H, Ht, nump, num_stride, Snum, denp, den_stride, Sden, Tl, K, K32, PADL, TP, l1, two_l2, gamma);
 }
 
 // A thread's share of the sum of n per-tile loss sums (256 threads; element e goes to thread e % 256, accumulator (e / 256) % 8):

@@ -126,17 +126,44 @@ def rccl_version():
 # --------------------------------------------------------------------------------------
 # update rules (the plugin boundary: abstract type AbstractCFUpdate, alternating.jl:1-8)
 # --------------------------------------------------------------------------------------
-# CMF_DIV_SQUARE, CMF_DIV_KL, CMF_DIV_IS (include/cmf_hip.h)
-_DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1, ":itakura_saito": 2, "itakura_saito": 2}
+# CMF_DIV_SQUARE, CMF_DIV_KL, CMF_DIV_IS (include/cmf_hip.h); ":beta" is no kind of cmf_mu_set_divergence: it has an entry of its
+# own, cmf_mu_set_beta_divergence, and is numbered here only
+_DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1, ":itakura_saito": 2, "itakura_saito": 2, ":beta": 3, "beta": 3}
 _DIV_IS = 2
-_DIV_NAMES = {0: ":square", 1: ":kl", 2: ":itakura_saito"}
+_DIV_BETA = 3
+_DIV_NAMES = {0: ":square", 1: ":kl", 2: ":itakura_saito", 3: ":beta"}
+BETA_WINDOW = 0.01  # CMF_BETA_WINDOW (include/cmf_hip.h; profiles/mu_beta_precision.txt: window)
+BETA_MAX = 4.0      # CMF_BETA_MAX
 
 
 def _divergence_kind(kind):
     key = kind if isinstance(kind, str) else (":" + getattr(kind, "name", str(kind)))
     if key not in _DIVERGENCES:
-        raise ValueError(f"divergence must be ':square' or ':kl' (or ':itakura_saito', spelled out), got {kind!r}")
+        raise ValueError(f"divergence must be ':square' or ':kl' (or ':itakura_saito', spelled out, or ':beta' with beta=), got {kind!r}")
     return _DIVERGENCES[key]
+
+
+def _check_beta(kind_code, beta):
+    """The beta of divergence=":beta" as cmf_mu_set_beta_divergence accepts it (the library's wording), or None for the other kinds."""
+    if kind_code != _DIV_BETA:
+        if beta is not None:
+            raise ValueError("beta= goes with divergence=':beta' only")
+        return None
+    if beta is None:
+        raise ValueError("divergence=':beta' needs beta=")
+    b = float(beta)
+    w = BETA_WINDOW * (1.0 - 1e-9)  # (the window's edges are accepted)
+    if not math.isfinite(b):
+        raise ValueError("beta must be finite")
+    if b == 0.0 or b == 1.0:
+        raise ValueError(f"beta = {b:g} is CMF_DIV_IS (beta = 0) or CMF_DIV_KL (beta = 1): the beta formula is 0/0 there, use "
+                         "divergence=':itakura_saito' or ':kl'")
+    if b < 0.0 or b > BETA_MAX:
+        raise ValueError(f"beta must lie in (0, {BETA_MAX:g}], got {b!r}")
+    if b < w or abs(b - 1.0) < w:
+        raise ValueError(f"beta = {b!r} lies within {BETA_WINDOW:g} of 0 or 1, where the float32 loss loses its digits to the factor "
+                         f"1 / (beta (beta - 1)): use CMF_DIV_IS / CMF_DIV_KL, or a beta at least {BETA_WINDOW:g} away")
+    return b
 
 
 class AbstractCFUpdate:
@@ -319,7 +346,7 @@ class MultUpdate(AbstractCFUpdate):
         return r.value, d.value
 
     # -- the divergence the rule minimises (cmf_mu_set_divergence) ---------------------------
-    def set_divergence(self, kind):
+    def set_divergence(self, kind, beta=None):
         """``":kl"``: the multiplicative update of the generalised Kullback-Leibler divergence (Smaragdis' convolutive NMF), for counts
         and spectrogram magnitudes: R = data ./ (est + eps) takes the place of data in the numerators, the denominators are sums of H
         and of W, and the loss is D(data, est + eps) / sum(data).  Data must be finite and non-negative with a positive sum.
@@ -330,8 +357,16 @@ class MultUpdate(AbstractCFUpdate):
         power spectrograms: with Q = 1 ./ (est + eps) and P = (data .* Q) .* Q the numerators contract P, the denominators Q, the
         update takes the square root of their quotient, and the loss is the mean of (r - 1) - log(r), r = data ./ (est + eps), per
         entry.  Data must be finite and strictly positive (add a floor to the spectrogram).  The library option "is_div" is set
-        here; no mask, no Gram form, one GPU."""
+        here; no mask, no Gram form, one GPU.
+        ``":beta"`` with ``beta=``: the beta-divergence between those three points (cmf_mu_set_beta_divergence; beta = 0.5 for audio,
+        1 < beta < 2 the Tweedie range): Q = e.^(beta - 1), P = data .* e.^(beta - 2), e = est + eps, the update raises the quotient
+        to gamma(beta) (1 for 1 < beta <= 2), the loss is the mean beta-divergence per entry.  BETA_WINDOW <= beta <= BETA_MAX,
+        at least BETA_WINDOW away from 1; data finite and non-negative; no mask, no Gram form, one GPU."""
         code = _divergence_kind(kind)
+        beta = _check_beta(code, beta)
+        if code == _DIV_BETA:
+            check(self._lib.cmf_mu_set_beta_divergence(self._h, beta))
+            return
         if code == _DIV_IS:
             self.set_option("is_div", 1)
         check(self._lib.cmf_mu_set_divergence(self._h, code))
@@ -1163,7 +1198,7 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
              "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
              "mask",  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
-             "divergence"}  # alg=:mult: ":square" (default), ":kl" or ":itakura_saito" (MultUpdate.set_divergence)
+             "divergence", "beta"}  # alg=:mult: ":square" (default), ":kl", ":itakura_saito" or ":beta" with beta= (MultUpdate.set_divergence)
 
 
 def init_rand(data, L, K, seed=None, device=None):
@@ -1218,7 +1253,18 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if not np.isin(mask, (0.0, 1.0)).all():
             raise ValueError("mask must hold 0 and 1 only (1 = observed)")
     divergence = _divergence_kind(kw.get("divergence", ":square"))
-    if divergence == _DIV_IS:
+    beta = _check_beta(divergence, kw.get("beta", None))
+    if divergence == _DIV_BETA:
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("divergence=':beta' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
+                                      "fits minimise the squared error (PGD also the absolute error)")
+        if mask is not None:
+            raise NotImplementedError("divergence=':beta' is not available with mask=: the beta-divergence form of the MU rule "
+                                      "has no masked form")
+        if devices is not None:
+            raise NotImplementedError("divergence=':beta' is not available with devices=[...]: the beta-divergence form of the "
+                                      "MU rule runs on one GPU")
+    elif divergence == _DIV_IS:
         if rule_type is not MultUpdate:
             raise NotImplementedError("divergence=':itakura_saito' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
                                       "fits minimise the squared error (PGD also the absolute error)")
@@ -1272,9 +1318,9 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if mask is not None:
             rule.set_mask(mask)  # (before the loop: loss_hist[0] is the masked loss too)
         if divergence:
-            rule.set_divergence(_DIV_NAMES[divergence])  # (before the loop: loss_hist[0] is the divergence too)
+            rule.set_divergence(_DIV_NAMES[divergence], beta=beta)  # (before the loop: loss_hist[0] is the divergence too)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
-        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence")}
+        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence", "beta")}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
     finally:
         if hasattr(rule, "close"):
@@ -1302,13 +1348,15 @@ def evaluate_mse(r, device=None):
     return compute_loss(r.data, r.W, r.H, device=device)
 
 
-def evaluate_divergence(r, kind=":kl", device=None):
+def evaluate_divergence(r, kind=":kl", device=None, beta=None):
     """The loss of the fitted model ``r`` under ``kind`` (cmf_compute_loss): for ``":kl"`` D(data, est + eps) / sum(data), what
     ``fit_cnmf(divergence=":kl")`` records in ``loss_hist``; for ``":itakura_saito"`` the mean Itakura-Saito divergence per entry
-    (what ``fit_cnmf(divergence=":itakura_saito")`` records); for ``":square"`` evaluate_mse's value."""
+    (what ``fit_cnmf(divergence=":itakura_saito")`` records); for ``":beta"`` with ``beta=`` the mean beta-divergence per entry;
+    for ``":square"`` evaluate_mse's value."""
+    beta = _check_beta(_divergence_kind(kind), beta)
     rule = MultUpdate(r.data, r.W, r.H, device=device)
     try:
-        rule.set_divergence(kind)
+        rule.set_divergence(kind, beta=beta)
         return rule.compute_loss()
     finally:
         rule.close()
@@ -1368,6 +1416,8 @@ def evaluate_heldout(r, mask, device=None, divergence=":square"):
     ``divergence=":kl"``: D / sum(data) over the same two sets of entries, D the sum of the divergence terms there (no square
     root): what ``fit_cnmf(divergence=":kl", mask=...)`` records in ``loss_hist``, and its held-out counterpart."""
     kl = _divergence_kind(divergence)
+    if kl == _DIV_BETA:
+        raise NotImplementedError("divergence=':beta' has no held-out score: the beta-divergence form of the MU rule has no masked form")
     if kl == _DIV_IS:
         raise NotImplementedError("divergence=':itakura_saito' has no held-out score: the Itakura-Saito form of the MU rule has no "
                                   "masked form")
@@ -1412,6 +1462,9 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
     by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
     combinations and the scores gathered on all ranks."""
+    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_BETA:
+        raise NotImplementedError("cross_validate(divergence=':beta') is not available: the beta-divergence form of the MU rule "
+                                  "has no masked form, so nothing can be held out")
     if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_IS:
         raise NotImplementedError("cross_validate(divergence=':itakura_saito') is not available: the Itakura-Saito form of the MU rule "
                                   "has no masked form, so nothing can be held out")

@@ -193,6 +193,9 @@ function set_divergence!(rule::HIPMultUpdate, kind::Symbol)
                 kind === :kl ? CMF_DIV_KL : kind === :itakura_saito ? CMF_DIV_IS : CMF_DIV_SQUARE))
     return rule
 end
+# set_beta_divergence!(rule, beta): the beta-divergence between those three points (cmf_mu_set_beta_divergence): Q = e.^(beta - 1),
+# P = data .* e.^(beta - 2), the step raised to gamma(beta); 0.01 <= beta <= 4, at least 0.01 away from 1; data finite and non-negative.
+set_beta_divergence!(rule::HIPMultUpdate, beta::Real) = check(ccall((:cmf_mu_set_beta_divergence, LIBCMF), Cint, (Ptr{Cvoid}, Float64), rule.handle, Float64(beta)))
 
 # update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
 function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)

@@ -477,6 +477,32 @@ int cmf_mu_set_divergence(cmf_handle h, int kind);
  * either order: the form has no masked form); the HALS and PGD entries answer CMF_ERR_STATE while it is installed.  Switching
  * between the three kinds on one handle voids est, the speculated contraction and a deferred loss each time. */
 #define CMF_DIV_IS 2
+/* The beta-divergence between those three points (beta_loss=<float> elsewhere): beta = 0.5 is the usual compromise between
+ * Itakura-Saito and KL for audio, 1 < beta < 2 the Tweedie compound-Poisson range, beta = 2 the squared error (halved).  With e as
+ * above, Q = e.^(beta - 1) and P = data .* e.^(beta - 2), the MU entries run
+ *   update_motifs!:        numW[:, :, l] = shift_cols(H, l) * P[:, 1+l:T]';  denomW[:, :, l] = shift_cols(H, l) * Q[:, 1+l:T]'
+ *                          (mult.jl:32-33 with data -> P, est -> Q);
+ *                          W .*= (numW ./ (denomW + l1W + 2 l2W W + eps)).^gamma;  W = max(eps, W)      (mult.jl:37-38)
+ *   update_feature_maps!:  P, Q from the new W;  numH = tensor_transconv(W, P);  denomH = tensor_transconv(W, Q)  (mult.jl:47-48);
+ *                          the same update of H (mult.jl:51-52)
+ * with the majorisation-minimisation exponent gamma = 1 / (2 - beta) for beta < 1, 1 for 1 < beta <= 2 (the element-wise kernels of
+ * the squared-error rule, untouched) and 1 / (beta - 1) for beta > 2 (Fevotte & Idier 2011): with l1 = l2 = 0 the loss does not
+ * increase.  LOSS: D / (N T), D = sum over entries of d(x | e) = (x^beta + (beta - 1) e^beta - beta x e^(beta - 1)) / (beta (beta - 1))
+ * with e from the new H: the mean divergence per entry, like CMF_DIV_IS (summed in a form that does not cancel: DESIGN.md 6a-beta).
+ * ACCEPTED: CMF_BETA_WINDOW <= beta <= CMF_BETA_MAX with |beta - 1| >= CMF_BETA_WINDOW.  beta = 0 and beta = 1 are CMF_DIV_IS and
+ * CMF_DIV_KL (the formula is 0/0 there; the text says so); beta < 0 takes e^(beta - 2) out of fp32; close to 0 and to 1 the factor
+ * 1 / (beta (beta - 1)) takes the digits of the fp32 loss (profiles/mu_beta_precision.txt has the window); above 4, x^beta leaves
+ * fp32 for entries of ordinary size.  All of these and a NaN: CMF_ERR_ARG, the handle as it was.
+ * Data must be finite and non-negative (an exact zero is legal: its term is e^beta / beta): checked in one pass when the form is
+ * installed, CMF_ERR_ARG with a text that starts "the beta-divergence needs".  Calling it again with another beta changes the
+ * exponent and voids est.  cmf_mu_set_divergence(h, CMF_DIV_SQUARE / CMF_DIV_KL / CMF_DIV_IS) leaves the form (kind 3 is not a
+ * kind: CMF_ERR_ARG); CMF_DIV_SQUARE restores the plain rule launch for launch.  Refusals as for CMF_DIV_IS: CMF_ERR_UNSUPPORTED on
+ * group handles, with the Gram forms and together with cmf_mu_set_mask (in either order); the HALS and PGD entries answer
+ * CMF_ERR_STATE while it is installed.  The few-component fusions are not taken, so results do not depend on "small_k_fuse",
+ * "speculate" or "reuse_est". */
+#define CMF_BETA_WINDOW 0.01
+#define CMF_BETA_MAX 4.0
+int cmf_mu_set_beta_divergence(cmf_handle h, double beta);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
