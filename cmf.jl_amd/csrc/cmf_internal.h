@@ -137,7 +137,7 @@ struct RoctxRange {
 // hxt_kernel<5> with two sources and tail rows adds one to each of "hxt_kernel<5>", "hxt_kernel:nsrc2" and "hxt_kernel:tail"), so
 // that a test can reach every name with a handful of shapes.  tests/test_exact_parity.py expects exactly this list.
 enum { LA_CONV = 0, LA_CONV2, LA_CONV3_WHOLE, LA_CONV3_WHOLE_P4, LA_CONV3_WHOLE_P16, LA_CONV3_P4, LA_CONV3_P16,
-       LA_CONV_SMALL, /* + 6: NKP 1, 2, 3, 4, 6, 8 */ LA_CONV_SMALL_Q = LA_CONV_SMALL + 6, LA_CONV_SMALL_PRE,
+       LA_CONV_SMALL, /* + 6: NKP 1, 2, 3, 4, 6, 8 */ LA_CONV_SMALL_Q = LA_CONV_SMALL + 6, LA_CONV_SMALL_PRE, LA_CONV_SMALL_WHOLE,
        LA_HXT, /* + 7: kHxtLP */ LA_HXT_NSRC1 = LA_HXT + 7, LA_HXT_NSRC2, LA_HXT_TAIL, LA_HXT_NO_TAIL,
        LA_TC, /* + 8: LT 4 .. 32 */ LA_TC_FRONT = LA_TC + 8, LA_TC_XCD,
        LA_HXT_SMALL, /* + 10: MBW 1 .. 10 */ LA_HXT_SMALL_RV = LA_HXT_SMALL + 10, /* + 3 */
@@ -148,7 +148,7 @@ enum { LA_CONV = 0, LA_CONV2, LA_CONV3_WHOLE, LA_CONV3_WHOLE_P4, LA_CONV3_WHOLE_
 static const char *const kLaunchNames[] = {
     "conv_kernel", "conv2_kernel", "conv3_kernel:whole", "conv3_kernel:whole+4", "conv3_kernel:whole+16", "conv3_kernel:pieces4", "conv3_kernel:pieces16",
     "conv_small_kernel<1>", "conv_small_kernel<2>", "conv_small_kernel<3>", "conv_small_kernel<4>", "conv_small_kernel<6>", "conv_small_kernel<8>",
-    "conv_small_kernel:quarter", "conv_small_kernel:pre",
+    "conv_small_kernel:quarter", "conv_small_kernel:pre", "conv_small_kernel:whole",
     "hxt_kernel<1>", "hxt_kernel<2>", "hxt_kernel<3>", "hxt_kernel<4>", "hxt_kernel<5>", "hxt_kernel<6>", "hxt_kernel<8>",
     "hxt_kernel:nsrc1", "hxt_kernel:nsrc2", "hxt_kernel:tail", "hxt_kernel:no_tail",
     "transconv_kernel<4>", "transconv_kernel<8>", "transconv_kernel<12>", "transconv_kernel<16>", "transconv_kernel<20>", "transconv_kernel<24>",
@@ -778,6 +778,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
         h->launches[LA_CONV_SMALL + (nkp <= 4 ? std::max(nkp, 1) - 1 : nkp <= 6 ? 4 : 5)] += 1;
         if (cutq > 0) h->launches[LA_CONV_SMALL_Q] += 1;
         if (pre) h->launches[LA_CONV_SMALL_PRE] += 1;
+        if (n_full > 0) h->launches[LA_CONV_SMALL_WHOLE] += 1; // (whole tiles in front of the quarter pieces, or alone)
         h->conv_partials = (int)grid.x;
         KCHK("conv_small_kernel");
         return CMF_OK;

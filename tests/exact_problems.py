@@ -12,6 +12,9 @@ Two families, so that the factor being updated is dense and each of its entries 
   both: X in {0 ... 40}.
 Dropping or doubling any time row, column, lag or component block then moves some num or den by at least 1, and
 preconditions() bounds every num / den by 2^20, so such an error is at least 8 ulp of fp32.
+
+The shape table SHAPES is shared with tests/test_gpu_divergence_paths.py, which holds the divergence forms of the rule to their fp64
+restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below).
 """
 import numpy as np
 
@@ -45,6 +48,12 @@ def components_of_nl(N, L, K, seed=0):
     return (_hash(n, l, salt=seed * 4 + 2) % np.uint64(K)).astype(np.int64)
 
 
+def _data_hash(N, T, seed=0):
+    """The hash X is drawn from, as an (N, T) array of uint64."""
+    nn, tt = np.meshgrid(np.arange(N), np.arange(T), indexing="ij")
+    return _hash(nn, tt, salt=seed * 4)
+
+
 def make_problem(N, T, K, L, family, seed=0):
     """(W (K, N, L), H (K, T), X (N, T)) in float64, Fortran order, integer-valued (family "W" or "H": see the module doc)."""
     k, n, l = np.meshgrid(np.arange(K), np.arange(N), np.arange(L), indexing="ij")
@@ -58,8 +67,7 @@ def make_problem(N, T, K, L, family, seed=0):
         W = (k == components_of_nl(N, L, K, seed)[None]).astype(np.float64)
     else:
         raise ValueError(family)
-    nn, tt = np.meshgrid(np.arange(N), np.arange(T), indexing="ij")
-    X = (_hash(nn, tt, salt=seed * 4) % np.uint64(XMAX + 1)).astype(np.float64)
+    X = (_data_hash(N, T, seed) % np.uint64(XMAX + 1)).astype(np.float64)
     return np.asfortranarray(W), np.asfortranarray(H), np.asfortranarray(X)
 
 
@@ -108,11 +116,12 @@ def first_bad(mask, names):
 
 
 # The launch paths of cmf_get_counter "launches:<path>" (csrc/cmf_internal.h kLaunchNames, in its order): the coverage test of
-# tests/test_exact_parity.py expects every one reached, and tests/test_exact_problems.py keeps this list equal to the C++ table.
+# tests/test_exact_parity.py expects every one reached (tests/test_gpu_divergence_paths.py: every one a divergence form can reach), and tests/test_exact_problems.py keeps this list equal to the C++ table.
 LAUNCH_PATHS = [
     "conv_kernel", "conv2_kernel", "conv3_kernel:whole", "conv3_kernel:whole+4", "conv3_kernel:whole+16", "conv3_kernel:pieces4",
     "conv3_kernel:pieces16", "conv_small_kernel<1>", "conv_small_kernel<2>", "conv_small_kernel<3>", "conv_small_kernel<4>",
-    "conv_small_kernel<6>", "conv_small_kernel<8>", "conv_small_kernel:quarter", "conv_small_kernel:pre", "hxt_kernel<1>",
+    "conv_small_kernel<6>", "conv_small_kernel<8>", "conv_small_kernel:quarter", "conv_small_kernel:pre", "conv_small_kernel:whole",
+    "hxt_kernel<1>",
     "hxt_kernel<2>", "hxt_kernel<3>", "hxt_kernel<4>", "hxt_kernel<5>", "hxt_kernel<6>", "hxt_kernel<8>", "hxt_kernel:nsrc1",
     "hxt_kernel:nsrc2", "hxt_kernel:tail", "hxt_kernel:no_tail", "transconv_kernel<4>", "transconv_kernel<8>",
     "transconv_kernel<12>", "transconv_kernel<16>", "transconv_kernel<20>", "transconv_kernel<24>", "transconv_kernel<28>",
@@ -147,6 +156,19 @@ def hxt_lp(L):
 
 def transconv_lt(L):
     return rup(L, 4) if L <= 32 else 32
+
+
+def conv3_cut(N, T, conv_split=1, n_cu=N_CU):
+    """(whole tiles, cut tiles, pieces per cut tile) of a conv3_kernel launch over T columns (cmf_internal.h conv_tail_cut)."""
+    tiles, slots = rup(N, 128) // 64 * ((T + 63) // 64), 12 * n_cu
+    rem, cut = tiles % slots, 0
+    if conv_split:
+        if 0 < rem <= 3 * n_cu:
+            cut = rem
+        if tiles // slots >= 4:
+            cut += 3 * n_cu
+        cut = min(cut, tiles)
+    return tiles - cut, cut, 16 if (0 < cut < n_cu and conv_split != 4) else 4
 
 
 def conv3_form(N, T, conv_split=1, n_cu=N_CU):
@@ -194,3 +216,257 @@ def small_k_plan(N, T, K, L, n_cu=N_CU):
     rps = (rounds + ns - 1) // ns
     NS = (rounds + rps - 1) // rps
     return MBW, RV, MBW3, RV3, NS, (K + 1) // 2
+
+
+# ---- the shape table of the two GPU files (tests/test_exact_parity.py, tests/test_gpu_divergence_paths.py) ------------------
+GROUPS = [dict(devices=[0] * R, halo_in_allreduce=hal) for R in (2, 3, 8) for hal in (0, 1)]
+CONV32 = [dict(), dict(conv_kernel=2), dict(conv_kernel=3), dict(conv_split=0), dict(conv_split=4)]
+FULL32 = CONV32 + [dict(gram=1), dict(gram=2), dict(reuse_est=0)] + GROUPS
+GENERAL = [dict(), dict(conv_split=0), dict(gram=1), dict(gram=2), dict(reuse_est=0), dict(devices=[0] * 2), dict(devices=[0] * 3, gram=1)]
+SMALL = ([dict(), dict(small_k=0), dict(reuse_est=0), dict(gram=1)] + [dict(small_k=s, small_k_fuse=f) for s in (1, 2) for f in (0, 1, 2)]
+         + [dict(devices=[0] * 2), dict(devices=[0] * 3, small_k=2, small_k_fuse=2)])
+
+# (N, T, K, L, configurations, why)
+SHAPES = [
+    # conv3_kernel grid forms (K = 32, L = 20)
+    (130, 700, 32, 20, FULL32, "conv3 pieces only, 16 pieces (44 tiles)"),
+    (1001, 2500, 32, 20, CONV32 + [dict(gram=1)], "conv3 pieces only, 4 pieces (640 tiles)"),
+    (2000, 3000, 32, 20, CONV32 + [dict(gram=1), dict(devices=[0] * 2, halo_in_allreduce=1)], "whole tiles only (1504 tiles)"),
+    (2000, 6250, 32, 20, CONV32, "whole + 16 pieces (3136 tiles: the T/8 shard), hxt tail rows"),
+    (2000, 6720, 32, 20, CONV32, "whole + 4 pieces (3360 tiles)"),
+    # hxt_kernel<LP> / transconv_kernel<LT> instances on the general kernels (K > 16, not a multiple of 32: conv_kernel)
+    (70, 600, 20, 2, GENERAL, "LP 1, LT 4"),
+    (70, 600, 20, 4, GENERAL, "LP 2, LT 4"),
+    (70, 600, 20, 6, GENERAL, "LP 3, LT 8"),
+    (70, 600, 20, 8, GENERAL, "LP 4, LT 8"),
+    (70, 600, 20, 10, GENERAL, "LP 5, LT 12"),
+    (70, 600, 20, 12, GENERAL, "LP 6, LT 12"),
+    (70, 600, 20, 16, GENERAL, "LP 8, LT 16"),
+    (70, 600, 20, 22, GENERAL, "LP 1, LT 24"),
+    (70, 600, 20, 26, GENERAL, "LP 1, LT 28"),
+    (70, 600, 20, 31, GENERAL, "LP 8, LT 32"),
+    (70, 600, 20, 40, GENERAL, "LP 5, LT 32 (L > 32)"),
+    (200, 1500, 32, 33, [dict(), dict(conv_split=0)], "LP 1 at L = 33, K = 32"),
+    (40, 40, 20, 16, GENERAL, "a recording shorter than one Gram tile past the lag window: gram_h_kernel"),
+    (30, 24, 32, 12, [dict(), dict(gram=1)], "T shorter than 2 L"),
+    # few components (K <= 16): C2 m blocks 1 .. 10 and 1 .. 3 + VALU rows, C3 1 .. 6 and 1 .. 3 + VALU rows, conv k pairs 1 .. 8
+    (90, 610, 5, 7, SMALL, "C2 / C3 1 block + VALU rows"),
+    (31, 420, 2, 33, SMALL, "C2 / C3 2 blocks + VALU rows, 1 k pair"),
+    (250, 1500, 5, 20, SMALL, "C2 / C3 3 blocks + VALU rows, C3 in 4 pieces"),
+    (48, 300, 4, 8, SMALL, "C2 / C3 1 block, 2 k pairs"),
+    (70, 257, 5, 10, SMALL, "C2 / C3 2 blocks, 3 k pairs"),
+    (300, 260, 13, 7, SMALL, "C2 / C3 3 blocks, 7 k pairs, C3 in 4 pieces"),
+    (10, 64, 8, 16, SMALL, "C2 / C3 4 blocks, 4 k pairs"),
+    (33, 400, 7, 19, SMALL, "C2 / C3 5 blocks"),
+    (65, 520, 11, 12, SMALL, "C2 5 blocks, 6 k pairs"),
+    (60, 400, 8, 22, SMALL, "C2 6 blocks"),
+    (60, 400, 10, 20, SMALL, "C2 7 blocks"),
+    (17, 150, 16, 64, SMALL, "C2 8 blocks, C3 6 blocks, L = 64"),
+    (60, 400, 14, 20, SMALL, "C2 9 blocks"),
+    (130, 700, 16, 20, SMALL, "C2 10 blocks, 8 k pairs, C3 in 2 pieces"),
+    # whole few-component tiles: 16 x 65 = 1040 tiles on 1024 SIMDs, 1024 whole tiles and a tail of 16 in quarter pieces
+    # (K = 8, L = 10 and not K = 5, L = 20: N L / K = 1250 terms per sum of the H half, as on the K = 32 rows above; with 4000 one term
+    #  of a divergence form's sums is no longer 4 element-wise bars of its element -- exact_problems.sensitivity)
+    (1000, 4100, 8, 10, [dict(), dict(small_k=0), dict(reuse_est=0), dict(conv_split=0), dict(small_k=2, small_k_fuse=2)],
+     "whole few-component tiles + quarter-piece tail, preloaded data tile"),
+]
+
+
+def conv_small_form(N, T, conv_split=1, n_cu=N_CU):
+    """(whole tiles, quarter-cut tiles) of a few-component conv launch over T columns (cmf_internal.h launch_conv)."""
+    tiles, per_round = rup(N, 128) // 64 * ((T + 63) // 64), 4 * n_cu
+    rem = tiles % per_round
+    cut = rem if (conv_split and tiles >= per_round and 0 < rem <= per_round // 4) else 0
+    if conv_split and tiles < per_round:
+        cut = tiles
+    return tiles - cut, cut
+
+
+# ---- the divergence forms of the MU rule on these problems (tests/test_gpu_divergence_paths.py) ------------------------------
+# est = tensor_conv(W, H) is a small integer, exact in fp32 on every conv path, so R, P and Q are element-wise functions of exact
+# operands: every conv tile form must store the same bits.  The contractions that follow sum POSITIVE terms of comparable size, so
+# the updated factor is compared with the fp64 restatement per element at a relative bar near fp32 rounding
+# (profiles/mu_divergence_elementwise.txt, tools/mu_divergence_elementwise.py), far below what one missing term moves (sensitivity).
+DIV_XMIN, DIV_XMAX = 16, 31  # strictly positive and narrow: the terms of one sum are comparable
+EPS = float(np.finfo(np.float64).eps)
+# form -> (divergence kind, beta, masked, accepts zeros, relative data); the names of the `bar` lines of
+# profiles/mu_divergence_elementwise.txt.  Relative data (make_divergence_problem): at the left edge of a recording est counts up from
+# 1 to its bulk value near 1.5 L, and P = data e^(beta - 2) of the forms with beta < 1 (Itakura-Saito: beta = 0) then spreads over
+# L^2 (L^1.5) inside one sum of the H half: a bulk term of the first columns' numerators is below the bar, whatever range data has.
+# With data / est in the narrow range instead, P spreads like Q does and every row meets the condition sensitivity >= 4 bars.
+FORMS = {"kl": (":kl", None, False, True, False), "kl_mask": (":kl", None, True, True, False),
+         "is": (":itakura_saito", None, False, False, True), "beta050": (":beta", 0.5, False, True, True),
+         "beta150": (":beta", 1.5, False, True, False)}
+
+
+def make_divergence_problem(N, T, K, L, family, zeros=False, seed=0, relative=False):
+    """(W, H, X, mask): W and H of make_problem, X in {16 ... 31} from the hash X of make_problem comes from (zeros: about one entry in
+    eight exactly 0, chosen by other bits of it), and a 0/1 mask in blocks of 1 x 8 entries (a quarter held out) for the masked form.
+    relative: X is that value times est / 16, est = tensor_conv(W, H) -- a multiple of 1/16 below 2^12, exact in fp32, with data / est
+    in [1, 2) (the forms FORMS marks)."""
+    W, H, _ = make_problem(N, T, K, L, family, seed)
+    h = _data_hash(N, T, seed)
+    X = (DIV_XMIN + h % np.uint64(DIV_XMAX - DIV_XMIN + 1)).astype(np.float64)
+    if relative:
+        import kl_mu_restatement as kr
+
+        X *= kr.tensor_conv(W, H) / DIV_XMIN
+    if zeros:
+        X[(h >> np.uint64(20)) % np.uint64(8) == 0] = 0.0
+    nn, tb = np.meshgrid(np.arange(N), np.arange(T) // 8, indexing="ij")
+    mask = ((_hash(nn, tb, salt=seed * 4 + 5) >> np.uint64(9)) % np.uint64(4) != 0).astype(np.float64)
+    return W, H, np.asfortranarray(X), np.asfortranarray(mask)
+
+
+def step_exponent(form):
+    """The exponent the element-wise step raises num / den to."""
+    kind, beta = FORMS[form][:2]
+    return 0.5 if kind == ":itakura_saito" else (1.0 / (2.0 - beta) if beta < 1 else 1.0 if beta <= 2 else 1.0 / (beta - 1.0)) if beta else 1.0
+
+
+def divergence_sources(form, X, mask, W, H, cdtype=np.float64, edtype=np.float64):
+    """(P, Q) in fp64: the array the numerators contract and the one the denominators contract (None: plain KL, whose denominators
+    are sums of the other factor), formed by the form's restatement."""
+    import beta_mu_restatement as br
+    import is_mu_restatement as ir
+    import kl_mu_restatement as kr
+    import masked_kl_mu_restatement as mk
+
+    kind, beta, masked = FORMS[form][:3]
+    if kind == ":kl":
+        return (mk.ratio(mk.MaskedKL(X, mask), W, H, cdtype, edtype), mask) if masked else (kr.ratio(X, W, H, cdtype, edtype), None)
+    if kind == ":itakura_saito":
+        return ir.pq(X, W, H, cdtype, edtype)
+    return br.pq(X, W, H, beta, cdtype, edtype)
+
+
+def divergence_loss(form, X, mask, W, H, cdtype=np.float64, edtype=np.float64):
+    """The loss compute_loss() reports under the form, by its restatement."""
+    import beta_mu_restatement as br
+    import is_mu_restatement as ir
+    import kl_mu_restatement as kr
+    import masked_kl_mu_restatement as mk
+
+    kind, beta, masked = FORMS[form][:3]
+    if kind == ":kl":
+        return mk.masked_kl_loss(mk.MaskedKL(X, mask), W, H, cdtype, edtype) if masked else kr.kl_loss(X, W, H, cdtype, edtype)
+    if kind == ":itakura_saito":
+        return ir.is_loss(X, W, H, cdtype, edtype)
+    return br.beta_loss(X, W, H, beta, cdtype, edtype)
+
+
+def divergence_half(form, family, X, mask, W, H, cdtype=np.float64, edtype=np.float64, corrupt=None):
+    """One update_motifs! (family "W") or update_feature_maps! (family "H") of the form from (W, H), the restatement's operations
+    with its intermediate arrays kept: a dict of P, Q (divergence_sources), num, den (the contractions; for plain KL the sums),
+    den_total = ((den + l1) + 2 l2 x) + eps, new (the updated factor) and, family "H", loss (after the update), with L1 and L2 as
+    regularisers.  tests/test_exact_problems.py holds it equal to the restatements' own update functions bit for bit.
+    corrupt(stage, arrays): called with "sources" after P and Q exist and with "sums" after num and den do, to damage them in
+    place (the mutation tests)."""
+    import kl_mu_restatement as kr
+
+    K, N, L = W.shape
+    T = H.shape[1]
+    P, Q = divergence_sources(form, X, mask, W, H, cdtype, edtype)
+    a = dict(P=P, Q=Q, W=W, H=H, family=family)
+    if corrupt:
+        corrupt("sources", a)
+    if family == "W":
+        a["num"] = kr.hxt(H, a["P"], L, cdtype)
+        a["den"] = kr.denom_W(H, N, L) if a["Q"] is None else kr.hxt(H, a["Q"], L, cdtype)
+        x = W
+    else:
+        a["num"] = kr.tensor_transconv(W, a["P"], cdtype)
+        a["den"] = kr.denom_H(W, T) if a["Q"] is None else kr.tensor_transconv(W, a["Q"], cdtype)
+        x = H
+    if corrupt:
+        corrupt("sums", a)
+    a["den_total"] = ((a["den"] + L1) + (2.0 * L2) * x) + EPS
+    q = a["num"] / a["den_total"]
+    g = step_exponent(form)
+    a["new"] = np.maximum(x * (np.sqrt(q) if g == 0.5 else q if g == 1.0 else q ** g), EPS)
+    if family == "H":
+        a["loss"] = divergence_loss(form, X, mask, W, a["new"], cdtype, edtype)
+    return a
+
+
+def _min_positive_terms(family, src, W, H):
+    """Per element of the updated factor, the smallest POSITIVE term of its contraction with src (inf where it has none).  On these
+    problems the factor that is not updated holds one unit entry per column / per (n, l): the terms are entries of src."""
+    K, N, L = W.shape
+    T = H.shape[1]
+    if src is None:  # (plain KL: the denominator sums the unit entries themselves)
+        return np.ones((K, N, L) if family == "W" else (K, T))
+    s = np.where(src > 0, src, np.inf)
+    if family == "W":  # num[k, n, l] = sum over the columns t of component k, t + l < T, of src[n, t + l]
+        comp = np.argmax(H, axis=0)
+        m = np.full((K, N, L), np.inf)
+        for k in range(K):
+            cols = np.flatnonzero(comp == k)
+            for lag in range(min(L, T)):
+                c = cols[cols + lag < T] + lag
+                if len(c):
+                    m[k, :, lag] = s[:, c].min(axis=1)
+        return m
+    comp = np.argmax(W, axis=0)  # (N, L); num[k, t] = sum over the (n, l) of component k, t + l < T, of src[n, t + l]
+    m = np.full((K, T), np.inf)
+    for lag in range(min(L, T)):
+        for k in range(K):
+            rows = comp[:, lag] == k
+            if rows.any():
+                np.minimum(m[k, : T - lag], s[rows, lag:].min(axis=0), out=m[k, : T - lag])
+    return m
+
+
+def sensitivity(form, a, exact=True):
+    """The smallest relative change of any element of the updated factor a["new"] (a: divergence_half in fp64) when ONE positive term
+    is removed from its numerator or from its denominator contraction: min over elements of 1 - (1 - p / num)^g and
+    (1 - q / den_total)^-g - 1, p and q the smallest positive terms of the element's two sums and g the step exponent.  (A term that
+    is exactly 0 -- data 0, a held-out entry -- cannot be missed: removing it changes nothing.)  Elements on the floor eps (num == 0)
+    have no term to lose and are left out.  exact=False: a lower bound in closed form, from the smallest positive entries of P and Q
+    and the largest sums -- cheap, for the large shapes."""
+    g = step_exponent(form)
+    num, dt = a["num"], a["den_total"]
+    live = num > 0
+    if exact:
+        p = _min_positive_terms(a["family"], a["P"], a["W"], a["H"])[live]
+        q = _min_positive_terms(a["family"], a["Q"], a["W"], a["H"])[live]
+        xn, xd = p / num[live], q / dt[live]
+    else:
+        xn = a["P"][a["P"] > 0].min() / num.max()
+        xd = (1.0 if a["Q"] is None else a["Q"][a["Q"] > 0].min()) / dt[live].max()
+    with np.errstate(divide="ignore"):
+        xn, xd = np.minimum(xn, 1.0), np.minimum(xd, 1.0 - 1e-12)
+        return float(min(np.min(1.0 - (1.0 - xn) ** g), np.min((1.0 - xd) ** -g - 1.0)))
+
+
+def rel_err(got, ref):
+    """|got - ref| / |ref| element-wise (ref: the fp64 restatement, every entry >= eps > 0)."""
+    ref = np.asarray(ref, dtype=np.float64)
+    return np.abs(np.asarray(got, dtype=np.float64) - ref) / np.abs(ref)
+
+
+def check_elementwise(got, ref, bar, names):
+    """None when every element of got is within the relative bar of ref (and finite); else a line that names the WORST element the way
+    first_bad names the first: 'rel 3.1e-03 (bar 2e-06) at k=.., n=.., l=..: got .., want .. (17 elements over the bar)'."""
+    r = rel_err(got, ref)
+    r = np.where(np.isfinite(r), r, np.inf)
+    if r.max() <= bar:
+        return None
+    i = np.unravel_index(np.argmax(r), r.shape)
+    where = first_bad(r == r[i], names)
+    return f"rel {r[i]:.2e} (bar {bar:g}) at {where}: got {got[i]!r}, want {ref[i]!r} ({int((r > bar).sum())} elements over the bar)"
+
+
+def read_bars(path):
+    """{"bar": {form: value}, "lossbar": {...}, "gpu": {...}} of profiles/mu_divergence_elementwise.txt."""
+    out = {"bar": {}, "lossbar": {}, "gpu": {}, "gpuloss": {}}
+    for line in open(path):
+        f = line.split()
+        if len(f) == 3 and f[0] in out:
+            out[f[0]][f[1]] = float(f[2])
+    return out
+
+
+def divergence_configs(configs, form):
+    """The configurations of a table row a divergence form accepts: no Gram form, one device."""
+    return [c for c in configs if "gram" not in c and "devices" not in c]

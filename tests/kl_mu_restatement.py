@@ -18,7 +18,9 @@ oracle/cmf_oracle.py's MU rule -- the contractions, the element-wise update, the
 operations follow it in the same order.
 
 `cdtype`: the number format the CONTRACTIONS (conv, transconv, the numW products) are carried out in; float32 models the device's
-arithmetic (tools/mu_kl_precision.py measures how far that drifts from fp64).  Everything else stays fp64.
+arithmetic (tools/mu_kl_precision.py measures how far that drifts from fp64).  `edtype` (ratio, divergence and kl_loss only): the number
+format of the EPILOGUE that forms R and the loss terms from the conv, as in tests/is_mu_restatement.py (the terms are then summed in
+fp64; tools/mu_divergence_elementwise.py).  Everything else stays fp64.
 
 LITERAL_SLICES: as in tests/masked_mu_restatement.py -- True multiplies the strided slices W[:, :, lag] as they are (the oracle's
 operation order, a plain loop), False (default) copies each slice first so that the products run in BLAS.
@@ -82,21 +84,27 @@ def check_data(data):
     return data
 
 
-def ratio(data, W, H, cdtype=np.float64):
+def ratio(data, W, H, cdtype=np.float64, edtype=np.float64):
     """R = data ./ (tensor_conv(W, H) + eps)."""
-    return data / (tensor_conv(W, H, cdtype) + EPS)
+    if edtype is np.float64:
+        return data / (tensor_conv(W, H, cdtype) + EPS)
+    return (data.astype(edtype) / (tensor_conv(W, H, cdtype).astype(edtype) + edtype(EPS))).astype(np.float64)
 
 
-def divergence(data, est_eps):
-    """D(X, e) = sum of (X > 0 ? X log(X / e) : 0) - X + e."""
+def divergence(data, est_eps, edtype=np.float64):
+    """D(X, e) = sum of (X > 0 ? X log(X / e) : 0) - X + e (edtype: the terms' format; they are summed in fp64)."""
     pos = data > 0
+    if edtype is not np.float64:  # the device's order: x log(q) + (e - x)
+        x, e = data.astype(edtype), est_eps.astype(edtype)
+        q = np.where(pos, x, edtype(1.0)) / np.where(pos, e, edtype(1.0))
+        return float(np.sum((np.where(pos, x * np.log(q), edtype(0.0)) + (e - x)).astype(np.float64)))
     q = np.where(pos, data, 1.0) / np.where(pos, est_eps, 1.0)
     return float(np.sum(np.where(pos, data * np.log(q), 0.0) - data + est_eps))
 
 
-def kl_loss(data, W, H, cdtype=np.float64):
+def kl_loss(data, W, H, cdtype=np.float64, edtype=np.float64):
     """D(data, tensor_conv(W, H) + eps) / sum(data): dimensionless, 0 for a perfect fit."""
-    return divergence(data, tensor_conv(W, H, cdtype) + EPS) / float(np.sum(data))
+    return divergence(data, tensor_conv(W, H, cdtype) + EPS, edtype) / float(np.sum(data))
 
 
 def denom_W(H, N, L):

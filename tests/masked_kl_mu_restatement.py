@@ -17,6 +17,7 @@ numerator and denominator are both 0 there and the factor entries fall to eps.  
 tests/kl_mu_restatement.py (whose denominators are these contractions written as sums: ones_denominators there).
 
 `cdtype`: the number format the CONTRACTIONS are carried out in, as in kl_mu_restatement (tools/mu_masked_kl_precision.py).
+`edtype` (ratio, divergence_sum and masked_kl_loss only): the number format of the epilogue that forms R and the loss terms, as there.
 """
 import numpy as np
 
@@ -83,24 +84,31 @@ class MaskedKL:
         self.xm_sum = float(np.sum(self.Xm))
 
 
-def ratio(rule, W, H, cdtype=np.float64):
+def ratio(rule, W, H, cdtype=np.float64, edtype=np.float64):
     """R = Xm ./ (tensor_conv(W, H) + eps)."""
-    return rule.Xm / (kr.tensor_conv(W, H, cdtype) + EPS)
+    if edtype is np.float64:
+        return rule.Xm / (kr.tensor_conv(W, H, cdtype) + EPS)
+    return (rule.Xm.astype(edtype) / (kr.tensor_conv(W, H, cdtype).astype(edtype) + edtype(EPS))).astype(np.float64)
 
 
-def divergence_sum(data, mask, est_eps, complement=False):
+def divergence_sum(data, mask, est_eps, complement=False, edtype=np.float64):
     """The divergence terms summed over the entries with mask == 1 (complement: mask == 0), by select."""
     sel = (np.asarray(mask) == 0) if complement else (np.asarray(mask) != 0)
     x = np.where(sel, data, 0.0)
     pos = x > 0
+    if edtype is not np.float64:  # (the terms in edtype, in the device's order, summed in fp64)
+        xe, e = x.astype(edtype), est_eps.astype(edtype)
+        q = np.where(pos, xe, edtype(1.0)) / np.where(pos, e, edtype(1.0))
+        term = np.where(pos, xe * np.log(q), edtype(0.0)) + (e - xe)
+        return float(np.sum(np.where(sel, term, edtype(0.0)).astype(np.float64)))
     q = np.where(pos, x, 1.0) / np.where(pos, est_eps, 1.0)
     term = np.where(pos, x * np.log(q), 0.0) - x + est_eps
     return float(np.sum(np.where(sel, term, 0.0)))
 
 
-def masked_kl_loss(rule, W, H, cdtype=np.float64):
+def masked_kl_loss(rule, W, H, cdtype=np.float64, edtype=np.float64):
     """D_M(data, tensor_conv(W, H) + eps) / sum(Xm)."""
-    return divergence_sum(rule.Xm, rule.mask, kr.tensor_conv(W, H, cdtype) + EPS) / rule.xm_sum
+    return divergence_sum(rule.Xm, rule.mask, kr.tensor_conv(W, H, cdtype) + EPS, edtype=edtype) / rule.xm_sum
 
 
 def update_motifs(rule, W, H, l1W=0.0, l2W=0.0, cdtype=np.float64):

@@ -7,7 +7,7 @@ row, column, lag or component block moves some num or den by at least 1 unit = 8
 the full-size fits, a seam error confined to one chunk, tile row or lag block fails here.  Every configuration of a shape must
 also give the same bits: num and den are exact, and every path applies the same cmf_mu.
 
-The shape table is derived from the plan rules (cmf_api.hip plan(), cmf_internal.h launch_conv) on a 256-CU MI355X; the
+The shape table (exact_problems.SHAPES, shared with tests/test_gpu_divergence_paths.py) is derived from the plan rules (cmf_api.hip plan(), cmf_internal.h launch_conv) on a 256-CU MI355X; the
 launch counters (cmf_get_counter "launches:<path>") record which instances each shape reached, and the last test asserts
 that the table reaches every named path."""
 import os
@@ -16,59 +16,12 @@ import time
 import numpy as np
 import pytest
 
-from exact_problems import L1, L2, EXACT, SENS, LAUNCH_PATHS, conv3_form, first_bad, hxt_lp, make_problem, small_k_plan, transconv_lt, ulps
+from exact_problems import L1, L2, EXACT, SENS, LAUNCH_PATHS, SHAPES, conv3_form, first_bad, make_problem, ulps
 
 pytestmark = pytest.mark.gpu
 
 ULP_BAR = 2
 EPS = float(np.finfo(np.float64).eps)
-
-GROUPS = [dict(devices=[0] * R, halo_in_allreduce=hal) for R in (2, 3, 8) for hal in (0, 1)]
-CONV32 = [dict(), dict(conv_kernel=2), dict(conv_kernel=3), dict(conv_split=0), dict(conv_split=4)]
-FULL32 = CONV32 + [dict(gram=1), dict(gram=2), dict(reuse_est=0)] + GROUPS
-GENERAL = [dict(), dict(conv_split=0), dict(gram=1), dict(gram=2), dict(reuse_est=0), dict(devices=[0] * 2), dict(devices=[0] * 3, gram=1)]
-SMALL = ([dict(), dict(small_k=0), dict(reuse_est=0), dict(gram=1)] + [dict(small_k=s, small_k_fuse=f) for s in (1, 2) for f in (0, 1, 2)]
-         + [dict(devices=[0] * 2), dict(devices=[0] * 3, small_k=2, small_k_fuse=2)])
-
-# (N, T, K, L, configurations, why)
-SHAPES = [
-    # conv3_kernel grid forms (K = 32, L = 20)
-    (130, 700, 32, 20, FULL32, "conv3 pieces only, 16 pieces (44 tiles)"),
-    (1001, 2500, 32, 20, CONV32 + [dict(gram=1)], "conv3 pieces only, 4 pieces (640 tiles)"),
-    (2000, 3000, 32, 20, CONV32 + [dict(gram=1), dict(devices=[0] * 2, halo_in_allreduce=1)], "whole tiles only (1504 tiles)"),
-    (2000, 6250, 32, 20, CONV32, "whole + 16 pieces (3136 tiles: the T/8 shard), hxt tail rows"),
-    (2000, 6720, 32, 20, CONV32, "whole + 4 pieces (3360 tiles)"),
-    # hxt_kernel<LP> / transconv_kernel<LT> instances on the general kernels (K > 16, not a multiple of 32: conv_kernel)
-    (70, 600, 20, 2, GENERAL, "LP 1, LT 4"),
-    (70, 600, 20, 4, GENERAL, "LP 2, LT 4"),
-    (70, 600, 20, 6, GENERAL, "LP 3, LT 8"),
-    (70, 600, 20, 8, GENERAL, "LP 4, LT 8"),
-    (70, 600, 20, 10, GENERAL, "LP 5, LT 12"),
-    (70, 600, 20, 12, GENERAL, "LP 6, LT 12"),
-    (70, 600, 20, 16, GENERAL, "LP 8, LT 16"),
-    (70, 600, 20, 22, GENERAL, "LP 1, LT 24"),
-    (70, 600, 20, 26, GENERAL, "LP 1, LT 28"),
-    (70, 600, 20, 31, GENERAL, "LP 8, LT 32"),
-    (70, 600, 20, 40, GENERAL, "LP 5, LT 32 (L > 32)"),
-    (200, 1500, 32, 33, [dict(), dict(conv_split=0)], "LP 1 at L = 33, K = 32"),
-    (40, 40, 20, 16, GENERAL, "a recording shorter than one Gram tile past the lag window: gram_h_kernel"),
-    (30, 24, 32, 12, [dict(), dict(gram=1)], "T shorter than 2 L"),
-    # few components (K <= 16): C2 m blocks 1 .. 10 and 1 .. 3 + VALU rows, C3 1 .. 6 and 1 .. 3 + VALU rows, conv k pairs 1 .. 8
-    (90, 610, 5, 7, SMALL, "C2 / C3 1 block + VALU rows"),
-    (31, 420, 2, 33, SMALL, "C2 / C3 2 blocks + VALU rows, 1 k pair"),
-    (250, 1500, 5, 20, SMALL, "C2 / C3 3 blocks + VALU rows, C3 in 4 pieces"),
-    (48, 300, 4, 8, SMALL, "C2 / C3 1 block, 2 k pairs"),
-    (70, 257, 5, 10, SMALL, "C2 / C3 2 blocks, 3 k pairs"),
-    (300, 260, 13, 7, SMALL, "C2 / C3 3 blocks, 7 k pairs, C3 in 4 pieces"),
-    (10, 64, 8, 16, SMALL, "C2 / C3 4 blocks, 4 k pairs"),
-    (33, 400, 7, 19, SMALL, "C2 / C3 5 blocks"),
-    (65, 520, 11, 12, SMALL, "C2 5 blocks, 6 k pairs"),
-    (60, 400, 8, 22, SMALL, "C2 6 blocks"),
-    (60, 400, 10, 20, SMALL, "C2 7 blocks"),
-    (17, 150, 16, 64, SMALL, "C2 8 blocks, C3 6 blocks, L = 64"),
-    (60, 400, 14, 20, SMALL, "C2 9 blocks"),
-    (130, 700, 16, 20, SMALL, "C2 10 blocks, 8 k pairs, C3 in 2 pieces"),
-]
 
 _seen = {}          # launches:<path> summed over every handle of the file
 _shapes_done = set()

@@ -1,9 +1,12 @@
-"""CPU half of tests/test_exact_parity.py: the integer problems' preconditions over its whole shape table, the ulp comparator's
-power to see one missing term, and the launch-path names kept equal to the library's table."""
+"""CPU half of tests/test_exact_parity.py and tests/test_gpu_divergence_paths.py: the integer problems' preconditions over the whole
+shape table, the ulp comparator's power to see one missing term, the launch-path names kept equal to the library's table, and for
+the divergence forms the problems, the restated halves, the sensitivity condition and the element-wise check's power to see
+corruptions a Frobenius-relative 1e-4 passes."""
 import os
 import re
 
 import numpy as np
+import pytest
 
 import exact_problems as ep
 
@@ -11,15 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _gpu_table():
-    """SHAPES of tests/test_exact_parity.py, read from its source (the module itself is GPU-marked)."""
-    import ast
-
-    src = open(os.path.join(ROOT, "tests", "test_exact_parity.py")).read()
-    tree = ast.parse(src)
-    for node in tree.body:
-        if isinstance(node, ast.Assign) and any(getattr(t, "id", None) == "SHAPES" for t in node.targets):
-            return [tuple(ast.literal_eval(e) for e in elt.elts[:4]) for elt in node.value.elts]
-    raise AssertionError("no SHAPES table")
+    """(N, T, K, L) of the table the two GPU files share."""
+    return [s[:4] for s in ep.SHAPES]
 
 
 def test_preconditions_hold_for_every_shape_in_the_table():
@@ -113,3 +109,219 @@ def test_plan_mirror_covers_the_instances():
     assert {min(8, {5: 6, 7: 8}.get(p[5], p[5])) for p in small} == {1, 2, 3, 4, 6, 8}
     k32 = [s for s in shapes if s[2] % 32 == 0 and s[3] == 20]
     assert {ep.conv3_form(s[0], s[1]) for s in k32} >= {"whole", "whole+4", "whole+16", "pieces4", "pieces16"}
+
+
+# ---- the divergence forms (tests/test_gpu_divergence_paths.py) ----------------------------------------------------------------
+BARS_FILE = os.path.join(ROOT, "profiles", "mu_divergence_elementwise.txt")
+MUTATION_SHAPES = [(130, 700, 32, 20), (70, 600, 20, 10), (90, 610, 5, 7)]
+
+
+def test_whole_few_component_tiles_are_in_the_table():
+    """launch_conv's few-component grid: every older row is quarter pieces only; the added row runs 1024 whole tiles and 16 cut."""
+    small = [s for s in _gpu_table() if s[2] <= 16]
+    whole = [s for s in small if ep.conv_small_form(s[0], s[1])[0] > 0]
+    assert whole == [(1000, 4100, 8, 10)]
+    assert ep.conv_small_form(1000, 4100) == (1024, 16) and ep.conv_small_form(1000, 4100, conv_split=0) == (1040, 0)
+    assert (8 + 1) // 2 <= 4 and 1040 <= 4 * 4 * ep.N_CU  # (the preloaded data tile: at most 4 k pairs, at most 4 rounds)
+
+
+def oracle_conv(W, H):
+    from oracle import cmf_oracle as oracle
+
+    return oracle.tensor_conv(W, H)
+
+
+def test_divergence_problem():
+    N, T, K, L = 90, 610, 5, 7
+    for family in ("W", "H"):
+        W0, H0, _ = ep.make_problem(N, T, K, L, family)
+        W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family)
+        _, _, Xz, maskz = ep.make_divergence_problem(N, T, K, L, family, zeros=True)
+        assert np.array_equal(W, W0) and np.array_equal(H, H0)
+        assert X.min() == ep.DIV_XMIN and X.max() == ep.DIV_XMAX and np.all(X == np.round(X))
+        assert len(np.unique(X)) == ep.DIV_XMAX - ep.DIV_XMIN + 1
+        zero = Xz == 0
+        assert 0.10 < zero.mean() < 0.15 and np.array_equal(Xz[~zero], X[~zero])
+        assert np.array_equal(mask, maskz) and set(np.unique(mask)) == {0.0, 1.0} and 0.2 < (mask == 0).mean() < 0.3
+        Xr = ep.make_divergence_problem(N, T, K, L, family, relative=True)[2]
+        est = oracle_conv(W, H)
+        assert np.array_equal(Xr * 16, X * est) and np.array_equal(Xr.astype(np.float32), Xr) and (Xr / est).min() >= 1 and (Xr / est).max() < 2
+        assert np.array_equal(mask[:, :608].reshape(N, -1, 8).min(axis=2), mask[:, :608].reshape(N, -1, 8).max(axis=2))  # blocks of 8
+
+
+@pytest.mark.parametrize("shape", MUTATION_SHAPES[1:], ids=str)
+def test_divergence_half_is_the_restatements(shape):
+    """divergence_half (the restatement's operations with the intermediate arrays kept) gives the bits of the restatements' own
+    update_motifs / update_feature_maps, in fp64 and in the float32 model."""
+    import beta_mu_restatement as br
+    import is_mu_restatement as ir
+    import kl_mu_restatement as kr
+    import masked_kl_mu_restatement as mk
+
+    N, T, K, L = shape
+    for family in ("W", "H"):
+        W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family, zeros=True)
+        Xp = ep.make_divergence_problem(N, T, K, L, family)[2]
+        for form, (kind, beta, masked, zeros_ok, relative) in ep.FORMS.items():
+            for dt in (np.float64, np.float32):
+                data = ep.make_divergence_problem(N, T, K, L, family, zeros=zeros_ok, relative=True)[2] if relative else X if zeros_ok else Xp
+                a = ep.divergence_half(form, family, data, mask, W, H, cdtype=dt, edtype=dt)
+                Wr, Hr = W.copy(order="K"), H.copy(order="K")  # (the layout decides the order of the BLAS sums)
+                if kind == ":kl" and masked:
+                    args, kw, mod = (mk.MaskedKL(data, mask), Wr, Hr), dict(cdtype=dt), mk
+                elif kind == ":kl":
+                    args, kw, mod = (data, Wr, Hr), dict(cdtype=dt), kr
+                elif kind == ":itakura_saito":
+                    args, kw, mod = (data, Wr, Hr), dict(cdtype=dt, edtype=dt), ir
+                else:
+                    args, kw, mod = (data, Wr, Hr, beta), dict(cdtype=dt, edtype=dt), br
+                if family == "W":
+                    mod.update_motifs(*args, l1W=ep.L1, l2W=ep.L2, **kw)
+                    assert np.array_equal(a["new"], Wr), (form, family, dt)
+                else:
+                    loss = mod.update_feature_maps(*args, l1H=ep.L1, l2H=ep.L2, **kw)
+                    assert np.array_equal(a["new"], Hr), (form, family, dt)
+                    if dt is np.float64 or kind != ":kl":  # (the KL restatements' own loss has no float32 epilogue)
+                        assert loss == a["loss"], (form, dt)
+                    else:
+                        assert abs(loss - a["loss"]) <= 1e-5 * loss
+
+
+def test_bars_file_states_the_condition():
+    """One bar and one loss bar per form, of the expected size, and every row's sensitivity at least 4 bars."""
+    bars = ep.read_bars(BARS_FILE)
+    assert set(bars["bar"]) == set(bars["lossbar"]) == set(ep.FORMS)
+    for form in ep.FORMS:
+        # (8 x a model error between one fp32 rounding and a few tens of them: sums of some hundred to a thousand terms)
+        assert 4e-7 <= bars["bar"][form] <= 2e-5 and 1e-7 <= bars["lossbar"][form] <= 2e-5, (form, bars)
+    rows = [ln.split() for ln in open(BARS_FILE) if ln.startswith("row ")]
+    variants = sum(2 if f[3] else 1 for f in ep.FORMS.values())
+    assert len(rows) == variants * 2 * len(ep.SHAPES)
+    for r in rows:
+        sens = float(r[-1].split("=")[-1])
+        assert sens >= 4 * bars["bar"][r[1].split("+")[0]], r
+
+
+@pytest.mark.parametrize("shape", MUTATION_SHAPES, ids=str)
+def test_sensitivity_from_the_arrays(shape):
+    """The condition again from arrays generated here; the closed-form bound is a lower bound of the exact value; and the definition
+    itself: removing the one smallest term of the most fragile element moves it by the value returned."""
+    bars = ep.read_bars(BARS_FILE)["bar"]
+    N, T, K, L = shape
+    for family in ("W", "H"):
+        for zeros in (False, True):
+            for form, f in ep.FORMS.items():
+                if zeros and not f[3]:
+                    continue
+                W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family, zeros=zeros, relative=f[4])
+                a = ep.divergence_half(form, family, X, mask, W, H)
+                s, lo = ep.sensitivity(form, a), ep.sensitivity(form, a, exact=False)
+                assert lo <= s * (1 + 1e-12) and s >= 4 * bars[form], (form, family, zeros, s, lo)
+    # the definition, on the W half of the Itakura-Saito form: brute force over every element's numerator terms
+    W, H, X, mask = ep.make_divergence_problem(N, T, K, L, "W", relative=True)
+    a = ep.divergence_half("is", "W", X, mask, W, H)
+    comp = np.argmax(H, axis=0)
+    k, n, lag = 1, N // 2, min(L, T) - 1
+    cols = np.flatnonzero(comp == k)
+    terms = a["P"][n, cols[cols + lag < T] + lag]
+    assert np.isclose(terms.sum(), a["num"][k, n, lag], rtol=1e-12)
+    moved = 1.0 - np.sqrt((a["num"][k, n, lag] - terms.min()) / a["num"][k, n, lag])
+    assert moved >= ep.sensitivity("is", a) * (1 - 1e-9)
+    assert np.isclose(ep._min_positive_terms("W", a["P"], W, H)[k, n, lag], terms.min(), rtol=0)
+
+
+def _corruptions(family, has_q):
+    """name -> corrupt(stage, arrays) for divergence_half: the damage a seam error in an epilogue or a contraction would do."""
+    big = 1.0 / ep.EPS
+
+    def strip(which):
+        def f(stage, a):  # one 4-row strip of a 64 x 64 block zeroed (a piece of a cut tile that stored P but not Q, or neither)
+            if stage == "sources":
+                a[which] = a[which].copy()
+                a[which][8:12, 192:256] = 0.0
+        return f
+
+    def lag(stage, a):  # C2 loses its last lag over one time chunk
+        if stage == "sums":
+            l = a["num"].shape[2] - 1
+            a["num"][:, :, l] -= a["H"][:, 128:384] @ a["P"][:, 128 + l:384 + l].T
+
+    def kpair(stage, a):  # C3 loses one k pair of one 32-unit block over one 64-column tile
+        if stage == "sums":
+            W, P = a["W"], a["P"]
+            for l in range(W.shape[2]):
+                a["num"][2:4, 64:128] -= W[2:4, :32, l] @ P[:32, 64 + l:128 + l]
+
+    def pad(stage, a):  # the contraction runs one column past T, where Q holds 1 / eps instead of the selected 0
+        if stage == "sums":
+            T = a["H"].shape[1]
+            for l in range(1, a["W"].shape[2]):
+                if family == "W":
+                    a["den"][:, :, l] += a["H"][:, T - l][:, None] * big
+                else:
+                    a["den"][:, T - l] += a["W"][:, :, l].sum(axis=1) * big
+
+    def double(stage, a):  # one time row of P counted twice
+        if stage == "sums":
+            t0 = 300
+            for l in range(a["W"].shape[2]):
+                if family == "W":
+                    a["num"][:, :, l] += a["H"][:, t0 - l][:, None] * a["P"][:, t0][None, :]
+                else:
+                    a["num"][:, t0 - l] += a["W"][:, :, l] @ a["P"][:, t0]
+
+    def term(stage, a):  # ONE term missing from the numerator of ONE element (the unit of exact_problems.sensitivity)
+        if stage == "sums":
+            if family == "W":
+                k, n, l = 1, 5, 2
+                t = [t for t in np.flatnonzero(a["H"][k] != 0)[3:] if a["P"][n, t + l] > 0][0]  # (a held-out entry is no term)
+                a["num"][k, n, l] -= a["P"][n, t + l]
+            else:
+                k, t = 1, 100
+                n, l = [(n, l) for l in range(a["W"].shape[2]) for n in np.flatnonzero(a["W"][k, :, l] != 0) if a["P"][n, t + l] > 0][0]
+                a["num"][k, t] -= a["P"][n, t + l]
+
+    out = {"strip_P": strip("P"), "double": double, "term": term, "lag" if family == "W" else "kpair": lag if family == "W" else kpair}
+    if has_q:
+        out.update(strip_Q=strip("Q"), pad=pad)
+    return out
+
+
+# Which of the corruptions a Frobenius-relative 1e-4 on the updated factor -- the bar of every other divergence test -- passes on at
+# least one (shape, form) here, measured by the test below (it asserts this very set).  On these three small shapes a strip, a lag
+# over a chunk, a k pair over a tile, a doubled time row and the padding read all move the norm by more than 1e-4 as well (a strip is
+# 4 of 70 ... 130 units); what the norm passes is the single term -- and, at the sizes the GPU test adds, everything confined to one
+# tile: a 4 x 64 strip changes 4 of 2000 units by 2 of 210 terms (4e-4 of the norm at T = 6720, 5e-5 at config 2's T = 50000).  The
+# element-wise check flags every one, at every size, because its bar is per element.
+FROBENIUS_PASSES = {"term"}
+
+
+def test_elementwise_check_flags_what_frobenius_passes():
+    bars = ep.read_bars(BARS_FILE)["bar"]
+    blind = set()
+    for N, T, K, L in MUTATION_SHAPES:
+        for family, names in (("W", "knl"), ("H", "kt")):
+            for form in ep.FORMS:
+                W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family, relative=ep.FORMS[form][4])
+                ref = ep.divergence_half(form, family, X, mask, W, H)
+                assert ep.check_elementwise(ref["new"].astype(np.float32), ref["new"], bars[form], names) is None
+                for name, corrupt in _corruptions(family, ref["Q"] is not None).items():
+                    got = ep.divergence_half(form, family, X, mask, W, H, corrupt=corrupt)["new"].astype(np.float32)
+                    msg = ep.check_elementwise(got, ref["new"], bars[form], names)
+                    assert msg is not None and " at k=" in msg, (name, form, family, (N, T, K, L))
+                    if np.linalg.norm(got - ref["new"]) / np.linalg.norm(ref["new"]) < 1e-4:
+                        blind.add(name)
+    print("a Frobenius-relative 1e-4 passes:", sorted(blind))
+    assert blind == FROBENIUS_PASSES
+
+
+def test_check_elementwise_reports_the_worst_element():
+    ref = np.full((3, 4, 5), 2.0)
+    got = ref.astype(np.float32)
+    assert ep.check_elementwise(got, ref, 1e-6, "knl") is None
+    got[1, 2, 3] *= 1.001
+    got[2, 0, 0] *= 1.1
+    msg = ep.check_elementwise(got, ref, 1e-6, "knl")
+    assert "k=2, n=0, l=0" in msg and "2 elements" in msg and msg.startswith("rel 1.00e-01")
+    got[0, 0, 0] = np.nan
+    assert "k=0, n=0, l=0" in ep.check_elementwise(got, ref, 1e-6, "knl")
