@@ -14,7 +14,9 @@ Dropping or doubling any time row, column, lag or component block then moves som
 preconditions() bounds every num / den by 2^20, so such an error is at least 8 ulp of fp32.
 
 The shape table SHAPES is shared with tests/test_gpu_divergence_paths.py, which holds the divergence forms of the rule to their fp64
-restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below).
+restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below),
+and with tests/test_gpu_exact_masked_mu.py and tests/test_gpu_exact_pgd.py, which hold the MU rule under a 0/1 mask and the PGD rule to
+their references on it (the last section: mu_mask, make_pgd_problem, pgd_half, pgd_preconditions).
 """
 import numpy as np
 
@@ -470,3 +472,273 @@ def read_bars(path):
 def divergence_configs(configs, form):
     """The configurations of a table row a divergence form accepts: no Gram form, one device."""
     return [c for c in configs if "gram" not in c and "devices" not in c]
+
+
+# ---- the masked MU rule and the PGD rule on these problems (tests/test_gpu_exact_masked_mu.py, tests/test_gpu_exact_pgd.py) -------
+# Masked MU: make_problem's X under the 0/1 mask of make_divergence_problem.  mask .* est, mask .* X, both numerators and denominators
+# and the loss tile sums stay sums of small non-negative integers, so the argument of the module doc holds unchanged.
+#
+# PGD: the residual est - X is a SIGNED integer, gradW = hxt(H, resid) and gradH = transconv(W, resid) are signed integer sums whose
+# every partial sum is bounded by the sum of absolute values; g = gscale G + 2 pen_sq x + pen_abs sign(x) is a multiple of 1/2;
+# pgd_w_grad_kernel / pgd_h_grad_kernel sum g^2 in double (an exact integer multiple of 1/4 below 2^53 in any order), so
+# alpha = (float)(step / (sqrt(sum g^2) + eps)) is ONE float32 number on every path, and x - alpha g, fused or not, is within
+# 0.5 ulp (the result) + 0.5 ulp of alpha |g| (the product) + 2^-24 alpha |g| (alpha rounded) of the fp64 value: with alpha |g| at most
+# a quarter of |x_new| (pgd_preconditions: no_clamp) that is below 1 ulp of x_new, inside the bar of 2.
+STEP0 = 5.0  # PGDUpdate's first stepW, stepH (pgd.jl:149-150)
+# name -> (loss, masked, (penaltiesW_sq, penaltiesW_abs), (penaltiesH_sq, penaltiesH_abs), nonneg); the first four are the loss kinds
+# under the rule's defaults (penaltiesW = [SquarePenalty(1)], penaltiesH = [], NonnegConstraint), then the dyadic AbsolutePenalty on
+# both factors and the rule without a constraint
+PGD_VARIANTS = {
+    "square": ("square", False, ((1.0,), ()), ((), ()), True),
+    "abs": ("abs", False, ((1.0,), ()), ((), ()), True),
+    "square_masked": ("square", True, ((1.0,), ()), ((), ()), True),
+    "abs_masked": ("abs", True, ((1.0,), ()), ((), ()), True),
+    "square_l1": ("square", False, ((1.0,), (0.5,)), ((), (0.5,)), True),
+    "abs_masked_free": ("abs", True, ((1.0,), ()), ((), ()), False),
+}
+PGD_LARGE_VARIANTS = ("square", "abs_masked")  # the rows with N >= 1000: a test stays at a few seconds
+
+
+def pgd_variants(N):
+    return list(PGD_LARGE_VARIANTS) if N >= 1000 else list(PGD_VARIANTS)
+
+
+_conv_last = [None, None, None]
+
+
+def _conv(W, H):
+    """tensor_conv(W, H) by the oracle; the last result is kept for the same two array objects (the helpers below never write into
+    W or H, and every variant of a row asks for the same est)."""
+    from oracle import cmf_oracle
+
+    if _conv_last[0] is not W or _conv_last[1] is not H:
+        _conv_last[:] = [W, H, cmf_oracle.tensor_conv(W, H)]
+    return _conv_last[2]
+
+
+def mu_mask(N, T, seed=0):
+    """The 0/1 mask of make_divergence_problem (blocks of 1 x 8 entries, a quarter held out) on its own."""
+    nn, tb = np.meshgrid(np.arange(N), np.arange(T) // 8, indexing="ij")
+    return np.asfortranarray(((_hash(nn, tb, salt=seed * 4 + 5) >> np.uint64(9)) % np.uint64(4) != 0).astype(np.float64))
+
+
+def holes_mask(N, T, seed=0):
+    """mu_mask with one unit (N // 2) and one sample (T // 3) never observed."""
+    m = mu_mask(N, T, seed)
+    m[N // 2, :] = 0.0
+    m[:, T // 3] = 0.0
+    return m
+
+
+PGD_R = 2  # the near-fit data's noise: r in {-PGD_R ... PGD_R}
+# The first step of a fresh rule has norm 5 whatever the data is (alpha g = 5 g / |g|), so its largest entry is at least 5 / sqrt(number
+# of entries of the factor): 0.2 ... 0.7 on the table's small rows, against entries of 1 and 2.  The dense factor is therefore
+# make_problem's times 4 (entries 4 and 8, est four times as large, every sum still far below 2^24): the step stays below a quarter of
+# every updated entry on every row, which is what the 2 ulp bound needs (pgd_preconditions: no_clamp).
+PGD_SCALE = 4.0
+
+
+def make_pgd_problem(N, T, K, L, family, seed=0):
+    """(W, H, X, mask): W and H of make_problem, the dense one times PGD_SCALE; NEAR-FIT data X = max(est + r, 0), est = tensor_conv(W, H) and r in {-2 ... 2} from
+    other bits of the hash make_problem's X comes from (a fifth of the residual is exactly 0: sign(0) = 0 of the AbsoluteLoss store;
+    the gradient is small, so alpha = 5 / |g| is large and one lost unit of a contraction moves an element by many ulp:
+    pgd_preconditions); and a WEIGHT mask in {0, 1, 2} in blocks of 1 x 8 entries, about a quarter 0 (the PGD mask is real-valued,
+    cmf_set_mask: the weight 2 catches an epilogue that treats it as a flag)."""
+    W, H, _ = make_problem(N, T, K, L, family, seed)
+    if family == "W":
+        W *= PGD_SCALE
+    else:
+        H *= PGD_SCALE
+    h = _data_hash(N, T, seed)
+    r = ((h >> np.uint64(24)) % np.uint64(2 * PGD_R + 1)).astype(np.float64) - PGD_R
+    X = np.maximum(_conv(W, H) + r, 0.0)
+    nn, tb = np.meshgrid(np.arange(N), np.arange(T) // 8, indexing="ij")
+    v = (_hash(nn, tb, salt=seed * 4 + 6) >> np.uint64(9)) % np.uint64(8)
+    mask = np.where(v < 2, 0.0, np.where(v < 5, 1.0, 2.0))
+    return W, H, np.asfortranarray(X), np.asfortranarray(mask)
+
+
+def _contract(family, W, H, E):
+    """compute_gradW! (pgd.jl:206-214, family "W") or compute_gradH! (:218-221) of the array E, in fp64."""
+    from oracle import cmf_oracle
+
+    if family == "H":
+        return cmf_oracle.tensor_transconv(W, E)
+    K, N, L = W.shape
+    T = H.shape[1]
+    out = np.zeros(W.shape)
+    for lag in range(min(L, T)):
+        out[:, :, lag] = H[:, : T - lag] @ E[:, lag:].T
+    return out
+
+
+def pgd_sources(variant, W, H, X, mask, weights=True):
+    """(E, gscale): the array the gradient contracts as the conv epilogue stores it -- est - data or its sign, times the mask -- and
+    the factor the gradient kernels apply (2 for SquareLoss, 1 for AbsoluteLoss).  weights=False: the mask read as a 0/1 flag."""
+    loss, masked = PGD_VARIANTS[variant][:2]
+    E = _conv(W, H) - X
+    if loss == "abs":
+        E = np.sign(E)
+    if masked:
+        E = E * (mask if weights else (mask != 0))
+    return E, (1.0 if loss == "abs" else 2.0)
+
+
+def pgd_half(variant, family, W, H, X, mask, corrupt=None, step=STEP0):
+    """The half-step of the variant from (W, H) with its intermediate arrays kept: E, gscale (pgd_sources), G (the contraction), g (the
+    gradient with the penalties), sumsq, alpha, new (the updated factor, clamped where the variant projects).  The operations are
+    oracle._pgd's (tests/test_exact_problems.py holds `new` equal to the oracle's factor bit for bit); this is what the preconditions,
+    the float32 model and the mutation tests are computed from, NOT the reference of the GPU tests (that is the oracle itself).
+    corrupt(stage, arrays): "sources" after E exists, "sums" after G does."""
+    _, _, penW, penH, nonneg = PGD_VARIANTS[variant]
+    pen_sq, pen_abs = penW if family == "W" else penH
+    a = dict(W=W, H=H, family=family, variant=variant)
+    a["E"], a["gscale"] = pgd_sources(variant, W, H, X, mask)
+    if corrupt:
+        corrupt("sources", a)
+    a["G"] = _contract(family, W, H, a["E"])
+    if corrupt:
+        corrupt("sums", a)
+    return pgd_finish(a, step)
+
+
+def pgd_finish(a, step=STEP0):
+    """g, sumsq, alpha, free and new of pgd_half from a["G"] (again after a mutation test has damaged G)."""
+    _, _, penW, penH, nonneg = PGD_VARIANTS[a["variant"]]
+    family = a["family"]
+    pen_sq, pen_abs = penW if family == "W" else penH
+    x = a["W"] if family == "W" else a["H"]
+    g = a["G"] * a["gscale"]
+    for w in pen_sq:
+        g = g + 2.0 * w * x
+    for w in pen_abs:
+        g = g + w * np.sign(x)
+    a["g"], a["x"] = g, x
+    a["sumsq"] = float(np.sum(g * g))
+    a["alpha"] = step / (np.sqrt(a["sumsq"]) + EPS)
+    a["free"] = x - a["alpha"] * g
+    a["new"] = np.maximum(a["free"], EPS) if nonneg else a["free"]
+    return a
+
+
+def pgd_f32_model(a, fused):
+    """The device's half-step from the EXACT gradient: alpha rounded to float32 (pgd_w_apply_kernel), then x - alpha g in float32 with
+    the product rounded (fused=False) or not (fused=True: fmaf(-alpha, g, x))."""
+    al = np.float32(a["alpha"])
+    x32, g32 = a["x"].astype(np.float32), a["g"].astype(np.float32)
+    assert np.array_equal(x32, a["x"]) and np.array_equal(g32, a["g"])  # (both exact in fp32)
+    if fused:
+        new = (a["x"] - np.float64(al) * a["g"]).astype(np.float32)  # (the fp64 product of two floats is exact; one rounding)
+    else:
+        new = x32 - al * g32
+    return np.maximum(new, np.float32(EPS)) if PGD_VARIANTS[a["variant"]][4] else new
+
+
+def pgd_oracle_half(oracle, variant, family, W, H, X, mask):
+    """(updated factor, (stepW, stepH), loss or None) of ONE oracle.pgd_update_motifs (family "W") or pgd_update_feature_maps (family
+    "H") on a fresh oracle.PGDUpdate: the reference of tests/test_gpu_exact_pgd.py."""
+    loss, masked, penW, penH, nonneg = PGD_VARIANTS[variant]
+    Wc, Hc = W.copy(order="F"), H.copy(order="F")
+    rule = oracle.PGDUpdate(X, Wc, Hc)
+    kw = dict(nonneg=nonneg, mask=mask if masked else None, loss=loss)
+    if family == "W":
+        oracle.pgd_update_motifs(rule, X, Wc, Hc, penaltiesW_sq=penW[0], penaltiesW_abs=penW[1], **kw)
+        return Wc, (rule.stepW, rule.stepH), None
+    lv = oracle.pgd_update_feature_maps(rule, X, Wc, Hc, penaltiesH_sq=penH[0], penaltiesH_abs=penH[1], **kw)
+    return Hc, (rule.stepW, rule.stepH), lv
+
+
+def max_tile_sum(a, tile=128):
+    """The largest sum of the non-negative array a over a tile x tile block (a bound for the 64 x 64 loss tiles of the conv epilogues)."""
+    N, T = a.shape
+    r = np.zeros((-(-N // tile) * tile, -(-T // tile) * tile))
+    r[:N, :T] = a
+    return r.reshape(r.shape[0] // tile, tile, r.shape[1] // tile, tile).sum(axis=(1, 3)).max()
+
+
+def contract_cols(family, W, H, dE, t0):
+    """The contraction (_contract) of an array that is dE on the columns t0 ... t0 + dE.shape[1] - 1 and 0 elsewhere: what a damaged
+    block of the contracted array adds to every sum (the mutation tests)."""
+    K, N, L = W.shape
+    T = H.shape[1]
+    t1 = t0 + dE.shape[1]
+    out = np.zeros(W.shape if family == "W" else H.shape)
+    for lag in range(min(L, T)):
+        a, b = max(t0, lag), t1
+        if a >= b:
+            continue
+        if family == "W":
+            out[:, :, lag] = H[:, a - lag:b - lag] @ dE[:, a - t0:].T
+        else:
+            out[:, a - lag:b - lag] += W[:, :, lag] @ dE[:, a - t0:]
+    return out
+
+
+def pgd_preconditions(a, X, mask):
+    """From the arrays of pgd_half (a) -- nothing here is met by skipping a row:
+      exact        every accumulation's sum of ABSOLUTE values (est, the contraction of |E| with the mask's weight in it) < 2^24
+      sumsq_exact  sum g^2 < 2^53 (a multiple of 1/4: exact in double in any order)
+      no_clamp     alpha max|g| <= a quarter of the smallest |updated entry| (and that entry > eps): the clamp never acts, the step
+                   itself is what is compared, and the product alpha g is rounded at most half as finely as the result
+      units        gscale alpha / the float32 spacing at the largest |x_new|: one unit of one contraction in ulp; >= 8 is asked
+      loss_exact   the 64 x 64 tile sums of the loss terms of the INTEGER factors (|E| or E^2, weights included) <= 2^24
+    """
+    W, H, family = a["W"], a["H"], a["family"]
+    absG = _contract(family, W, H, np.abs(a["E"]))
+    est = _conv(W, H)
+    b = dict(absG=float(absG.max()), est=float(est.max()), sumsq=a["sumsq"])
+    b["exact"] = max(b["absG"] * a["gscale"] + 2.0 * np.abs(a["x"]).max() + 0.5, b["est"], X.max()) < EXACT
+    b["sumsq_exact"] = a["sumsq"] < 2.0 ** 53 and a["sumsq"] * 4 == np.round(a["sumsq"] * 4)
+    b["alpha_g"] = float(a["alpha"] * np.abs(a["g"]).max())
+    b["min_new"] = float(np.abs(a["free"]).min())
+    b["no_clamp"] = b["alpha_g"] <= 0.25 * b["min_new"] and float(a["free"].min()) > EPS
+    top = np.float32(np.abs(a["new"]).max())
+    b["units"] = float(a["gscale"] * a["alpha"] / np.spacing(top))
+    b["sensitive"] = b["units"] >= 8.0
+    b["loss_tile"] = float(max_tile_sum(np.abs(a["E"]) if PGD_VARIANTS[a["variant"]][0] == "abs" else a["E"] ** 2))
+    b["loss_exact"] = b["loss_tile"] <= EXACT
+    return b
+
+
+def assert_pgd_preconditions(a, X, mask, what):
+    b = pgd_preconditions(a, X, mask)
+    assert b["exact"], f"{what}: an fp32 accumulation would round ({b})"
+    assert b["sumsq_exact"], f"{what}: sum g^2 is not exact in double ({b})"
+    assert b["no_clamp"], f"{what}: alpha max|g| = {b['alpha_g']:.3f} against a smallest entry of {b['min_new']:.3g}: above a quarter of it"
+    assert b["sensitive"], f"{what}: one unit of a contraction is {b['units']:.2f} ulp only (8 asked: 4 bars of 2 ulp)"
+    return b
+
+
+def masked_mu_half(family, W, H, X, mask, corrupt=None):
+    """One update_motifs! (family "W") or update_feature_maps! (family "H") of the MU rule under the 0/1 mask, masked_mu_restatement's
+    operations with the intermediate arrays kept (Xm, est = mask .* conv, num, den, new): for the preconditions and the mutation tests;
+    tests/test_exact_problems.py holds `new` equal to the restatement's factor bit for bit.  corrupt: as in pgd_half."""
+    a = dict(W=W, H=H, family=family, M=mask)
+    a["Xm"] = np.where(mask != 0, X, 0.0)
+    a["est"] = np.where(mask != 0, _conv(W, H), 0.0)
+    if corrupt:
+        corrupt("sources", a)
+    a["num"], a["den"] = _contract(family, W, H, a["Xm"]), _contract(family, W, H, a["est"])
+    if corrupt:
+        corrupt("sums", a)
+    x = W if family == "W" else H
+    a["new"] = np.maximum(x * (a["num"] / (((a["den"] + L1) + (2.0 * L2) * x) + EPS)), EPS)
+    return a
+
+
+def assert_masked_mu_preconditions(a, what, holes=False):
+    """assert_preconditions of tests/test_exact_parity.py on the masked sums, and every element of the updated factor keeps at least
+    one observed term (holes: the deliberate exception) where the row gives every element at least 16 terms to begin with.  Where it
+    does not -- an element of H sums the N L / K entries (n, t + l) of its component: 7 on the row (70, 600, 20, 2); on (40, 40, 20, 16)
+    a component owns two columns of H -- blocks of 1 x 8 holding out a quarter now and then hold out all of an element's terms.
+    Every such element has num = den = 0 and must come out as eps exactly, which is asserted on every row."""
+    assert max(a["num"].max(), a["den"].max(), a["est"].max()) < EXACT, f"{what}: an fp32 accumulation would round"
+    assert max(a["num"].max(), a["den"].max()) <= SENS, f"{what}: num / den above 2^20: the 2 ulp bar could miss a single term"
+    seen = _contract(a["family"], a["W"], a["H"], (a["M"] != 0).astype(np.float64))
+    terms = _contract(a["family"], a["W"], a["H"], np.ones(a["M"].shape))
+    live = terms > 0
+    if not holes and terms[live].min() >= 16:
+        assert seen[live].min() >= 1, f"{what}: {(seen[live] == 0).sum()} elements of the updated factor have no observed term"
+    assert np.all(a["new"][seen == 0] == EPS)
+    seen[~live] = -1  # (no term at all, mask or not: lags beyond the recording, components without a column)
+    return seen

@@ -1,7 +1,8 @@
 """CPU half of tests/test_exact_parity.py and tests/test_gpu_divergence_paths.py: the integer problems' preconditions over the whole
 shape table, the ulp comparator's power to see one missing term, the launch-path names kept equal to the library's table, and for
 the divergence forms the problems, the restated halves, the sensitivity condition and the element-wise check's power to see
-corruptions a Frobenius-relative 1e-4 passes."""
+corruptions a Frobenius-relative 1e-4 passes; and for the masked MU rule and the PGD rule (tests/test_gpu_exact_masked_mu.py,
+tests/test_gpu_exact_pgd.py) the preconditions on the whole table, a float32 model of the PGD half-step and the same kind of mutations."""
 import os
 import re
 
@@ -325,3 +326,263 @@ def test_check_elementwise_reports_the_worst_element():
     assert "k=2, n=0, l=0" in msg and "2 elements" in msg and msg.startswith("rel 1.00e-01")
     got[0, 0, 0] = np.nan
     assert "k=0, n=0, l=0" in ep.check_elementwise(got, ref, 1e-6, "knl")
+
+
+# ---- the masked MU rule and the PGD rule (tests/test_gpu_exact_masked_mu.py, tests/test_gpu_exact_pgd.py) ------------------------
+PROFILE = os.path.join(ROOT, "profiles", "exact_masked_pgd.txt")
+ULP_BAR = 2
+SMALL_ROW, LARGEST_ROW = (70, 600, 20, 10), (2000, 6720, 32, 20)
+TABLE_IDS = [f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in ep.SHAPES]
+
+
+def test_pgd_problem():
+    N, T, K, L = 90, 610, 5, 7
+    for family in ("W", "H"):
+        W0, H0, _ = ep.make_problem(N, T, K, L, family)
+        W, H, X, mask = ep.make_pgd_problem(N, T, K, L, family)
+        dense, dense0, other, other0 = (W, W0, H, H0) if family == "W" else (H, H0, W, W0)
+        assert np.array_equal(dense, ep.PGD_SCALE * dense0) and np.array_equal(other, other0)
+        r = X - oracle_conv(W, H)
+        assert np.all(X == np.round(X)) and X.min() >= 0 and set(np.unique(r)) == set(range(-ep.PGD_R, ep.PGD_R + 1))
+        assert 0.17 < (r == 0).mean() < 0.23  # sign(0) = 0 of the AbsoluteLoss store is exercised
+        assert set(np.unique(mask)) == {0.0, 1.0, 2.0} and 0.2 < (mask == 0).mean() < 0.3 and 0.3 < (mask == 2).mean() < 0.45
+        assert np.array_equal(mask[:, :608].reshape(N, -1, 8).min(axis=2), mask[:, :608].reshape(N, -1, 8).max(axis=2))  # blocks of 8
+        m01 = ep.mu_mask(N, T)
+        assert np.array_equal(m01, ep.make_divergence_problem(N, T, K, L, family)[3])
+        holes = ep.holes_mask(N, T)
+        assert not holes[N // 2].any() and not holes[:, T // 3].any() and holes.mean() > 0.7
+
+
+@pytest.mark.parametrize("shape", [(70, 600, 20, 10), (90, 610, 5, 7), (30, 24, 32, 12)], ids=str)
+def test_halves_are_the_references(shape):
+    """pgd_half and masked_mu_half (the operations with the intermediate arrays kept) give the bits of the references the GPU tests
+    compare with: the oracle's PGD rule and the masked restatement."""
+    from oracle import cmf_oracle as oracle
+
+    import masked_mu_restatement as mr
+
+    N, T, K, L = shape
+    for family in ("W", "H"):
+        W, H, X, mask = ep.make_pgd_problem(N, T, K, L, family)
+        for variant in ep.PGD_VARIANTS:
+            a = ep.pgd_half(variant, family, W, H, X, mask)
+            ref, steps, loss = ep.pgd_oracle_half(oracle, variant, family, W, H, X, mask)
+            assert np.array_equal(a["new"], ref), (variant, family)
+            assert (steps[0] if family == "H" else steps[1]) == ep.STEP0 and (steps[1] if family == "H" else steps[0]) in (ep.STEP0 * 1.05, ep.STEP0 * 0.70)
+            assert (loss is None) == (family == "W")
+        W, H, X = ep.make_problem(N, T, K, L, family)
+        for m in (ep.mu_mask(N, T), ep.holes_mask(N, T)):
+            a = ep.masked_mu_half(family, W, H, X, m)
+            Wr, Hr = W.copy(order="K"), H.copy(order="K")
+            rule = mr.MaskedMult(X, m)
+            if family == "W":
+                mr.update_motifs(rule, Wr, Hr, l1W=ep.L1, l2W=ep.L2)
+                assert np.array_equal(a["new"], Wr)
+            else:
+                mr.update_feature_maps(rule, Wr, Hr, l1H=ep.L1, l2H=ep.L2)
+                assert np.array_equal(a["new"], Hr)
+
+
+def _profile_rows():
+    """{(rule, shape, family, variant): {key: value}} of the `row` lines of profiles/exact_masked_pgd.txt."""
+    out = {}
+    for line in open(PROFILE):
+        f = line.split()
+        if f and f[0] == "row":
+            out[(f[1], f[2], f[3], f[4])] = {kv.split("=")[0]: float(kv.split("=")[1]) for kv in f[5:]}
+    return out
+
+
+@pytest.mark.parametrize("N,T,K,L", [s[:4] for s in ep.SHAPES], ids=TABLE_IDS)
+def test_pgd_preconditions_and_float32_model(N, T, K, L):
+    """Every row, family and variant: the preconditions from the arrays generated (none is met by skipping a row), and the float32
+    model of the half-step -- the exact integer gradient, alpha rounded to float32, product and difference in float32, fused and not --
+    within 2 ulp of the fp64 half-step per element: the derivation of exact_problems' PGD section, confirmed.  The values are those
+    profiles/exact_masked_pgd.txt records."""
+    rows = _profile_rows()
+    for family in ("W", "H"):
+        W, H, X, mask = ep.make_pgd_problem(N, T, K, L, family)
+        r2 = (ep._conv(W, H) - X) ** 2
+        assert ep.max_tile_sum(r2) <= ep.EXACT  # compute_loss() of the integer factors is exact
+        for variant in ep.pgd_variants(N):
+            what = f"{(N, T, K, L)} {family} {variant}"
+            a = ep.pgd_half(variant, family, W, H, X, mask)
+            b = ep.assert_pgd_preconditions(a, X, mask, what)
+            assert b["loss_exact"], what
+            worst = max(float(ep.ulps(ep.pgd_f32_model(a, fused), a["new"]).max()) for fused in (False, True))
+            assert worst <= ULP_BAR, f"{what}: the float32 model is {worst:.2f} ulp from the fp64 half-step"
+            rec = rows[("pgd", f"{N}x{T}x{K}x{L}", family, variant)]
+            assert abs(rec["model_ulp"] - worst) <= 0.006 and abs(rec["units"] - b["units"]) <= 0.006 * b["units"], (what, rec, worst, b["units"])
+
+
+def test_pgd_step_decisions_are_not_close_calls():
+    """rule.steps is compared exactly: the loss after the half-step is far from the rule's first cur_loss (norm(data), pgd.jl:151), so
+    a float32 loss takes the 1.05 / 0.70 decision the oracle takes.  (The five rows with N >= 1000: in the GPU test's own run.)"""
+    from oracle import cmf_oracle as oracle
+
+    for N, T, K, L in [s[:4] for s in ep.SHAPES if s[0] < 1000]:
+        for family in ("W", "H"):
+            W, H, X, mask = ep.make_pgd_problem(N, T, K, L, family)
+            for variant in ep.pgd_variants(N):
+                Wc, Hc = W.copy(order="F"), H.copy(order="F")
+                rule = oracle.PGDUpdate(X, Wc, Hc)
+                loss, masked, penW, penH, nonneg = ep.PGD_VARIANTS[variant]
+                kw = dict(nonneg=nonneg, mask=mask if masked else None, loss=loss)
+                if family == "W":
+                    oracle.pgd_update_motifs(rule, X, Wc, Hc, penaltiesW_sq=penW[0], penaltiesW_abs=penW[1], **kw)
+                else:
+                    oracle.pgd_update_feature_maps(rule, X, Wc, Hc, penaltiesH_sq=penH[0], penaltiesH_abs=penH[1], **kw)
+                assert abs(rule.cur_loss - rule.datanorm) > 1e-3 * rule.datanorm, (N, T, K, L, family, variant, rule.cur_loss, rule.datanorm)
+
+
+@pytest.mark.parametrize("N,T,K,L", [s[:4] for s in ep.SHAPES], ids=TABLE_IDS)
+def test_masked_mu_preconditions(N, T, K, L):
+    """assert_preconditions of tests/test_exact_parity.py on the MASKED sums, and every element keeps an observed term."""
+    rows = _profile_rows()
+    for family in ("W", "H"):
+        W, H, X = ep.make_problem(N, T, K, L, family)
+        a = ep.masked_mu_half(family, W, H, X, ep.mu_mask(N, T))
+        seen = ep.assert_masked_mu_preconditions(a, f"{(N, T, K, L)} {family}")
+        worst = float(ep.ulps(a["new"].astype(np.float32), a["new"]).max())
+        assert worst <= 0.5
+        rec = rows[("masked_mu", f"{N}x{T}x{K}x{L}", family, "mask")]
+        assert rec["max_sum"] == max(a["num"].max(), a["den"].max()) and rec["min_observed"] == seen[seen > 0].min()
+    if (N, T, K, L) == (130, 700, 32, 20):  # the holes: the unit's row of W and the sample's ... have no observed term
+        W, H, X = ep.make_problem(N, T, K, L, "W")
+        a = ep.masked_mu_half("W", W, H, X, ep.holes_mask(N, T))
+        seen = ep.assert_masked_mu_preconditions(a, "holes", holes=True)
+        assert np.all(a["new"][:, N // 2, :] == ep.EPS) and (a["new"] == ep.EPS).sum() == K * L == (seen == 0).sum()
+
+
+def _pgd_mutations(a, X, mask):
+    """name -> the change of G a seam error of the residual conv or of the contraction would make (pgd_half's arrays a)."""
+    family, W, H, E = a["family"], a["W"], a["H"], a["E"]
+    K, N, L = W.shape
+    T = H.shape[1]
+    masked = ep.PGD_VARIANTS[a["variant"]][1]
+    out = {}
+    dE = np.zeros((N, 64))
+    dE[8:12] = -E[8:12, 192:256]  # a 4-row strip of one 64-column block of the residual never stored
+    out["strip"] = ep.contract_cols(family, W, H, dE, 192)
+    lag = min(L, T) - 1
+    if family == "W":  # C2 loses its last lag over one time chunk
+        d = np.zeros(W.shape)
+        d[:, :, lag] = -(H[:, 128:384] @ E[:, 128 + lag:384 + lag].T)
+        out["lag"] = d
+    else:  # C3 loses one k pair of one 32-unit block over one 64-column tile
+        d = np.zeros(H.shape)
+        for l in range(min(L, T)):
+            d[2:4, 64:128] -= W[2:4, :32, l] @ E[:32, 64 + l:128 + l]
+        out["kpair"] = d
+    out["double"] = ep.contract_cols(family, W, H, E[:, 300:301], 300)  # one time row counted twice
+    if masked:
+        raw = ep.pgd_sources(a["variant"].replace("_masked", "").replace("_free", ""), W, H, X, mask)[0][:64, 256:320]
+        dE = np.zeros((N, 64))
+        dE[:64] = raw * mask[:64, 264:328] - E[:64, 256:320]  # the mask tile read one 8-block off
+        out["mask_shift"] = ep.contract_cols(family, W, H, dE, 256)
+        dE = np.zeros((N, 64))
+        dE[:64] = raw * (mask[:64, 256:320] != 0) - E[:64, 256:320]  # the weight read as a 0/1 flag
+        out["mask_flag"] = ep.contract_cols(family, W, H, dE, 256)
+    d = np.zeros(W.shape if family == "W" else H.shape)
+    if family == "W":  # ONE term missing from ONE element
+        k, n, l = 1, 5, 2
+        t = [t for t in np.flatnonzero(H[k] != 0)[3:40] if E[n, t + l] != 0][0]
+        d[k, n, l] = -H[k, t] * E[n, t + l]
+    else:
+        k, t = 1, 100
+        n, l = [(n, l) for l in range(L) for n in np.flatnonzero(W[k, :, l] != 0) if E[n, t + l] != 0][0]
+        d[k, t] = -W[k, n, l] * E[n, t + l]
+    out["term"] = d
+    return out
+
+
+def _mu_mutations(a, X):
+    """name -> (change of num, change of den) for masked_mu_half's arrays a."""
+    family, W, H, M, Xm, est = a["family"], a["W"], a["H"], a["M"], a["Xm"], a["est"]
+    K, N, L = W.shape
+    T = H.shape[1]
+    zero = np.zeros(W.shape if family == "W" else H.shape)
+    out = {}
+    dE = np.zeros((N, 64))
+    dE[8:12] = -est[8:12, 192:256]
+    out["strip"] = (zero, ep.contract_cols(family, W, H, dE, 192))
+    lag = min(L, T) - 1
+    if family == "W":
+        d = np.zeros(W.shape)
+        d[:, :, lag] = -(H[:, 128:384] @ Xm[:, 128 + lag:384 + lag].T)
+        out["lag"] = (d, zero)
+    else:
+        d = np.zeros(H.shape)
+        for l in range(min(L, T)):
+            d[2:4, 64:128] -= W[2:4, :32, l] @ Xm[:32, 64 + l:128 + l]
+        out["kpair"] = (d, zero)
+    out["double"] = (ep.contract_cols(family, W, H, Xm[:, 300:301], 300), zero)
+    conv = ep._conv(W, H)[:64, 256:320]
+    shifted = M[:64, 264:328] != 0  # the mask tile read one 8-block off, for data and est alike
+    dX, dEst = np.zeros((N, 64)), np.zeros((N, 64))
+    dX[:64] = np.where(shifted, X[:64, 256:320], 0.0) - Xm[:64, 256:320]
+    dEst[:64] = np.where(shifted, conv, 0.0) - est[:64, 256:320]
+    out["mask_shift"] = (ep.contract_cols(family, W, H, dX, 256), ep.contract_cols(family, W, H, dEst, 256))
+    dEst = np.zeros((N, 64))
+    dEst[:64] = conv - est[:64, 256:320]  # the mask not read in one tile: est stored unmasked
+    out["mask_unread"] = (zero, ep.contract_cols(family, W, H, dEst, 256))
+    d = zero.copy()
+    if family == "W":
+        k, n, l = 1, 5, 2
+        t = [t for t in np.flatnonzero(H[k] != 0)[3:40] if Xm[n, t + l] != 0][0]
+        d[k, n, l] = -H[k, t] * Xm[n, t + l]
+    else:
+        k, t = 1, 100
+        n, l = [(n, l) for l in range(L) for n in np.flatnonzero(W[k, :, l] != 0) if Xm[n, t + l] != 0][0]
+        d[k, t] = -W[k, n, l] * Xm[n, t + l]
+    out["term"] = (d, zero)
+    return out
+
+
+def _frob(got, ref):
+    return np.linalg.norm(got - ref) / np.linalg.norm(ref)
+
+
+# What a Frobenius-relative 1e-4 on the updated factor -- the bar of tests/test_gpu_masked_mu.py and of the PGD tests of
+# tests/test_gpu_parity.py -- passes on the LARGEST row of the table, measured by the test below, which asserts these very sets.  PGD:
+# every corruption confined to a tile, a chunk or a time row (a unit of G moves an element by alpha, 1e-4 of an entry).  Masked MU: the
+# single term; a strip, a chunk, a tile or a time row still moves the norm by a few 1e-4 at T = 6720 and falls below the bar at config
+# 2's T = 50000 (the comment at FROBENIUS_PASSES above).  The 2 ulp check flags every one on both rows.
+NORMWISE_PASSES_ON_THE_LARGEST_ROW = {
+    ("pgd", "W"): {"strip", "lag", "double", "mask_shift", "mask_flag", "term"},
+    ("pgd", "H"): {"strip", "kpair", "double", "mask_shift", "mask_flag", "term"},
+    ("masked_mu", "W"): {"term"},
+    ("masked_mu", "H"): {"term"},
+}
+
+
+@pytest.mark.parametrize("shape", [SMALL_ROW, LARGEST_ROW], ids=str)
+def test_two_ulp_check_flags_what_a_normwise_check_passes(shape):
+    N, T, K, L = shape
+    blind = {k: set() for k in NORMWISE_PASSES_ON_THE_LARGEST_ROW}
+    for family, names in (("W", "knl"), ("H", "kt")):
+        W, H, X, mask = ep.make_pgd_problem(N, T, K, L, family)
+        for variant in ("square", "abs_masked"):
+            a = ep.pgd_half(variant, family, W, H, X, mask)
+            assert ep.ulps(ep.pgd_f32_model(a, False), a["new"]).max() <= ULP_BAR
+            for name, dG in _pgd_mutations(a, X, mask).items():
+                assert np.any(dG != 0), (name, variant, family)
+                bad = ep.pgd_finish(dict(a, G=a["G"] + dG))
+                got = ep.pgd_f32_model(bad, False)
+                u = ep.ulps(got, a["new"])
+                assert u.max() > ULP_BAR and ep.first_bad(u > ULP_BAR, names), (name, variant, family, shape, u.max())
+                if _frob(got, a["new"]) < 1e-4:
+                    blind[("pgd", family)].add(name)
+        W, H, X = ep.make_problem(N, T, K, L, family)
+        a = ep.masked_mu_half(family, W, H, X, ep.mu_mask(N, T))
+        x = W if family == "W" else H
+        for name, (dnum, dden) in _mu_mutations(a, X).items():
+            assert np.any(dnum != 0) or np.any(dden != 0), (name, family)
+            got = np.maximum(x * ((a["num"] + dnum) / ((((a["den"] + dden) + ep.L1) + (2.0 * ep.L2) * x) + ep.EPS)), ep.EPS).astype(np.float32)
+            u = ep.ulps(got, a["new"])
+            assert u.max() > ULP_BAR and ep.first_bad(u > ULP_BAR, names), (name, family, shape, u.max())
+            if _frob(got, a["new"]) < 1e-4:
+                blind[("masked_mu", family)].add(name)
+    print("a Frobenius-relative 1e-4 passes:", {k: sorted(v) for k, v in blind.items()})
+    if shape == LARGEST_ROW:
+        assert blind == NORMWISE_PASSES_ON_THE_LARGEST_ROW
