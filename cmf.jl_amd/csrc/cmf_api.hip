@@ -1279,6 +1279,8 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
                     for (const cmf_handle_s *s : h->group->sh) *value += (s != h) ? s->launches[c] : 0;
                 return CMF_OK;
             }
+        for (int c = 0; c < HL_NCLS; ++c) // the HALS entries' table (a HALS handle is never a group)
+            if (std::strcmp(name + 9, kHalsLaunchNames[c]) == 0) { *value = h->hals_launches[c]; return CMF_OK; }
         return fail(CMF_ERR_ARG, "unknown launch path '%s'", name + 9);
     }
     if (h->group) { // host cost of the pipelined iterations of a group (reading a counter resets nothing)

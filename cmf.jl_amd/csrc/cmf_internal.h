@@ -165,6 +165,27 @@ static const char *const kLaunchNames[] = {
     "halo_pack2_kernel", "halo_unpack2_kernel", "halo_pack3_kernel", "halo_unpack3_kernel"};
 static_assert(sizeof(kLaunchNames) / sizeof(kLaunchNames[0]) == LA_NCLS, "one name per launch path");
 
+// Launch paths of the HALS entries (cmf_rules.hip), a table of its own answered by the same cmf_get_counter "launches:<name>" and
+// counted the same way: on the host at the launch site, instances and forms separately (a chased persistent sweep with three pullers
+// per row adds one to "hals_h_persist_kernel", "hals_h_persist_kernel:P3", "hals_h_persist_kernel:chased" and "conv3_chase_kernel").
+// tests/test_exact_problems.py keeps exact_problems.HALS_LAUNCH_PATHS equal to this list; tests/test_gpu_exact_hals.py reaches every name.
+enum { HL_W_REG = 0, /* + 10: NQ 2 .. 32 (kHalsNQ) */ HL_W_GEN = HL_W_REG + 10,
+       HL_G_RESID, HL_G_DIFF, HL_G_SPEC, HL_W_SPECULATE,
+       HL_P_INIT_DEN, HL_P_INIT_RESID, HL_P_INIT_SNAP,
+       HL_PERSIST, /* + 4: P 1 .. 4 */ HL_PERSIST_CHASED = HL_PERSIST + 5, HL_CHASE, HL_CHASE_REST,
+       HL_STAGE, HL_STAGE_LAG2, HL_STAGE_LAG3, HL_ROW_GEN, HL_PUSH_GEN, HL_NCLS };
+static const int kHalsNQ[10] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};
+static const char *const kHalsLaunchNames[] = {
+    "hals_w_sweep_reg_kernel<2>", "hals_w_sweep_reg_kernel<4>", "hals_w_sweep_reg_kernel<6>", "hals_w_sweep_reg_kernel<8>", "hals_w_sweep_reg_kernel<10>",
+    "hals_w_sweep_reg_kernel<12>", "hals_w_sweep_reg_kernel<16>", "hals_w_sweep_reg_kernel<20>", "hals_w_sweep_reg_kernel<24>", "hals_w_sweep_reg_kernel<32>",
+    "hals_w_sweep_gen_kernel",
+    "hals_g:residual", "hals_g:difference", "hals_g:speculated", "hals_w_speculate",
+    "hals_p_init_kernel:den", "hals_p_init_kernel:residual", "hals_p_init_kernel:snapshot",
+    "hals_h_persist_kernel", "hals_h_persist_kernel:P1", "hals_h_persist_kernel:P2", "hals_h_persist_kernel:P3", "hals_h_persist_kernel:P4",
+    "hals_h_persist_kernel:chased", "conv3_chase_kernel", "conv3_chase_kernel:rest",
+    "hals_h_stage_kernel", "hals_h_stage_kernel:lag2", "hals_h_stage_kernel:lag3", "hals_h_row_gen_kernel", "hals_h_push_gen_kernel"};
+static_assert(sizeof(kHalsLaunchNames) / sizeof(kHalsLaunchNames[0]) == HL_NCLS, "one name per HALS launch path");
+
 // mu_div of a handle under cmf_mu_set_beta_divergence: behind the kinds of cmf_mu_set_divergence, which does not take it
 #define CMF_DIV_BETA 3
 
@@ -314,6 +335,7 @@ struct cmf_handle_s {
     int prof_every = 1;          // bracket every n-th launch of a class (option value n)
     int prof_seen[32] = {0};
     int64_t launches[LA_NCLS] = {0}; // cmf_get_counter "launches:<name>" (kLaunchNames)
+    int64_t hals_launches[HL_NCLS] = {0}; // ... of the HALS entries (kHalsLaunchNames)
     struct ProfRec { hipEvent_t a, b; int cls; };
     unsigned prof_mask = 0; // option "profile_mask"
     std::vector<ProfRec> prof_recs;

@@ -170,6 +170,7 @@ int hals_w_speculate(cmf_handle_s *h)
     if (h->est_kind != EST_RESID || h->hals_gram == 1 || h->group) return CMF_OK;
     CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden));
     CMFTRY(compute_hh(h));
+    h->hals_launches[HL_W_SPECULATE] += 1;
     h->hals_spec_gen = h->est_gen;
     return CMF_OK;
 }
@@ -191,6 +192,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
         CMFTRY(launch_gram_w(h, h->hals_HH, h->numden + LKN));
         G = h->numden + LKN;
         Gsub = h->numden;
+        h->hals_launches[HL_G_DIFF] += 1;
     } else {
         // (both already enqueued behind the loss of the update_feature_maps! before, for exactly this state: hals_w_speculate)
         const bool spec = h->hals_spec_gen >= 0 && h->hals_spec_gen == h->est_gen && h->est_kind == EST_RESID;
@@ -201,6 +203,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
             CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden));
             CMFTRY(compute_hh(h));
         }
+        h->hals_launches[spec ? HL_G_SPEC : HL_G_RESID] += 1;
     }
     // the K*L sequential column updates, k outer / lag inner (hals.jl:90-97)
     if (h->hals_w_general) { // L * Kpad beyond the register-resident sweep: one workgroup per unit, the state in LDS
@@ -210,6 +213,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
         hipLaunchKernelGGL(hals_w_sweep_gen_kernel, dim3(d.N), dim3(256), lds_g, h->stream, h->Wt, h->Wn, G, Gsub, h->hals_HH,
                            d.N, d.K, d.L, d.Np, d.K32, h->hals_NpH, (float)l1W, (float)l2W);
         KCHK("hals_w_sweep_gen_kernel");
+        h->hals_launches[HL_W_GEN] += 1;
         set_est(h, EST_NONE);
         return CMF_OK;
     }
@@ -232,6 +236,8 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
     else SWEEP(32, 4);
 #undef SWEEP
     KCHK("hals_w_sweep_reg_kernel");
+    for (int i = 0; i < 10; ++i)
+        if (nq <= kHalsNQ[i]) { h->hals_launches[HL_W_REG + i] += 1; break; }
     set_est(h, EST_NONE);
     return CMF_OK;
 }
@@ -274,6 +280,8 @@ static int hals_h_project(cmf_handle_s *h, bool contract, bool snapshot = false)
                            h->tc_S1, d.Tl, d.K32, h->hals_TPp, h->H, h->Ht, snap, d.TP, d.PADL, flags, nflags);
     }
     KCHK("hals_p_init_kernel");
+    h->hals_launches[gram ? HL_P_INIT_DEN : HL_P_INIT_RESID] += 1;
+    if (snap) h->hals_launches[HL_P_INIT_SNAP] += 1;
     return CMF_OK;
 }
 
@@ -308,6 +316,8 @@ static int hals_h_sweep_stage(cmf_handle_s *h, const HalsRowParams &q)
         hipLaunchKernelGGL(hals_h_stage_kernel, grid, dim3(256), 0, h->stream, sp);
         KCHK("hals_h_stage_kernel");
     }
+    h->hals_launches[HL_STAGE] += 1; // (per sweep: its nstages launches are one path)
+    h->hals_launches[sp.lag == 3 ? HL_STAGE_LAG3 : HL_STAGE_LAG2] += 1;
     return CMF_OK;
 }
 
@@ -325,10 +335,12 @@ static int hals_h_sweep_general(cmf_handle_s *h, HalsRowParams q)
         q.D = h->hals_D + (size_t)k * q.TPp;
         hipLaunchKernelGGL(hals_h_row_gen_kernel, dim3(1), dim3(64), lds, h->stream, q);
         KCHK("hals_h_row_gen_kernel");
+        h->hals_launches[HL_ROW_GEN] += 1;
         if (k + 1 < d.K) {
             hipLaunchKernelGGL(hals_h_push_gen_kernel, dim3((d.Tl + 255) / 256, d.K - 1 - k), dim3(256), 0, h->stream, h->hals_PT, q.D, h->hals_GW,
                                h->hals_GE, k, d.Tl, d.L, d.K32, q.TPp, q.ne, q.t_edge0);
             KCHK("hals_h_push_gen_kernel");
+            h->hals_launches[HL_PUSH_GEN] += 1;
         }
     }
     return CMF_OK;
@@ -352,6 +364,8 @@ int hals_persist_launch(cmf_handle_s *h, const HalsRowParams &q, int debug, bool
     if (clear_flags) HIPCHK(hipMemsetAsync(h->hals_flags, 0, nflags * sizeof(int), h->stream));
     hipLaunchKernelGGL(hals_h_persist_kernel, dim3(d.K + (d.K - 1) * pp.P), dim3(1024), lds, h->stream, pp);
     KCHK("hals_h_persist_kernel");
+    h->hals_launches[HL_PERSIST] += 1;
+    if (pp.P >= 1 && pp.P <= 4) h->hals_launches[HL_PERSIST + pp.P] += 1;
     return CMF_OK;
 }
 
@@ -417,6 +431,8 @@ static int hals_persist_chased(cmf_handle_s *h, const HalsRowParams &q, int ra)
     if (rc == CMF_OK) rc = launch_conv_rows<CONV_RESID>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA);
     h->stream = keep;
     CMFTRY(rc);
+    h->hals_launches[HL_PERSIST_CHASED] += 1;
+    h->hals_launches[HL_CHASE] += 1;
     HIPCHK(hipEventRecord(h->hals_ev[1], h->hals_sA));
     HIPCHK(hipEventRecord(h->hals_ev[2], h->hals_sB));
     HIPCHK(hipStreamWaitEvent(keep, h->hals_ev[1], 0)); // H is final behind the pipeline; the chasing launch is joined in front of the
@@ -435,7 +451,10 @@ int hals_resid_and_loss(cmf_handle_s *h, double *sumsq)
     h->hals_chased_rows = h->hals_chased_partials = 0;
     if (ra <= 0) return resid_and_loss(h, sumsq);
     int nB = 0;
-    if (ra < rows_t) CMFTRY(launch_conv_rows<CONV_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
+    if (ra < rows_t) {
+        CMFTRY(launch_conv_rows<CONV_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
+        h->hals_launches[HL_CHASE_REST] += 1;
+    }
     HIPCHK(hipStreamWaitEvent(h->stream, h->hals_ev[2], 0));
     h->conv_partials = nA + nB;
     set_est(h, EST_RESID);

@@ -16,7 +16,8 @@ preconditions() bounds every num / den by 2^20, so such an error is at least 8 u
 The shape table SHAPES is shared with tests/test_gpu_divergence_paths.py, which holds the divergence forms of the rule to their fp64
 restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below),
 and with tests/test_gpu_exact_masked_mu.py and tests/test_gpu_exact_pgd.py, which hold the MU rule under a 0/1 mask and the PGD rule to
-their references on it (the last section: mu_mask, make_pgd_problem, pgd_half, pgd_preconditions).
+their references on it (mu_mask, make_pgd_problem, pgd_half, pgd_preconditions).  The last section holds the HALS sweeps' own table
+(HALS_SHAPES), the mirror of their plan, their element-wise check and the mutations of their restatement (tests/test_gpu_exact_hals.py).
 """
 import numpy as np
 
@@ -742,3 +743,402 @@ def assert_masked_mu_preconditions(a, what, holes=False):
     assert np.all(a["new"][seen == 0] == EPS)
     seen[~live] = -1  # (no term at all, mask or not: lags beyond the recording, components without a column)
     return seen
+
+
+# ---- the HALS rule on these problems (tests/test_gpu_exact_hals.py; CPU half in tests/test_exact_problems.py) ----------------------
+# Every contraction the HALS rule makes on an integer problem -- G = resid * H_unfold' from the stored residual or as denomW - numW,
+# HH and the lag correlations it is assembled from, P = transconv(W, resid) or denomH - numH, the lag Grams PW and the taps GW / GE --
+# is an integer sum below 2^24 in absolute values (hals_preconditions): exact in fp32 in any order, so the projections reach the sweeps
+# bit-identical on every path and under every value of hals_gram.  What is left is the rounding INSIDE the sequential recurrences.
+# It is measured, not derived: hals_gram_form.w_half / h_half with the sweep's state in float32 against the same in fp64, per element
+# in units of the fp32 spacing at scale = max(|value before the clamp|, |old value|).  Each half runs on the family whose updated factor
+# is dense (W on "W", H on "H"): with the other factor dense the Gauss-Seidel sweep amplifies rounding a thousandfold and no bar near
+# rounding exists.  The bar of a half is 4 times the worst model error over the table, and at least 8 (a kernel associates the cross-row
+# sums differently, fuses multiply-adds, and multiplies by a reciprocal where the model divides); profiles/exact_hals.txt records it
+# (tools/exact_hals_profile.py) and tests/test_exact_problems.py recomputes it.
+HALS_LAUNCH_PATHS = [
+    "hals_w_sweep_reg_kernel<2>", "hals_w_sweep_reg_kernel<4>", "hals_w_sweep_reg_kernel<6>", "hals_w_sweep_reg_kernel<8>",
+    "hals_w_sweep_reg_kernel<10>", "hals_w_sweep_reg_kernel<12>", "hals_w_sweep_reg_kernel<16>", "hals_w_sweep_reg_kernel<20>",
+    "hals_w_sweep_reg_kernel<24>", "hals_w_sweep_reg_kernel<32>", "hals_w_sweep_gen_kernel",
+    "hals_g:residual", "hals_g:difference", "hals_g:speculated", "hals_w_speculate",
+    "hals_p_init_kernel:den", "hals_p_init_kernel:residual", "hals_p_init_kernel:snapshot",
+    "hals_h_persist_kernel", "hals_h_persist_kernel:P1", "hals_h_persist_kernel:P2", "hals_h_persist_kernel:P3", "hals_h_persist_kernel:P4",
+    "hals_h_persist_kernel:chased", "conv3_chase_kernel", "conv3_chase_kernel:rest",
+    "hals_h_stage_kernel", "hals_h_stage_kernel:lag2", "hals_h_stage_kernel:lag3", "hals_h_row_gen_kernel", "hals_h_push_gen_kernel",
+]
+HALS_NQ = (2, 4, 6, 8, 10, 12, 16, 20, 24, 32)  # the instances of hals_w_sweep_reg_kernel<NQ, WD>
+HALS_PMAX = 4
+HALS_REGS = [(0.0, 0.0), (L1, L2)]
+HALS_BAR_FACTOR, HALS_BAR_FLOOR = 4.0, 8.0
+
+
+def hals_plan(N, T, K, L, cfg=None, n_cu=N_CU):
+    """cmf_rules.hip hals_plan / hals_w_impl / hals_h_project / hals_chase_rows restated: a dict of nq (the 64-lane slots the state
+    L * K32 needs), NQ (the register instance, None under the general W sweep), pad_slots (NQ - nq), w_general, h_general, P (pullers
+    per row; 0: the stage pipeline), nblk (64-column blocks of a row), chase (tile rows of the residual conv that chase the pipeline)
+    and gram_window (the Gram form of P fits its LDS window), for the options of cfg."""
+    cfg = cfg or {}
+    K32 = rup(K, 32)
+    general, persist, chase = cfg.get("hals_general", 0), cfg.get("hals_persist", 1), cfg.get("hals_chase", -1)
+    p = dict(nq=(L * K32 + 63) // 64, nblk=(T + 63) // 64)
+    p["w_general"] = bool(L * K32 > 2048 or 4 * K * L * 2 * 4 > 64 * 1024 or general & 1)
+    p["h_general"] = bool(L > 64 or general & 2)
+    p["NQ"] = None if p["w_general"] else min(q for q in HALS_NQ if q >= p["nq"])
+    p["pad_slots"] = 0 if p["w_general"] else p["NQ"] - p["nq"]
+    P = 0
+    if persist != 0 and not p["h_general"]:
+        P = min(HALS_PMAX, (n_cu - K) // (K - 1)) if K > 1 else 1
+        if persist > 1:
+            P = min(P, persist)
+        if ((K - 1) * (2 * L - 1 + 64 + 2 * (L - 1)) + 1024) * 4 > 120 * 1024 or (P < 2 and K > 1):
+            P = 0
+        small_k = K <= 16 and L <= 64
+        if P == 4 and persist == 1 and chase != 0 and K % 32 == 0 and not small_k and T >= 4096:
+            P = 3
+    p["P"] = P
+    rows, ra = (T + 63) // 64, 0
+    if chase != 0 and P > 0 and K % 32 == 0 and cfg.get("hals_gram", 2) != 1 and n_cu // 8 - (K + (K - 1) * P + 7) // 8 >= 4 and rows >= 64:
+        pct = chase
+        if pct < 0:
+            conv_ms = 2.0 * K * N * (L * T) / (0.87 * 157.3e12) * 1e3
+            pipe_ms = (T + (K - 1) * (L - 1)) * 43.0 / 2.4e9 / 0.63 * 1e3
+            share = (n_cu // 8 - (K + (K - 1) * P + 7) // 8) / (n_cu // 8) * (0.76 * pipe_ms) / conv_ms
+            pct = int(max(10.0, min(95.0, 110.0 * share)))
+        ra = min(rows, rows * min(pct, 100) // 100)
+    p["chase"] = ra
+    p["gram_window"] = K32 * (64 + 2 * (L - 1)) * 4 <= 96 * 1024
+    return p
+
+
+_SWEEPS = [dict(), dict(hals_persist=2), dict(hals_persist=3), dict(hals_persist=0, hals_seg=256), dict(hals_persist=0, hals_seg=256, hals_lag=3),
+           dict(hals_general=3)]
+# (N, T, K, L, sweep configurations, why); every configuration runs under hals_gram = 2, 0 and 1
+HALS_SHAPES = [
+    # the W sweep's register instances (N odd: the guard of the last unit; 37: five workgroups), the H pipelines beside them
+    (37, 150, 5, 4, [dict(), dict(hals_general=1)], "NQ 2; five rows, 3 blocks for 4 pullers, T no multiple of 64; the general W sweep forced"),
+    (37, 768, 32, 8, [dict(), dict(hals_persist=2)], "NQ 4; T a multiple of 64"),
+    (37, 700, 32, 12, [dict()], "NQ 6; L - 1 >= 8: a second chunk of edge taps"),
+    (37, 700, 32, 16, [dict()], "NQ 8"),
+    (37, 700, 32, 20, _SWEEPS, "NQ 10; every H pipeline: 4, 2, 3 pullers, the stage pipeline over three segments at lag 2 and 3, both general sweeps forced"),
+    (37, 700, 32, 24, [dict()], "NQ 12"),
+    (37, 700, 32, 32, [dict()], "NQ 16"),
+    (37, 1300, 64, 20, [dict(), dict(hals_persist=2), dict(hals_persist=0)], "NQ 20 (ring 4 deep); K = 64: 3 pullers, D staged through LDS in more than one piece"),
+    (37, 1300, 64, 24, [dict()], "NQ 24"),
+    (37, 1300, 64, 32, [dict()], "NQ 32, all slots live"),
+    (133, 700, 33, 3, [dict(), dict(hals_general=2)], "NQ 4 with 3 slots live; two k blocks; the general H sweep forced (half of X zero: HALS_XZERO)"),
+    (37, 700, 33, 31, [dict()], "NQ 32 with 31 slots live"),
+    (37, 1300, 64, 18, [dict()], "NQ 20 with 18 slots live"),
+    (37, 1300, 64, 40, [dict()], "L * K32 = 2560: the general W sweep by the plan"),
+    (37, 700, 18, 20, [dict(), dict(hals_persist=3)], "K = 18"),
+    # hals_hh_kernel's four ways to an entry, short recordings, the window lengths
+    (9, 5, 2, 8, [dict(), dict(hals_persist=0)], "T < L: every column an edge column, rows of H_unfold that are all zero"),
+    (9, 30, 2, 20, [dict()], "L < T < 2 L: HH summed directly"),
+    (9, 80, 1, 20, [dict()], "T <= 64 + L; K = 1: one sweeper, one puller slot, no cross-row term"),
+    (9, 50, 2, 1, [dict(), dict(hals_persist=0)], "L = 1: no edge, no lag; T < 64.  No clamp share: at L = 1 no shape and no range of X has one (HALS_NO_CLAMP_AT_L)"),
+    (9, 200, 4, 64, [dict(), dict(hals_persist=0)], "L = 64: the widest on-chip window; NQ 32"),
+    (9, 200, 3, 70, [dict()], "L = 70: both general sweeps by the plan"),
+    # the residual conv chasing the persistent pipeline (the shape of test_hals_residual_conv_chasing_the_row_pipeline)
+    (130, 9000, 32, 20, [dict(hals_chase=65), dict(hals_chase=0)], "the chased form at 65 per cent (3 pullers), and 4 pullers without it; many slabs of the lag correlations"),
+    # past the Gram form's LDS window (below)
+    (29, 1200, 129, 46, [dict()], "K32 (64 + 2 (L - 1)) 4 = 98560 > 96 KB: P from the residual under every hals_gram; 129 rows: the stage pipeline by the plan; the general W sweep"),
+]
+# The last row lies past the LDS window of the Gram form of P, K32 * (64 + 2 (L - 1)) * 4 > 96 KB (160 * 154 * 4 = 98560): hals_h_project
+# must then form P from the transposed residual under hals_gram = 2 and 1 as well ("hals_p_init_kernel:residual", the same bits as
+# hals_gram = 0) -- if its condition were wrong, gram_denom_h would refuse the shape.  Shapes with fewer components are past the window
+# too ((65, 98), (33, 162), (3, 354)), but est sums L entries of 1 and 2 and with L near 100 it lies above X in {0 ... 40} nearly
+# everywhere: fewer than 9 % of the elements stay positive, and a wider X takes the float32 model to 110 ... 170 units, which would
+# quadruple every row's bar.  (129, 46) keeps X and meets every precondition.
+
+
+# est of a row sums min(L, T) entries of 1 and 2: with three lags it stays below 6, X in {0 ... 40} lies above it nearly everywhere
+# and the clamp hardly acts (3 % of W).  On such a row every z-th entry of X, chosen by other bits of its hash, is 0 (a narrower range
+# of X instead makes every sum a small integer and the clamp a tie on hundreds of elements).
+HALS_XZERO = {(133, 700, 33, 3): 2}
+# At L = 1 with one unit entry per column (per unit) the least-squares problem decouples: every updated element is a MEAN of entries of
+# X, never negative, whatever N, T, K and the range of X are.  Under l1 = l2 = 0 an element sits on the clamp only where that mean is
+# exactly 0 -- a tie, not a decision, and one of the close calls the same list of conditions forbids; under l1 > 0 sparse X would clamp
+# the elements whose sum of X is below l1, but the row runs under both regulariser pairs and must meet the conditions under both.  So no
+# shape meets the clamp share at L = 1, and it is not asked there (assert_hals_preconditions); every other condition is.
+HALS_NO_CLAMP_AT_L = 1
+
+
+def make_hals_problem(N, T, K, L, family, seed=0):
+    """make_problem's integer factors and X in {0 ... XMAX} (HALS_XZERO: with the row's share of zeros)."""
+    W, H, X = make_problem(N, T, K, L, family, seed)
+    z = HALS_XZERO.get((N, T, K, L))
+    if z is not None:
+        X[(_data_hash(N, T, seed) >> np.uint64(20)) % np.uint64(z) != 0] = 0.0
+    return W, H, X
+
+
+def hals_half(family, W, H, X, reg, dtype=np.float64, corrupt=None, eps=None):
+    """hals_gram_form.w_half (family "W") or h_half ("H") under the regularisers reg = (l1, l2)."""
+    import hals_gram_form as hg
+    from oracle import cmf_oracle
+
+    return (hg.w_half if family == "W" else hg.h_half)(cmf_oracle, W, H, X, reg[0], reg[1], dtype, corrupt, eps)
+
+
+def hals_units(got, a):
+    """|got - a["new"]| in units of the fp32 spacing at a["scale"], element-wise (a: w_half / h_half in fp64); not finite -> inf."""
+    sp = np.spacing(a["scale"].astype(np.float32)).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        u = np.abs(np.asarray(got, dtype=np.float64) - a["new"]) / sp
+    return np.where(np.isfinite(u), u, np.inf)
+
+
+def hals_excused(a, bar):
+    """Elements whose value before the clamp is within the bar of 0: their zero pattern is not decided (they still meet the bar).
+    Not among them: the steps whose squared norm is 0 (a lag beyond the recording, a component without an entry in the window).  Their
+    projection is an empty sum, exactly 0 on every path and never added to, so the value before the clamp is -l1 / (eps + l2) in any
+    arithmetic: 0 or negative, and the element is 0."""
+    return (np.abs(a["pre"]) <= bar * np.spacing(a["scale"].astype(np.float32)).astype(np.float64)) & (a["diag"] != 0)
+
+
+def hals_contractions(family, a):
+    """name -> the largest sum of ABSOLUTE values of every contraction in front of the family's sweep, both forms of the projections
+    (a: the fp64 half of the family).  Below 2^24 every partial sum of it is an exact fp32 integer in any order."""
+    from oracle import cmf_oracle
+
+    W, H, R = a["W"], a["H"], a["R"]
+    K, N, L = W.shape
+    T = H.shape[1]
+    est = R + (cmf_oracle.tensor_conv(W, H) - R)  # (= est: R is est - X)
+    X = est - R
+    out = dict(est=est.max(), X=X.max())
+    if family == "W":
+        Hu = a["Hu"]
+        out.update(G=(np.abs(R) @ Hu.T).max(), denomW=(est @ Hu.T).max(), numW=(X @ Hu.T).max(), HH=a["HH"].max(),
+                   corr=max((H[:, : T - d] @ H[:, d:].T).max() for d in range(min(L, T))))
+    else:
+        PW = a["PW"]
+        out.update(P=cmf_oracle.tensor_transconv(W, np.abs(R)).max(), denomH=cmf_oracle.tensor_transconv(W, est).max(),
+                   numH=cmf_oracle.tensor_transconv(W, X).max(), PW=PW.max(),
+                   taps=max(PW[np.arange(max(0, e), min(L, L + e)), :, np.arange(max(0, e), min(L, L + e)) - e, :].sum(axis=0).max() for e in range(-(L - 1), L)))
+    return {k: float(v) for k, v in out.items()}
+
+
+def hals_preconditions(family, a, bar):
+    """From the arrays of the fp64 half: exact (every contraction < 2^24), the shares of the updated elements strictly positive (pos) and
+    exactly on the clamp (clamp) -- for the H half also among the last L - 1 columns (edge_pos, edge_clamp) --, close (the elements
+    within the bar of the clamp: excused from the zero-pattern check, counted) and min_pre (the closest |pre| / spacing of the others,
+    the steps of norm 0 apart: hals_excused)."""
+    c = hals_contractions(family, a)
+    new, L = a["new"], a["W"].shape[2]
+    b = dict(abs_sum=max(c.values()), exact=max(c.values()) < EXACT, pos=float((new > 0).mean()), clamp=float((new == 0).mean()))
+    if family == "H" and L > 1:
+        edge = new[:, max(0, new.shape[1] - L + 1):]
+        b.update(edge_pos=float((edge > 0).mean()), edge_clamp=float((edge == 0).mean()))
+    ex = hals_excused(a, bar)
+    b["close"] = int(ex.sum())
+    sp = np.spacing(a["scale"].astype(np.float32)).astype(np.float64)
+    b["min_pre"] = float((np.abs(a["pre"]) / sp)[~ex & (a["diag"] != 0)].min())
+    return b
+
+
+def assert_hals_preconditions(b, size, L, what):
+    assert b["exact"], f"{what}: a contraction reaches {b['abs_sum']:.0f} >= 2^24"
+    for key in ("pos", "edge_pos"):
+        assert b.get(key, 1.0) >= 0.15, f"{what}: {key} = {b[key]:.3f}: fewer than 15 % of the updated elements are strictly positive"
+    for key in ("clamp", "edge_clamp"):
+        assert L == HALS_NO_CLAMP_AT_L or b.get(key, 1.0) >= 0.05, f"{what}: {key} = {b[key]:.3f}: fewer than 5 % of the updated elements sit on the clamp"
+    assert b["close"] <= 0.001 * size, f"{what}: {b['close']} of {size} elements decide their clamp within the bar"
+
+
+def read_hals_profile(path):
+    """{"row": {(shape, family, reg): {key: value}}, "bar": {"W": .., "H": .., "loss": ..}, "gpu": {name: value}} of profiles/exact_hals.txt."""
+    out = dict(row={}, bar={}, gpu={})
+    for line in open(path):
+        f = line.split()
+        if f and f[0] == "row":
+            out["row"][(f[1], f[2], f[3])] = {kv.split("=")[0]: float(kv.split("=")[1]) for kv in f[4:]}
+        elif f and f[0] in ("bar", "gpu") and len(f) == 3:
+            out[f[0]][f[1]] = float(f[2])
+    return out
+
+
+def hals_bars(path=None):
+    """(bar of the W half, bar of the H half, relative bar of the loss: 4 times the worst float32 model, no floor) from the `row` lines of profiles/exact_hals.txt."""
+    import os
+
+    path = path or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exact_hals.txt")
+    rows = read_hals_profile(path)["row"]
+    bar = {f: max(HALS_BAR_FLOOR, HALS_BAR_FACTOR * max(v["model"] for k, v in rows.items() if k[1] == f)) for f in ("W", "H")}
+    loss = HALS_BAR_FACTOR * max(v["loss_model"] for k, v in rows.items() if k[1] == "H")
+    return bar["W"], bar["H"], loss
+
+
+def check_hals(got, a, bar, names, launches=""):
+    """(worst units, message or None): every element of got within the bar of a["new"] in hals_units, and the zero pattern a["new"]'s
+    apart from the excused elements; the message names the worst element as check_elementwise does."""
+    u = hals_units(got, a)
+    worst = float(u.max())
+    msg = None
+    if not worst <= bar:
+        i = np.unravel_index(np.argmax(u), u.shape)
+        msg = (f"{u[i]:.1f} units (bar {bar:g}) at {first_bad(u == u[i], names)}: got {got[i]!r}, want {a['new'][i]!r} (old {a['old'][i]!r}, before the clamp "
+               f"{a['pre'][i]!r}; {int((~(u <= bar)).sum())} elements over the bar); launches {launches}")
+    else:
+        bad = ((np.asarray(got) > 0) != (a["new"] > 0)) & ~hals_excused(a, bar)
+        if bad.any():
+            i = tuple(np.argwhere(bad)[0])
+            msg = (f"zero pattern differs at {first_bad(bad, names)}: got {got[i]!r}, want {a['new'][i]!r} (before the clamp {a['pre'][i]!r}; "
+                   f"{int(bad.sum())} elements); launches {launches}")
+    return worst, msg
+
+
+# ---- what a local error of a sweep kernel does to the restatement (the mutation tests of tests/test_exact_problems.py) -------------
+def _best(cands):
+    """The candidate (score, ...) with the largest score, or None."""
+    cands = [c for c in cands if c[0] > 0]
+    return max(cands, key=lambda c: c[0]) if cands else None
+
+
+def hals_w_mutations(a, plan):
+    """name -> corrupt hook for hals_gram_form.w_half: the local errors of a W sweep kernel, each at a site where the reference (a: the
+    fp64 half) says it matters -- the unit with the largest change at the step, a later column that is not clamped.  A name is absent
+    where the row has no such site (L = 1: HH is diagonal, no step adds to a later one's state)."""
+    W = a["W"]
+    K, N, L = W.shape
+    HH, d, live = a["HH"], a["new"] - a["old"], a["pre"] > 0
+    order = lambda j: (j % K) * L + j // K  # the step at which column j = l K + k is swept
+    out = {}
+    k = K // 2
+    cands = []
+    for kk in [k] + [x for x in range(K) if x != k]:  # one term d[n] HH[j, j2] of one step never added to G[n, j2]
+        for l in range(L):
+            j = l * K + kk
+            n = int(np.argmax(np.abs(d[kk, :, l])))
+            for j2 in np.flatnonzero(HH[j]):
+                k2, l2 = j2 % K, j2 // K
+                if order(j2) > order(j) and live[k2, n, l2]:
+                    cands.append((abs(d[kk, n, l]) * HH[j, j2] / HH[j2, j2], order(j), int(j2)))
+        if _best(cands):
+            break  # (the middle row where it has a site; on the shortest recordings another row)
+    best = _best(cands)
+    if best:
+        _, s_at, j_drop = best
+
+        def term(stage, x, s_at=s_at, j_drop=j_drop):
+            if stage == "step" and x["s"] == s_at:
+                x["row"] = x["row"].copy()
+                x["row"][j_drop] = 0
+
+        out["term"] = term
+    cands = []
+    for s in list(range(k * L, min(k * L + L, K * L - 1))) + list(range(K * L - 1)):  # one unit's update of step s + 1 made with the HH row of step s
+        if s == 0 and _best(cands):
+            break  # (the middle row has a site)
+        (k0, l0), (k1, l1) = divmod(s, L), divmod(s + 1, L)
+        j0, j1 = l0 * K + k0, l1 * K + k1
+        n = int(np.argmax(np.abs(d[k1, :, l1])))
+        later = np.array([order(j2) > s + 1 for j2 in range(K * L)])
+        cands.append((abs(d[k1, n, l1]) * np.abs(HH[j0] - HH[j1])[later].sum(), s + 1, n, j0))
+    best = _best(cands)
+    if best:
+        _, s_at, n_at, j_old = best
+
+        def stale(stage, x, s_at=s_at, n_at=n_at, j_old=j_old):
+            if stage == "step" and x["s"] == s_at:
+                x["row_unit"] = (n_at, HH[j_old])
+
+        out["stale_row"] = stale
+    if plan["pad_slots"] > 0:  # the last live slot taken for padding at one step: its 64 columns miss that step's update
+        K32 = rup(K, 32)
+        cols = np.array([l * K + kk for l in range(L) for kk in range(K) if (l * K32 + kk) // 64 == plan["nq"] - 1])
+        cands = []
+        for l in range(L):
+            j = l * K + k
+            later = np.array([order(j2) > order(j) for j2 in cols])
+            n = int(np.argmax(np.abs(d[k, :, l])))
+            cands.append((abs(d[k, n, l]) * HH[j, cols[later]].sum() if later.any() else 0.0, order(j)))
+        best = _best(cands)
+        if best:
+            s_at = best[1]
+
+            def slot(stage, x, s_at=s_at):
+                if stage == "step" and x["s"] == s_at:
+                    x["row"] = x["row"].copy()
+                    x["row"][cols] = 0
+
+            out["slot"] = slot
+    return out
+
+
+def hals_h_mutations(a):
+    """name -> corrupt hook for hals_gram_form.h_half: the local errors of an H sweep kernel, at sites the reference says matter.
+    Absent where the row has no such site: K = 1 has no cross-row term, L = 1 no edge, no push and (one entry per (n, l)) no cross-row
+    tap; "cross_interior" needs a 64-column block that is not the last."""
+    import hals_gram_form as hg
+
+    W, H = a["W"], a["H"]
+    K, N, L = W.shape
+    T = H.shape[1]
+    D, live, nrm = a["new"] - a["old"], a["pre"] > 0, a["diag"]
+    te0 = max(0, T - L + 1)
+    Lt = np.minimum(L, T - np.arange(T))
+    out = {}
+    if L > 1:
+        # a truncated window taken at full length: the norm and the taps of one of the last L - 1 columns
+        full = np.array([hg.window_taps(a["PW"], k)[L - 1, k, L - 1] for k in range(K)])
+        cands = [(abs(full[k] - nrm[k, t]) * live[k, t], k, t) for k in range(K) for t in range(te0, T) if Lt[t] < L]
+        best = _best(cands)
+        if best:
+            _, k_at, t_at = best
+
+            def window(stage, x, k_at=k_at, t_at=t_at):
+                if stage == "row" and x["k"] == k_at:
+                    x["Lt"] = x["Lt"].copy()
+                    x["Lt"][t_at] = L
+
+            out["window"] = window
+        # one same-row push D[t] g[k, e] never added to P[k, t + e]
+        cands = []
+        for k in range(K):
+            tap = hg.window_taps(a["PW"], k)
+            if not tap[L - 1, k, L:].any():
+                continue  # (this row's windows never overlap themselves at another lag)
+            for t in range(T // 2, min(T // 2 + 16, T - 1)):
+                for e in range(1, min(L, T - t)):
+                    if live[k, t + e]:
+                        cands.append((abs(D[k, t]) * tap[Lt[t] - 1, k, e + L - 1] / nrm[k, t + e], k, t, e))
+        best = _best(cands)
+        if best:
+            _, k_at, t_at, e_at = best
+
+            def push(stage, x, k_at=k_at, t_at=t_at, e_at=e_at):
+                if stage == "row" and x["k"] == k_at:
+                    x["skip_push"].add((t_at, e_at))
+
+            out["push"] = push
+    if K > 1 and L > 1:
+        nblk = (T + 63) // 64
+        k2 = max(0, K // 2 - 1)
+        tap = hg.window_taps(a["PW"], k2)
+        for name, cols in (("cross_interior", range(64 * (nblk // 2), 64 * (nblk // 2) + 64) if nblk >= 2 and nblk // 2 < nblk - 1 else ()),
+                           ("cross_edge", range(64 * (nblk - 1), T))):
+            cands = []
+            es = np.arange(-(L - 1), L)
+            for kt in range(k2 + 1, K):
+                for tp in cols:
+                    if not live[kt, tp]:
+                        continue
+                    ts = tp - es
+                    ok = (ts >= 0) & (ts < T)
+                    if name == "cross_edge" and tp < te0:
+                        ok &= ts >= te0
+                    tv, ev = ts[ok], es[ok]
+                    score = np.abs(D[k2, tv]) * tap[Lt[tv] - 1, kt, ev + L - 1] / nrm[kt, tp]
+                    if len(score) and score.max() > 0:
+                        i = int(np.argmax(score))
+                        cands.append((float(score[i]), kt, int(tv[i]), int(ev[i])))
+                if len(cands) >= 8:
+                    break  # (the rows next to the source row where they have a site; on sparse lag Grams a later one)
+            best = _best(cands)
+            if best:
+                def cross(stage, x, site=best[1:]):
+                    if stage == "row" and x["k"] == k2:
+                        x["lose"].add(site)
+
+                out[name] = cross
+    return out

@@ -2,7 +2,9 @@
 shape table, the ulp comparator's power to see one missing term, the launch-path names kept equal to the library's table, and for
 the divergence forms the problems, the restated halves, the sensitivity condition and the element-wise check's power to see
 corruptions a Frobenius-relative 1e-4 passes; and for the masked MU rule and the PGD rule (tests/test_gpu_exact_masked_mu.py,
-tests/test_gpu_exact_pgd.py) the preconditions on the whole table, a float32 model of the PGD half-step and the same kind of mutations."""
+tests/test_gpu_exact_pgd.py) the preconditions on the whole table, a float32 model of the PGD half-step and the same kind of mutations;
+and for the HALS sweeps (tests/test_gpu_exact_hals.py) the launch names, the plan mirror, the preconditions and the float32 model on every row
+of HALS_SHAPES, the bars made from them, and the local errors of a sweep kernel as mutations of the restatement."""
 import os
 import re
 
@@ -586,3 +588,187 @@ def test_two_ulp_check_flags_what_a_normwise_check_passes(shape):
     print("a Frobenius-relative 1e-4 passes:", {k: sorted(v) for k, v in blind.items()})
     if shape == LARGEST_ROW:
         assert blind == NORMWISE_PASSES_ON_THE_LARGEST_ROW
+
+
+# ---- the HALS sweeps (tests/test_gpu_exact_hals.py) -----------------------------------------------------------------------------
+HALS_PROFILE = os.path.join(ROOT, "profiles", "exact_hals.txt")
+HALS_IDS = [f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in ep.HALS_SHAPES]
+_hals_halves = {}
+
+
+def _hals_half(shape, family, r):
+    """(W, H, X, the fp64 half) of a row under the regulariser pair r, formed once per session."""
+    key = (shape, family, r)
+    if key not in _hals_halves:
+        W, H, X = ep.make_hals_problem(*shape, family)
+        _hals_halves[key] = (W, H, X, ep.hals_half(family, W, H, X, ep.HALS_REGS[r]))
+    return _hals_halves[key]
+
+
+def test_hals_launch_path_names_match_the_library():
+    src = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_internal.h")).read()
+    m = re.search(r"kHalsLaunchNames\[\] = \{(.*?)\};", src, re.S)
+    assert m, "kHalsLaunchNames table not found"
+    assert re.findall(r'"([^"]+)"', m.group(1)) == ep.HALS_LAUNCH_PATHS
+    assert len(set(ep.HALS_LAUNCH_PATHS)) == len(ep.HALS_LAUNCH_PATHS) and not set(ep.HALS_LAUNCH_PATHS) & set(ep.LAUNCH_PATHS)
+    m = re.search(r"kHalsNQ\[10\] = \{(.*?)\};", src)
+    assert m and tuple(int(x) for x in m.group(1).split(",")) == ep.HALS_NQ
+
+
+def test_hals_plan_mirror_assigns_every_instance_to_a_row():
+    """By the plan rules the table reaches every register instance of the W sweep (three of them with padding slots), the general W
+    sweep by the plan and forced, one to four pullers per row, the stage pipeline at both lags over more than one segment, the general H
+    sweep by the plan and forced, the chased form, and the T and L edges the sweeps treat separately; the GPU test confirms the plans
+    with the launch counters."""
+    plans = [(s[:4], cfg, ep.hals_plan(*s[:4], cfg)) for s in ep.HALS_SHAPES for cfg in s[4]]
+    default = {shape: p for shape, cfg, p in plans if not cfg or set(cfg) == {"hals_chase"}}
+    assert set(default) == {s[:4] for s in ep.HALS_SHAPES}
+    assert {p["NQ"] for p in default.values() if p["NQ"]} == set(ep.HALS_NQ)
+    padded = {(s[2], s[3]): (p["nq"], p["NQ"]) for s, p in default.items() if p["pad_slots"]}
+    assert padded[(33, 3)] == (3, 4) and padded[(33, 31)] == (31, 32) and padded[(64, 18)] == (18, 20)
+    assert default[(37, 1300, 64, 40)]["w_general"] and default[(9, 200, 3, 70)]["w_general"] and default[(9, 200, 3, 70)]["h_general"]
+    forced_w = [s for s, cfg, p in plans if cfg.get("hals_general", 0) & 1 and not default[s]["w_general"]]
+    forced_h = [s for s, cfg, p in plans if cfg.get("hals_general", 0) & 2 and not default[s]["h_general"]]
+    assert len(set(forced_w)) >= 2 and len(set(forced_h)) >= 2
+    assert {p["P"] for _, _, p in plans} == {0, 1, 2, 3, 4}
+    assert {s[2] for s, _, p in plans if p["P"] > 0} >= {1, 2, 18, 64}
+    assert any(p["P"] > p["nblk"] for _, _, p in plans), "no row with fewer blocks than pullers"
+    stage = [(s, cfg) for s, cfg, p in plans if p["P"] == 0 and not p["h_general"]]
+    assert {cfg.get("hals_lag", 2) for s, cfg in stage if s[1] > 256 and cfg.get("hals_seg") == 256} == {2, 3}
+    chased = [(s, cfg, p) for s, cfg, p in plans if p["chase"]]
+    assert [(s, cfg.get("hals_chase"), p["P"], p["chase"]) for s, cfg, p in chased] == [((130, 9000, 32, 20), 65, 3, 91)]
+    past = {s for s, _, p in plans if not p["gram_window"]}  # the Gram form of P past its LDS window: from the residual under every hals_gram
+    assert past == {(29, 1200, 129, 46)} and ep.rup(129, 32) * (64 + 2 * 45) * 4 > 96 * 1024 >= ep.rup(129, 32) * (64 + 2 * 44) * 4
+    shapes = list(default)
+    assert any(T < L for _, T, _, L in shapes) and any(L < T < 2 * L for _, T, _, L in shapes) and any(2 * L <= T <= 64 + L for _, T, _, L in shapes)
+    assert any(T % 64 == 0 for _, T, _, _ in shapes) and any(T < 64 for _, T, _, _ in shapes) and {1, 64} <= {L for _, _, _, L in shapes}
+    assert any(L >= 10 and p["P"] > 0 for (_, _, _, L), p in default.items())
+    assert all(N % 2 == 1 for N, _, _, _ in shapes if N < 100)
+
+
+@pytest.mark.parametrize("shape", [(12, 40, 3, 6), (9, 5, 2, 8), (9, 70, 5, 1), (20, 150, 7, 9)])
+def test_hals_halves_are_the_sweeps(shape):
+    """w_half / h_half in fp64 give w_sweep / h_sweep bit for bit on the integer problems (where the taps are exact), and on real-valued
+    factors W bit for bit and H to the rounding of the taps' matrix product."""
+    import hals_gram_form as hg
+    from oracle import cmf_oracle as o
+
+    for family in ("W", "H"):
+        W, H, X = ep.make_problem(*shape, family)
+        for reg in ep.HALS_REGS:
+            np.testing.assert_array_equal(hg.w_half(o, W, H, X, *reg)["new"], hg.w_sweep(o, W, H, X, *reg))
+            np.testing.assert_array_equal(hg.h_half(o, W, H, X, *reg)["new"], hg.h_sweep(o, W, H, X, *reg))
+    N, T, K, L = shape
+    rng = np.random.default_rng(3)
+    W, H, X = rng.random((K, N, L)), rng.random((K, T)), rng.random((N, T))
+    np.testing.assert_array_equal(hg.w_half(o, W, H, X, 0.1, 0.2)["new"], hg.w_sweep(o, W, H, X, 0.1, 0.2))
+    b = hg.h_half(o, W, H, X, 0.1, 0.2)
+    np.testing.assert_allclose(b["new"], hg.h_sweep(o, W, H, X, 0.1, 0.2), rtol=0, atol=1e-12)
+    assert abs(b["loss"] - o.compute_loss(X, W, b["new"])) <= 1e-14
+
+
+@pytest.mark.parametrize("N,T,K,L", [s[:4] for s in ep.HALS_SHAPES], ids=HALS_IDS)
+def test_hals_preconditions_and_float32_model(N, T, K, L):
+    """Every row, half and regulariser pair, from the arrays generated: every contraction below 2^24 in absolute sums, the shares of
+    positive and clamped elements (also among the last L - 1 columns of H), the clamp decided away from the bar, and the float32
+    model's distance from the fp64 half -- the values profiles/exact_hals.txt records, from which the bars are made."""
+    prof = ep.read_hals_profile(HALS_PROFILE)["row"]
+    bars = dict(zip("WH", ep.hals_bars(HALS_PROFILE)[:2]))
+    for family in ("W", "H"):
+        for r, reg in enumerate(ep.HALS_REGS):
+            W, H, X, a = _hals_half((N, T, K, L), family, r)
+            what = f"{(N, T, K, L)} {family} reg{r}"
+            b = ep.hals_preconditions(family, a, bars[family])
+            ep.assert_hals_preconditions(b, a["new"].size, L, what)
+            m = ep.hals_half(family, W, H, X, reg, np.float32)
+            model = float(ep.hals_units(m["new"], a).max())
+            assert model <= bars[family] / ep.HALS_BAR_FACTOR * (1 + 1e-5), f"{what}: the model is {model:.2f} units from fp64: above a quarter of the bar"
+            assert not (((m["new"] > 0) != (a["new"] > 0)) & ~ep.hals_excused(a, bars[family])).any(), f"{what}: the model's zero pattern differs outside the excused elements"
+            rec = prof[(f"{N}x{T}x{K}x{L}", family, f"reg{r}")]
+            assert abs(rec["model"] - model) <= 0.006 * max(model, 1.0), (what, rec["model"], model)
+            b["zero_mismatch"] = int(((m["new"] > 0) != (a["new"] > 0)).sum())
+            assert rec["abs_sum"] == b["abs_sum"] and rec["close"] == b["close"] and rec["zero_mismatch"] == b["zero_mismatch"], (what, rec, b)
+            for key in ("pos", "clamp", "edge_pos", "edge_clamp"):
+                assert (key in rec) == (key in b) and abs(rec.get(key, 0.0) - b.get(key, 0.0)) < 1e-5, (what, key, rec, b)
+            assert abs(rec["min_pre"] - b["min_pre"]) <= 1e-4 * b["min_pre"], (what, rec["min_pre"], b["min_pre"])
+            if family == "H":
+                rel = abs(m["loss"] - a["loss"]) / a["loss"]
+                assert rel <= ep.hals_bars(HALS_PROFILE)[2] / ep.HALS_BAR_FACTOR * (1 + 1e-6)
+                assert abs(rec["loss_model"] - rel) <= 0.05 * rel + 1e-12, (what, rec["loss_model"], rel)
+
+
+def test_hals_bars_are_made_from_the_profile_rows():
+    """One bar per half: 4 times the worst float32-model error over the table, at least 8; the loss bar 4 times the worst relative error
+    of the float32 conv model's loss (no floor).  The `bar` lines
+    of the profile are these numbers, and there is a `row` line for every row, half and regulariser pair (and no other)."""
+    prof = ep.read_hals_profile(HALS_PROFILE)
+    want = {(f"{s[0]}x{s[1]}x{s[2]}x{s[3]}", f, f"reg{r}") for s in ep.HALS_SHAPES for f in "WH" for r in range(len(ep.HALS_REGS))}
+    assert set(prof["row"]) == want
+    bw, bh, bl = ep.hals_bars(HALS_PROFILE)
+    for f, bar in (("W", bw), ("H", bh)):
+        worst = max(v["model"] for k, v in prof["row"].items() if k[1] == f)
+        assert bar == max(8.0, 4.0 * worst) and abs(prof["bar"][f] - bar) <= 1e-4 * bar
+    assert bl == 4.0 * max(v["loss_model"] for k, v in prof["row"].items() if k[1] == "H")
+    assert abs(prof["bar"]["loss"] - bl) <= 1e-4 * bl
+    # no bar comes from a GPU result: the `gpu` lines are below the bars, and changing them changes nothing above
+    for name, v in prof["gpu"].items():
+        assert v <= (bl if name == "loss" else bw if name.startswith("W") else bh), (name, v)
+
+
+# The local errors a sweep kernel would make, applied to the restatement through its corrupt hook; `None`: every row must have a site.
+HALS_W_MUTATIONS = {"term": "L > 1", "stale_row": "K > 1, L > 1", "slot": "padding slots, L > 1"}
+HALS_H_MUTATIONS = {"window": "L > 1", "push": "L > 1", "cross_interior": "K > 1, L > 1, more than two blocks", "cross_edge": "K > 1, L > 1"}
+
+
+@pytest.mark.parametrize("N,T,K,L", [s[:4] for s in ep.HALS_SHAPES], ids=HALS_IDS)
+def test_hals_check_flags_the_local_errors_of_a_sweep(N, T, K, L):
+    """Each mutation moves the worst element by at least 4 bars on every row it applies to (under the regularisers (0.5, 0.25)): one
+    G-update term of one step dropped, the HH row of step s used at step s + 1 for one unit, the last live slot's update dropped at one
+    step where the instance has padding slots (W); one truncated window taken at full length, norm and taps, one cross-row term of one
+    source row lost in an interior and in an edge block, one same-row push lost (H); l1 or l2 left out (both).  Where a mutation does
+    not apply there is no such term: at L = 1 HH and the taps are diagonal (no step feeds a later one); with one component the HH rows of
+    two consecutive steps agree on every column still to be swept; K = 1 has no cross-row term.
+
+    NOT covered by any mutation here, said plainly: (1) the update of a PADDING slot of hals_w_sweep_reg_kernel.  A slot past L * K32
+    has no column in the restatement: the kernel holds zeros there and multiplies them by the zeros its bounded loads return, so
+    dropping that update changes no result and no CPU mutation can stand for it.  The `slot` mutation is a different error -- the last
+    LIVE slot taken for padding at one step -- and what holds the padding slots themselves is the GPU file's element-wise check on the
+    three rows that have them.  (2) eps left out moves NOTHING on any row, which is asserted: the squared norms are integers; where one
+    is >= 1, eps = 2^-52 vanishes in the fp32 sum and moves the fp64 reference by 1e-16; where it is 0 the projection is exactly 0, the
+    quotient is 0/0 or -l1/0 and fmaxf(., 0) makes both 0, as the reference does.  A kernel without eps passes the GPU file."""
+    shape = (N, T, K, L)
+    bw, bh, _ = ep.hals_bars(HALS_PROFILE)
+    plan = ep.hals_plan(N, T, K, L)
+    nblk = (T + 63) // 64
+    applies = {"term": L > 1, "stale_row": L > 1 and K > 1, "slot": plan["pad_slots"] > 0 and L > 1, "window": L > 1, "push": L > 1,
+               "cross_interior": K > 1 and L > 1 and nblk >= 3, "cross_edge": K > 1 and L > 1}
+    for family, bar in (("W", bw), ("H", bh)):
+        W, H, X, a = _hals_half(shape, family, 1)
+        muts = ep.hals_w_mutations(a, plan) if family == "W" else ep.hals_h_mutations(a)
+        for name in (HALS_W_MUTATIONS if family == "W" else HALS_H_MUTATIONS):
+            if not applies[name]:
+                continue
+            assert name in muts, f"{shape} {family}: no site for the mutation {name!r}"
+            moved = float(ep.hals_units(ep.hals_half(family, W, H, X, ep.HALS_REGS[1], corrupt=muts[name])["new"], a).max())
+            assert moved >= 4 * bar, f"{shape} {family} {name}: moves the worst element by {moved:.0f} units only ({4 * bar:.0f} asked)"
+        for name, reg in (("l1", (0.0, ep.L2)), ("l2", (ep.L1, 0.0))):
+            moved = float(ep.hals_units(ep.hals_half(family, W, H, X, reg)["new"], a).max())
+            assert moved >= 4 * bar, f"{shape} {family} {name} left out: moves the worst element by {moved:.0f} units only ({4 * bar:.0f} asked)"
+        W, H, X, a = _hals_half(shape, family, 0)  # (l2 = 0: eps is all there is beside the norm)
+        moved = float(ep.hals_units(ep.hals_half(family, W, H, X, ep.HALS_REGS[0], eps=0.0)["new"], a).max())
+        assert moved < 1.0, f"{shape} {family}: eps left out moves an element by {moved:.2f} units"
+
+
+def test_hals_check_reports_the_worst_element():
+    W, H, X, a = _hals_half((9, 30, 2, 20), "H", 1)
+    got = a["new"].astype(np.float32).astype(np.float64)
+    assert ep.check_hals(got, a, 8.0, "kt")[1] is None
+    i = tuple(np.argwhere(a["new"] > 0)[3])
+    got[i] *= 1.0 + 1e-3
+    worst, msg = ep.check_hals(got, a, 8.0, "kt", ["x"])
+    assert worst > 1000 and msg.startswith(f"{worst:.1f} units (bar 8) at k={i[0]}, t={i[1]}: got ") and msg.endswith("; 1 elements over the bar); launches ['x']")
+    got = a["new"].copy()
+    j = tuple(np.argwhere((a["new"] == 0) & (a["diag"] != 0))[0])
+    got[j] = 1e-30  # within any bar of 0, but not ON the clamp
+    worst, msg = ep.check_hals(got, a, 8.0, "kt")
+    assert worst < 1 and msg.startswith(f"zero pattern differs at k={j[0]}, t={j[1]}")

@@ -17,7 +17,7 @@ oracle's fp64 step (exact_problems' PGD section; tests/test_exact_problems.py co
 One unit of one contraction moves an element by at least 200 ulp (profiles/exact_masked_pgd.txt; at least 8 asserted), so a lost term, a
 mask tile read one block off or a weight read as a flag fails here, where the norm-wise 1e-4 of tests/test_gpu_parity.py passes them.
 
-Not covered, and why: the HALS sweeps (sequential divisions: no exactness argument; their CONV_RESID conv is the one reached here);
+Not covered, and why: the HALS sweeps have a file of their own (tests/test_gpu_exact_hals.py; their CONV_RESID conv is the one reached here);
 UnitNormConstraint (its per-component norms are not exact); several PGD iterations from non-integer factors (tests/test_gpu_parity.py,
 norm-wise)."""
 import os
