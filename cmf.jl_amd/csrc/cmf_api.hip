@@ -216,7 +216,7 @@ static void destroy_impl(cmf_handle_s *h)
     (void)hipSetDevice(h->device);
     float *fbufs[] = {h->H, h->Ht, h->Wt, h->Wn, h->X, h->XT, h->est, h->estT, h->wslabs, h->numden_own, h->hslabs,
                       h->halo_own[0], h->halo_own[1], h->halo_own[2], h->halo_own[3],
-                      h->gram_numden_h, h->pgd_gradH, h->M, h->MT, h->Xm, h->XmT, h->hals_snap, h->hals_HX, h->hals_cslabs, h->hals_C, h->hals_HH, h->hals_PT, h->hals_D, h->hals_PW, h->hals_GW, h->hals_GE, h->hals_GWt};
+                      h->gram_numden_h, h->pgd_gradH, h->M, h->MT, h->Xm, h->XmT, h->Xs, h->XsT, h->hals_snap, h->hals_HX, h->hals_cslabs, h->hals_C, h->hals_HH, h->hals_PT, h->hals_D, h->hals_PW, h->hals_GW, h->hals_GE, h->hals_GWt};
     for (float *p : fbufs)
         if (mine(p)) (void)hipFree(p);
     if (h->kl_denH) (void)hipFree(h->kl_denH);
@@ -559,6 +559,8 @@ static int mu_launch_conv(cmf_handle_s *h, int family, int base, float *out, int
         CASE(CONV_KLM_LOSS) CASE(CONV_KLM_LOSS_R)
         CASE(CONV_IS_PQ) CASE(CONV_IS_PQ_T) CASE(CONV_IS_LOSS) CASE(CONV_IS_LOSS_PQ)
         CASE(CONV_BETA_PQ) CASE(CONV_BETA_PQ_T) CASE(CONV_BETA_LOSS) CASE(CONV_BETA_LOSS_PQ)
+        CASE(CONV_ISM_PQ) CASE(CONV_ISM_PQ_T) CASE(CONV_ISM_LOSS) CASE(CONV_ISM_LOSS_PQ)
+        CASE(CONV_BETAM_PQ) CASE(CONV_BETAM_PQ_T) CASE(CONV_BETAM_LOSS) CASE(CONV_BETAM_LOSS_PQ)
 #undef CASE
     default: return fail(CMF_ERR_STATE, "internal: the MU rule launches no conv mode %d", conv_mode(family, base));
     }
@@ -1352,6 +1354,14 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
         h->kl_mask = value;
         return CMF_OK;
     }
+    if (std::strcmp(name, "pq_mask") == 0) { // cmf_mu_set_mask + the Itakura-Saito / beta form together (not listed by cmf_option_names: off by default, see the header)
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "pq_mask: the mask and the divergence of the MU rule are chosen on single-GPU handles only");
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "pq_mask must be 0 or 1");
+        if (!value && h->mu_mask && (h->mu_div == CMF_DIV_IS || h->mu_div == CMF_DIV_BETA))
+            return fail(CMF_ERR_STATE, "pq_mask: the Itakura-Saito or beta form and a mask are both installed; clear the mask or restore CMF_DIV_SQUARE first");
+        h->pq_mask = value;
+        return CMF_OK;
+    }
     if (std::strcmp(name, "is_div") == 0) { // lets cmf_mu_set_divergence take CMF_DIV_IS (not listed by cmf_option_names: off by default, see the header)
         if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "is_div: the divergence of the MU rule is chosen on single-GPU handles only");
         if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "is_div must be 0 or 1");
@@ -1770,12 +1780,52 @@ static int kl_free_tables(cmf_handle_s *h)
     return CMF_OK;
 }
 
+static bool mu_div_pq(const cmf_handle_s *h) { return h->mu_div == CMF_DIV_IS || h->mu_div == CMF_DIV_BETA; }
+static int is_check_data(cmf_handle_s *h);
+static int beta_check_data(cmf_handle_s *h);
+
+// the sentinel copies of data exist while a mask and the Itakura-Saito / beta form are both installed (the stream has been drained)
+static void pq_free_sentinel(cmf_handle_s *h)
+{
+    if (h->Xs) (void)hipFree(h->Xs);
+    if (h->XsT) (void)hipFree(h->XsT);
+    h->Xs = h->XsT = nullptr;
+}
+
+// Itakura-Saito / beta under the installed mask (option "pq_mask"): the data check over the observed entries alone and, when it passes,
+// fresh sentinel copies Xs / XsT (one more pass: a mask that fails has written nothing).  *count_out: the observed entries.
+static int pq_mask_sentinel(cmf_handle_s *h, int div, double *count_out)
+{
+    const CmfDims &d = h->d;
+    const size_t TPNp = (size_t)d.TP * d.Np;
+    const int strict = div == CMF_DIV_IS ? 1 : 0;
+    double cb[2]; // observed | bad among them
+    CMFTRY(flat_reduce(h, "pq_mask_sentinel_kernel", 2, cb, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(pq_mask_sentinel_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, (float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                           (float *)nullptr, n4, strict, h->partial);
+    }));
+    if (cb[1] > 0.0 && strict)
+        return fail(CMF_ERR_ARG, "Itakura-Saito divergence needs finite, strictly positive data (%.0f entries are zero, negative, NaN or infinite): "
+                                 "add a small floor to the spectrogram, e.g. data + 1e-6 * max(data)", cb[1]);
+    if (cb[1] > 0.0) return fail(CMF_ERR_ARG, "the beta-divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", cb[1]);
+    if (!h->Xs) CMFTRY(dalloc_zero(&h->Xs, TPNp));
+    if (!h->XsT) CMFTRY(dalloc_zero(&h->XsT, TPNp));
+    CMFTRY(flat_reduce(h, "pq_mask_sentinel_kernel", 2, cb, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(pq_mask_sentinel_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, h->Xs, h->XT, h->MT, h->XsT, n4, strict, h->partial);
+    }));
+    *count_out = cb[0];
+    return CMF_OK;
+}
+
 // The MU entries leave the masked rule: est, the speculated contraction and a deferred loss are void, the masked copies of data freed.
 // While the KL form is installed (option "kl_mask") the rule goes back to the raw data, which must pass the KL check first: a failure
 // returns CMF_ERR_ARG and leaves the handle as it was.
 static int mu_mask_off(cmf_handle_s *h)
 {
-    if (h->mu_mask && h->mu_div) {
+    if (h->mu_mask && mu_div_pq(h)) { // (option "pq_mask": the same re-check by the form's own rule; data_sum is the entry count again)
+        CMFTRY(h->mu_div == CMF_DIV_IS ? is_check_data(h) : beta_check_data(h));
+        h->data_sum = (double)h->d.N * (double)h->d.Tl;
+    } else if (h->mu_mask && h->mu_div) {
         double sum = 0.0;
         CMFTRY(kl_check_data(h, h->X, &sum));
         h->data_sum = sum;
@@ -1783,8 +1833,9 @@ static int mu_mask_off(cmf_handle_s *h)
     drop_carry(h);
     h->spec_gen = -1;
     set_est(h, EST_NONE);
-    if (!h->mu_mask && !h->Xm && !h->XmT) return CMF_OK;
+    if (!h->mu_mask && !h->Xm && !h->XmT && !h->Xs && !h->XsT) return CMF_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
+    pq_free_sentinel(h);
     if (h->Xm) (void)hipFree(h->Xm);
     if (h->XmT) (void)hipFree(h->XmT);
     h->Xm = h->XmT = nullptr;
@@ -1828,18 +1879,19 @@ static int kl_install_mask(cmf_handle_s *h, const double *mask)
     h->spec_gen = -1;
     set_est(h, EST_NONE);
     HIPCHK(hipStreamSynchronize(h->stream));
-    float *const old[4] = {h->M, h->MT, h->Xm, h->XmT};
+    float *const old[6] = {h->M, h->MT, h->Xm, h->XmT, h->Xs, h->XsT};
     const bool old_on = h->mu_mask;
     const double old_ss = h->xm_sumsq, old_norm = h->xm_norm;
-    h->M = h->MT = h->Xm = h->XmT = nullptr;
+    h->M = h->MT = h->Xm = h->XmT = h->Xs = h->XsT = nullptr;
     double sum = 0.0;
     int rc = mu_install_mask(h, mask);
-    if (rc == CMF_OK) rc = kl_check_data(h, h->Xm, &sum);
+    // (Itakura-Saito / beta, option "pq_mask": the form's own check over the observed entries, the sentinel copies, the observed count)
+    if (rc == CMF_OK) rc = mu_div_pq(h) ? pq_mask_sentinel(h, h->mu_div, &sum) : kl_check_data(h, h->Xm, &sum);
     if (rc != CMF_OK) {
         (void)hipStreamSynchronize(h->stream);
-        for (float *q : {h->M, h->MT, h->Xm, h->XmT})
+        for (float *q : {h->M, h->MT, h->Xm, h->XmT, h->Xs, h->XsT})
             if (q) (void)hipFree(q);
-        h->M = old[0]; h->MT = old[1]; h->Xm = old[2]; h->XmT = old[3];
+        h->M = old[0]; h->MT = old[1]; h->Xm = old[2]; h->XmT = old[3]; h->Xs = old[4]; h->XsT = old[5];
         h->mu_mask = old_on;
         h->xm_sumsq = old_ss;
         h->xm_norm = old_norm;
@@ -1866,11 +1918,11 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
         h->M = h->MT = nullptr;
         return CMF_OK;
     }
-    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form (its Q = e.^(beta - 1) would need the mask tile in the "
+    if (h->mu_div == CMF_DIV_BETA && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form (its Q = e.^(beta - 1) would need the mask tile in the "
                                                                      "storing epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form (its Q = 1 ./ e would need the mask tile in the storing "
+    if (h->mu_div == CMF_DIV_IS && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form (its Q = 1 ./ e would need the mask tile in the storing "
                                                                    "epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-    if (h->mu_div && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
+    if (h->mu_div == CMF_DIV_KL && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
                                                   "which is not a product of Gram matrices; set gram = 0 first");
     const CmfDims &d = h->d;
@@ -1906,13 +1958,15 @@ static int is_check_data(cmf_handle_s *h)
 static int is_install(cmf_handle_s *h)
 {
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no Itakura-Saito form; set gram = 0 first");
-    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
-    CMFTRY(is_check_data(h));
+    if (h->mu_mask && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
     const CmfDims &d = h->d;
+    double count = (double)d.N * (double)d.Tl;
+    if (h->mu_mask) CMFTRY(pq_mask_sentinel(h, CMF_DIV_IS, &count)); // (option "pq_mask": the check over the observed entries, the sentinel copies)
+    else CMFTRY(is_check_data(h));
     if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
     if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
     if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
-    h->data_sum = (double)d.N * (double)d.Tl;
+    h->data_sum = count; // (under a mask: the observed entries)
     h->mu_div = CMF_DIV_IS;
     return CMF_OK;
 }
@@ -1933,6 +1987,7 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
     set_est(h, EST_NONE);
     if (kind == CMF_DIV_SQUARE) { // today's rule again, launch for launch
         CMFTRY(kl_free_tables(h));
+        pq_free_sentinel(h); // (the stream has been drained)
         h->mu_div = CMF_DIV_SQUARE;
         return CMF_OK;
     }
@@ -1946,6 +2001,10 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
     CMFTRY(kl_check_data(h, h->mu_mask ? h->Xm : h->X, &sum));
     if (!h->kl_denH) CMFTRY(dalloc_zero(&h->kl_denH, (size_t)d.Tl * d.K32));
     if (!h->kl_sums) CMFTRY(dalloc_zero(&h->kl_sums, (size_t)d.K32 * std::max(d.L, KL_HCHUNKS)));
+    if (h->Xs || h->XsT) { // (from Itakura-Saito / beta under a mask: their sentinel copies go)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        pq_free_sentinel(h);
+    }
     h->data_sum = sum;
     h->mu_div = CMF_DIV_KL;
     return CMF_OK;
@@ -1984,9 +2043,12 @@ int cmf_mu_set_beta_divergence(cmf_handle h, double beta)
     set_est(h, EST_NONE);
     if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no beta-divergence form; set gram = 0 first");
-    if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
-    if (h->mu_div != CMF_DIV_BETA) CMFTRY(beta_check_data(h)); // (a failure leaves the divergence the handle had)
+    if (h->mu_mask && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
     const CmfDims &d = h->d;
+    double count = (double)d.N * (double)d.Tl;
+    if (h->mu_mask && h->mu_div == CMF_DIV_BETA) count = h->data_sum; // (another beta under the same mask: checked, the copies are there)
+    else if (h->mu_mask) CMFTRY(pq_mask_sentinel(h, CMF_DIV_BETA, &count)); // (option "pq_mask"; from Itakura-Saito too: the copies are the same, the check is not run twice for nothing)
+    else if (h->mu_div != CMF_DIV_BETA) CMFTRY(beta_check_data(h)); // (a failure leaves the divergence the handle had)
     if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
     if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
     if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
@@ -2000,7 +2062,7 @@ int cmf_mu_set_beta_divergence(cmf_handle h, double beta)
     }
     h->mu_beta = beta;
     h->mu_gamma = (float)(beta < 1.0 ? 1.0 / (2.0 - beta) : beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); // Fevotte & Idier 2011
-    h->data_sum = (double)d.N * (double)d.Tl;
+    h->data_sum = count; // (under a mask: the observed entries)
     h->mu_div = CMF_DIV_BETA;
     return CMF_OK;
 }
@@ -2019,12 +2081,19 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
     // Under the KL form with its mask (option "kl_mask") the pair is (sum of the divergence terms, sum of data) over the selected entries.
     const MuForm &f = mu_form(h);
     h->mask_complement_now = comp ? 1 : 0;
-    const int rc = mu_launch_conv(h, f.held_out_family, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy, nullptr);
+    // Under Itakura-Saito / beta with their mask (option "pq_mask") it is (sum of the divergence terms, number of entries): the observed
+    // entries are summed on the sentinel copy like the training loss, the complement on the raw data with the mask tile.
+    const bool pqm = conv_pq_masked(f.held_out_family);
+    const int rc = mu_launch_conv(h, f.held_out_family, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy, (pqm && !comp) ? h->Xs : nullptr);
     h->mask_complement_now = 0;
     CMFTRY(rc);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, h->conv_partials, h->d_scalar + 1, (double *)nullptr);
     KCHK("loss_reduce_kernel");
     CMFTRY(read_scalar(h, 1, resid_sumsq));
+    if (pqm) { // (data_sum holds the observed count)
+        *data_sumsq = comp ? (double)h->d.N * (double)h->d.Tl - h->data_sum : h->data_sum;
+        return CMF_OK;
+    }
     if (f.held_out_family != CONV_FAM_KL_MASKED) return mask_select(h, false, comp ? 1 : 0, data_sumsq);
     return flat_reduce(h, "kl_masked_sum_kernel", 1, data_sumsq, [&](int nb, size_t n4) {
         hipLaunchKernelGGL(kl_masked_sum_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, n4, comp ? 1 : 0, h->partial);

@@ -201,7 +201,9 @@ enum EstKind : int {
     EST_KL_R = 7,            // data ./ (tensor_conv(W,H) + eps)  (the KL form of the MU rule)
     EST_KL_R_MASKED = 8,     // Xm ./ (tensor_conv(W,H) + eps)  (R of the KL form under a mask: exactly 0 where the mask is 0)
     EST_IS_PQ = 9,           // P of the Itakura-Saito form (and est2 holds Q)
-    EST_BETA_PQ = 10         // P of the beta form for the installed beta (and est2 holds Q); a change of beta voids it
+    EST_BETA_PQ = 10,        // P of the beta form for the installed beta (and est2 holds Q); a change of beta voids it
+    EST_IS_PQ_MASKED = 11,   // mask .* P of the Itakura-Saito form under a mask (and est2 holds mask .* Q)
+    EST_BETA_PQ_MASKED = 12  // the same of the beta form
 };
 // the residual the PGD rule keeps (resid_and_loss): masked by MaskedLoss, its sign under AbsoluteLoss
 static inline int pgd_est_kind(bool masked, bool loss_abs) { return EST_RESID + (masked ? 1 : 0) + (loss_abs ? 2 : 0); }
@@ -322,6 +324,9 @@ struct cmf_handle_s {
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
     double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
     int is_div = 0;              // cmf_set_option "is_div": 1 lets cmf_mu_set_divergence take CMF_DIV_IS
+    int pq_mask = 0;             // cmf_set_option "pq_mask": 1 lets the Itakura-Saito / beta forms and a mask of cmf_mu_set_mask be installed together
+    float *Xs = nullptr, *XsT = nullptr; // ... and while both are: data with a negative sentinel at the held-out entries, in the layouts of X and XT
+                                         // (what the masked P, Q convs read: conv_pq_sentinel); data_sum then holds the observed count
     float *est2 = nullptr, *est2T = nullptr; // Q = 1 ./ e of the Itakura-Saito form beside P in est / estT: [TP][Np] / [Np][TP], zero-filled; allocated when the form is first installed, kept until the handle goes
 
     double data_sumsq = 0.0, data_norm = 0.0;
@@ -541,6 +546,7 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
 // mu_form(h).  A new form: a row here, its conv modes in mu_launch_conv (cmf_api.hip), its install / refusal entry (cmf_mu_set_mask, cmf_mu_set_divergence).
 using MuBuf = float *cmf_handle_s::*; // a buffer of the handle
 constexpr MuBuf MU_NONE = nullptr, MU_X = &cmf_handle_s::X, MU_XT = &cmf_handle_s::XT, MU_XM = &cmf_handle_s::Xm, MU_XMT = &cmf_handle_s::XmT, MU_M = &cmf_handle_s::M,
+                MU_XS = &cmf_handle_s::Xs, MU_XST = &cmf_handle_s::XsT,
                 MU_MT = &cmf_handle_s::MT, MU_EST = &cmf_handle_s::est, MU_EST_T = &cmf_handle_s::estT, MU_EST2 = &cmf_handle_s::est2, MU_EST2_T = &cmf_handle_s::est2T;
 struct MuForm {
     int store_family, loss_family;  // conv family (cmf_conv_modes.h) of the bases store / store' and of loss / loss + store
@@ -559,7 +565,7 @@ struct MuForm {
     bool pow_update = false;        // the element-wise updates raise the quotient to the handle's mu_gamma where that is not 1 (last: the older rows do not name it)
     constexpr bool kl_den() const { return h_den < 0; }
 };
-enum { MU_SQUARE = 0, MU_SQUARE_MASKED, MU_KL, MU_KL_MASKED, MU_IS, MU_BETA, MU_NFORMS };
+enum { MU_SQUARE = 0, MU_SQUARE_MASKED, MU_KL, MU_KL_MASKED, MU_IS, MU_BETA, MU_IS_MASKED, MU_BETA_MASKED, MU_NFORMS };
 constexpr MuForm kMuForms[MU_NFORMS] = { // (in the order of the enum)
     {CONV_FAM_PLAIN, CONV_FAM_PLAIN, EST_CONV, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
      2, {MU_X, MU_EST}, 2, MU_XT, 0, 1, false, true, false, CONV_FAM_MU_MASKED},
@@ -577,12 +583,18 @@ constexpr MuForm kMuForms[MU_NFORMS] = { // (in the order of the enum)
     // (the Itakura-Saito row with the beta family's epilogues and the power step)
     {CONV_FAM_BETA, CONV_FAM_BETA, EST_BETA_PQ, MU_X, {MU_NONE, MU_NONE, MU_NONE, MU_NONE},
      2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, false, false, true, CONV_FAM_MU_MASKED, true},
+    // (the two rows above under the mask: every base reads the sentinel copy of data, so P and Q come out exactly 0 at the held-out
+    //  entries and the contractions on them are the masked sums; cmf_masked_loss scores by the form's own divergence)
+    {CONV_FAM_IS_MASKED, CONV_FAM_IS_MASKED, EST_IS_PQ_MASKED, MU_XS, {MU_XS, MU_XST, MU_XS, MU_XS},
+     2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, true, false, true, CONV_FAM_IS_MASKED},
+    {CONV_FAM_BETA_MASKED, CONV_FAM_BETA_MASKED, EST_BETA_PQ_MASKED, MU_XS, {MU_XS, MU_XST, MU_XS, MU_XS},
+     2, {MU_EST, MU_EST2}, 2, MU_EST2_T, 1, 0, false, false, true, CONV_FAM_BETA_MASKED, true},
 };
 // the element-wise step of the active form: 0 the plain quotient, 1 its square root, 2 its power mu_gamma (cmf_mu_step)
 static inline int mu_step_kind(const cmf_handle_s *h, const MuForm &f) { return (f.pow_update && h->mu_gamma != 1.f) ? 2 : f.sqrt_update ? 1 : 0; }
 static inline const MuForm &mu_form(const cmf_handle_s *h)
 {
-    return kMuForms[h->mu_div == CMF_DIV_BETA ? MU_BETA : h->mu_div == CMF_DIV_IS ? MU_IS : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
+    return kMuForms[h->mu_div == CMF_DIV_BETA ? (h->mu_mask ? MU_BETA_MASKED : MU_BETA) : h->mu_div == CMF_DIV_IS ? (h->mu_mask ? MU_IS_MASKED : MU_IS) : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
 }
 static inline float *mu_buf(const cmf_handle_s *h, MuBuf b) { return b ? h->*b : nullptr; }
 // What the MU entries read for data / "est is current".  reuse_est, the speculated C2 contraction and the deferred loss carry all
@@ -764,7 +776,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
     ProfScope prof_(h, conv_pgd(MODE) ? PROF_CONV_RESID : conv_base(MODE) == CONV_BASE_STORE ? PROF_CONV : conv_base(MODE) == CONV_BASE_STORE_T ? PROF_CONV_T
                        : conv_base(MODE) == CONV_BASE_LOSS ? PROF_CONV_LOSS : PROF_CONV_LOSS_STORE);
     const CmfDims &d = h->d;
-    if ((conv_mu_masked(MODE) || conv_kl_masked(MODE)) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
+    if ((conv_mu_masked(MODE) || conv_kl_masked(MODE) || conv_pq_masked(MODE)) && !(h->M && h->MT)) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
     ConvParams p;
     if (conv_pq(MODE) && !(h->est2 && h->est2T)) return fail(CMF_ERR_STATE, "internal: an Itakura-Saito or beta conv without its second pair of buffers");
     p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (conv_data_transposed(MODE) ? h->XT : h->X); p.partial = h->partial;

@@ -78,6 +78,10 @@ __device__ __forceinline__ float cmf_bload(__amdgpu_buffer_rsrc_t r, int voff_by
 //   beta-divergence (24 .. 27), lg = log2(e): the Itakura-Saito modes with Q = exp2((beta - 1) lg) and P = data * exp2((beta - 2) lg)
 //     (v_log_f32 / v_exp_f32, no powf), the same two stores and the same SELECT (eps^(beta - 1) is huge for beta < 1 and tiny but not 0
 //     above); the summed terms are e^beta phi(data / e) (cmf_beta_term).  The exponents and phi's constants come in p.beta_*.
+//   Itakura-Saito and beta under the MU rule's 0/1 mask (28 .. 31, 32 .. 35): the two families above with held-out entries stored as
+//     exact 0 in P and in Q and adding 0, by a SELECT.  No mask tile: p.data is the sentinel copy of data (Xs / XsT, negative where the
+//     mask is 0; observed data is >= 0), and the padding's select becomes live && !(x < 0) (cmf_pq_live).  The loss-only modes (30, 34)
+//     with p.loss_abs read the RAW data and the mask tile and sum over mask == 0 (cmf_masked_loss: the held-out score); they store nothing.
 // ---------------------------------------------------------------------------------------------
 struct ConvParams {
     const float *Ht;
@@ -201,6 +205,24 @@ template <> struct ConvPQ<true> {
     __device__ __forceinline__ float term(float x) const { return cmf_beta_term(x, e, lg, p); }
 };
 
+// The two-array modes under the MU rule's 0/1 mask (conv_pq_masked): "observed" is read off the data value, !(x < 0) -- the storing modes
+// and the training loss are given the sentinel copy of data (CMF_PQ_HELD_OUT where the mask is 0, written once at install), so the
+// epilogue holds no mask tile beside its 16 data values.  A held-out entry takes the padding's path: Q exact 0 through `live`, P exact 0
+// by a select of its own ((x q) q would be -0), the term 0.  The unmasked families compile to what they were.
+#define CMF_PQ_HELD_OUT (-1.f)
+template <int MODE> __device__ __forceinline__ bool cmf_pq_live(bool live, float x)
+{
+    if constexpr (conv_pq_sentinel(MODE)) return live && !(x < 0.f);
+    else return live;
+}
+template <int MODE, typename Q> __device__ __forceinline__ float cmf_pq_P(const Q &q, bool lv, float x)
+{
+    if constexpr (conv_pq_sentinel(MODE)) return lv ? q.P(x) : 0.f;
+    else return q.P(x);
+}
+// the held-out score (loss only, p.loss_abs, raw data): the entries the mask observes become the sentinel, the others keep their value
+__device__ __forceinline__ float cmf_pq_held_out(float x, float m) { return m == 0.f ? x : CMF_PQ_HELD_OUT; }
+
 // wave sum on the DPP network (row shifts, then the two row broadcasts): the total lands in lane 63
 __device__ __forceinline__ float cmf_wave_sum63(float x)
 {
@@ -221,6 +243,7 @@ __device__ __forceinline__ void conv_pq_epilogue_(f32x16 (&acc)[2][2], const Con
 {
     const int Np = p.Np, TP = p.TP;
     constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    constexpr bool HELD = conv_pq_masked(MODE) && conv_reads_mask(MODE); // the loss-only masked mode: with p.loss_abs the held-out score
     if (!conv_transposed(MODE)) {
         // acc[ti][ni][r]: t = tw + ti*32 + crow(r,h), n = nw + ni*32 + i
         int rows = p.T_store - tw; // rows of the sub-tile that exist
@@ -242,15 +265,24 @@ __device__ __forceinline__ void conv_pq_epilogue_(f32x16 (&acc)[2][2], const Con
                 for (int r = 0; r < 16; ++r)
                     dv[r] = PRE ? pre[gt][gn][r] // (the caller loaded the data tile under its MFMA loop: conv3_tile)
                                 : cmf_bload(rd, voff, ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4); // rows past T_store read as 0 (selected away below)
+                if constexpr (HELD) {
+                    if (p.loss_abs) { // wave-uniform: the held-out score
+                        const __amdgpu_buffer_rsrc_t rm = cmf_rsrc(p.mask + origin, bytes);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            dv[r] = cmf_pq_held_out(dv[r], cmf_bload(rm, voff, ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4));
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int so = ((gt * 32 + (r & 3) + 8 * (r >> 2)) * Np + gn * 32) * 4;
-                    const ConvPQ<conv_beta(MODE)> q(acc[gt][gn][r], live, p);
+                    const bool lv = cmf_pq_live<MODE>(live, dv[r]);
+                    const ConvPQ<conv_beta(MODE)> q(acc[gt][gn][r], lv, p);
                     if (STORE) {
-                        cmf_bstore(q.P(dv[r]), ro, voff, so);
+                        cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, so);
                         cmf_bstore(q.Q(), ro2, voff, so);
                     }
-                    if (LOSS) lsum += (live && gt * 32 + cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
+                    if (LOSS) lsum += (lv && gt * 32 + cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
                 }
             }
         if (LOSS) {
@@ -284,8 +316,9 @@ __device__ __forceinline__ void conv_pq_epilogue_(f32x16 (&acc)[2][2], const Con
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int so = ((ni * 32 + (r & 3) + 8 * (r >> 2)) * TP + ti * 32) * 4;
-                        const ConvPQ<conv_beta(MODE)> q(acc[ni][ti][r], nw + ni * 32 + cmf_crow(r, h) < p.N, p);
-                        cmf_bstore(q.P(dv[r]), ro, voff, so);
+                        const bool lv = cmf_pq_live<MODE>(nw + ni * 32 + cmf_crow(r, h) < p.N, dv[r]);
+                        const ConvPQ<conv_beta(MODE)> q(acc[ni][ti][r], lv, p);
+                        cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, so);
                         cmf_bstore(q.Q(), ro2, voff, so);
                     }
                 }
@@ -299,6 +332,7 @@ __device__ __forceinline__ void conv_pq_epilogue_block(const f32x16 &acc, const 
 {
     const int Np = p.Np, TP = p.TP;
     constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    constexpr bool HELD = conv_pq_masked(MODE) && conv_reads_mask(MODE); // the loss-only masked mode: with p.loss_abs the held-out score
     if (!conv_transposed(MODE)) {
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 32 ? 32 : rows);
@@ -312,16 +346,24 @@ __device__ __forceinline__ void conv_pq_epilogue_block(const f32x16 &acc, const 
         float dv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) dv[r] = cmf_bload(rd, voff, (((r & 3) + 8 * (r >> 2)) * Np) * 4); // rows past T_store read as 0 (selected away below)
+        if constexpr (HELD) {
+            if (p.loss_abs) { // wave-uniform: the held-out score
+                const __amdgpu_buffer_rsrc_t rm = cmf_rsrc(p.mask + origin, bytes);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dv[r] = cmf_pq_held_out(dv[r], cmf_bload(rm, voff, (((r & 3) + 8 * (r >> 2)) * Np) * 4));
+            }
+        }
         float lsum = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int so = (((r & 3) + 8 * (r >> 2)) * Np) * 4;
-            const ConvPQ<conv_beta(MODE)> q(acc[r], live, p);
+            const bool lv = cmf_pq_live<MODE>(live, dv[r]);
+            const ConvPQ<conv_beta(MODE)> q(acc[r], lv, p);
             if (STORE) {
-                cmf_bstore(q.P(dv[r]), ro, voff, so);
+                cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, so);
                 cmf_bstore(q.Q(), ro2, voff, so);
             }
-            if (LOSS) lsum += (live && cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
+            if (LOSS) lsum += (lv && cmf_crow(r, h) < rows) ? q.term(dv[r]) : 0.f;
         }
         if (LOSS) {
             const float x = cmf_wave_sum63(lsum);
@@ -341,8 +383,9 @@ __device__ __forceinline__ void conv_pq_epilogue_block(const f32x16 &acc, const 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int so = (((r & 3) + 8 * (r >> 2)) * TP) * 4;
-                const ConvPQ<conv_beta(MODE)> q(acc[r], nb + cmf_crow(r, h) < p.N, p);
-                cmf_bstore(q.P(dv[r]), ro, voff, so);
+                const bool lv = cmf_pq_live<MODE>(nb + cmf_crow(r, h) < p.N, dv[r]);
+                const ConvPQ<conv_beta(MODE)> q(acc[r], lv, p);
+                cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, so);
                 cmf_bstore(q.Q(), ro2, voff, so);
             }
         }
@@ -355,6 +398,7 @@ __device__ __forceinline__ void conv16_pq_epilogue(const f32x4 &acc, const ConvP
 {
     const int Np = p.Np, TP = p.TP;
     constexpr bool LOSS = conv_writes_loss(MODE), STORE = conv_stores(MODE);
+    constexpr bool HELD = conv_pq_masked(MODE) && conv_reads_mask(MODE); // the loss-only masked mode: with p.loss_abs the held-out score
     if (!conv_transposed(MODE)) { // acc[r]: t = tb + 4*kq + r, n = nb + j
         int rows = p.T_store - tb;
         rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
@@ -368,15 +412,23 @@ __device__ __forceinline__ void conv16_pq_epilogue(const f32x4 &acc, const ConvP
         float dv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) dv[r] = cmf_bload(rd, voff, r * Np * 4);
+        if constexpr (HELD) {
+            if (p.loss_abs) { // wave-uniform: the held-out score
+                const __amdgpu_buffer_rsrc_t rm = cmf_rsrc(p.mask + origin, bytes);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dv[r] = cmf_pq_held_out(dv[r], cmf_bload(rm, voff, r * Np * 4));
+            }
+        }
         float lsum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const ConvPQ<conv_beta(MODE)> q(acc[r], live, p);
+            const bool lv = cmf_pq_live<MODE>(live, dv[r]);
+            const ConvPQ<conv_beta(MODE)> q(acc[r], lv, p);
             if (STORE) {
-                cmf_bstore(q.P(dv[r]), ro, voff, r * Np * 4);
+                cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, r * Np * 4);
                 cmf_bstore(q.Q(), ro2, voff, r * Np * 4);
             }
-            if (LOSS) lsum += (live && 4 * kq + r < rows) ? q.term(dv[r]) : 0.f;
+            if (LOSS) lsum += (lv && 4 * kq + r < rows) ? q.term(dv[r]) : 0.f;
         }
         if (LOSS) {
             const float x = cmf_wave_sum63(lsum);
@@ -395,8 +447,9 @@ __device__ __forceinline__ void conv16_pq_epilogue(const f32x4 &acc, const ConvP
             for (int r = 0; r < 4; ++r) dv[r] = cmf_bload(rd, voff, r * TP * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const ConvPQ<conv_beta(MODE)> q(acc[r], nb + 4 * kq + r < p.N, p);
-                cmf_bstore(q.P(dv[r]), ro, voff, r * TP * 4);
+                const bool lv = cmf_pq_live<MODE>(nb + 4 * kq + r < p.N, dv[r]);
+                const ConvPQ<conv_beta(MODE)> q(acc[r], lv, p);
+                cmf_bstore(cmf_pq_P<MODE>(q, lv, dv[r]), ro, voff, r * TP * 4);
                 cmf_bstore(q.Q(), ro2, voff, r * TP * 4);
             }
         }
@@ -4048,6 +4101,45 @@ static __global__ __launch_bounds__(256) void kl_masked_sum_kernel(const float *
     }
     s = cmf_block_sum_f64(s, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// Itakura-Saito and beta under the 0/1 mask (option "pq_mask"): one pass over the flat padded data and mask (both layouts; the padding
+// has M = 0).  partial[b] = how many entries the block's part of M observes, partial[gridDim.x + b] = how many of those hold data the
+// form cannot take (strict: not finite and > 0, Itakura-Saito; otherwise not finite and >= 0) -- held-out entries are not looked at.
+// Xs / XsT (NULL together: the check alone) take the sentinel copy the masked P, Q convs read: data where observed, CMF_PQ_HELD_OUT
+// elsewhere, so that "x < 0" is "held out" (observed data has passed this check: it is >= 0).
+static __global__ __launch_bounds__(256) void pq_mask_sentinel_kernel(const float *X, const float *M, float *Xs, const float *XT, const float *MT,
+                                                                      float *XsT, size_t n4, int strict, double *partial)
+{
+    __shared__ double red[256];
+    double cnt = 0.0, bad = 0.0;
+    for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < n4; idx += (size_t)gridDim.x * 256) {
+        const float4 x = reinterpret_cast<const float4 *>(X)[idx];
+        const float4 m = reinterpret_cast<const float4 *>(M)[idx];
+        const float xv[4] = {x.x, x.y, x.z, x.w}, mv[4] = {m.x, m.y, m.z, m.w};
+        float o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool obs = mv[q] != 0.f;
+            const bool ok = (strict ? xv[q] > 0.f : xv[q] >= 0.f) && xv[q] <= 3.402823466e+38f; // (false for NaN)
+            cnt += obs ? 1.0 : 0.0;
+            bad += (obs && !ok) ? 1.0 : 0.0;
+            o[q] = obs ? xv[q] : CMF_PQ_HELD_OUT;
+        }
+        if (Xs) {
+            reinterpret_cast<float4 *>(Xs)[idx] = make_float4(o[0], o[1], o[2], o[3]);
+            const float4 xt = reinterpret_cast<const float4 *>(XT)[idx];
+            const float4 mt = reinterpret_cast<const float4 *>(MT)[idx];
+            reinterpret_cast<float4 *>(XsT)[idx] = make_float4(mt.x != 0.f ? xt.x : CMF_PQ_HELD_OUT, mt.y != 0.f ? xt.y : CMF_PQ_HELD_OUT,
+                                                               mt.z != 0.f ? xt.z : CMF_PQ_HELD_OUT, mt.w != 0.f ? xt.w : CMF_PQ_HELD_OUT);
+        }
+    }
+    cnt = cmf_block_sum_f64(cnt, red);
+    bad = cmf_block_sum_f64(bad, red);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = cnt;
+        partial[gridDim.x + blockIdx.x] = bad;
+    }
 }
 
 #define KL_HCHUNKS 16

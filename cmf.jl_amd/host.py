@@ -129,6 +129,7 @@ def rccl_version():
 # CMF_DIV_SQUARE, CMF_DIV_KL, CMF_DIV_IS (include/cmf_hip.h); ":beta" is no kind of cmf_mu_set_divergence: it has an entry of its
 # own, cmf_mu_set_beta_divergence, and is numbered here only
 _DIVERGENCES = {":square": 0, "square": 0, ":kl": 1, "kl": 1, ":itakura_saito": 2, "itakura_saito": 2, ":beta": 3, "beta": 3}
+_DIV_KL = 1
 _DIV_IS = 2
 _DIV_BETA = 3
 _DIV_NAMES = {0: ":square", 1: ":kl", 2: ":itakura_saito", 3: ":beta"}
@@ -1258,9 +1259,9 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if rule_type is not MultUpdate:
             raise NotImplementedError("divergence=':beta' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
                                       "fits minimise the squared error (PGD also the absolute error)")
-        if mask is not None:
+        if mask is not None and not (options or {}).get("pq_mask", 0):
             raise NotImplementedError("divergence=':beta' is not available with mask=: the beta-divergence form of the MU rule "
-                                      "has no masked form")
+                                      "has no masked form unless the library option is set: options={'pq_mask': 1}")
         if devices is not None:
             raise NotImplementedError("divergence=':beta' is not available with devices=[...]: the beta-divergence form of the "
                                       "MU rule runs on one GPU")
@@ -1268,9 +1269,9 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
         if rule_type is not MultUpdate:
             raise NotImplementedError("divergence=':itakura_saito' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
                                       "fits minimise the squared error (PGD also the absolute error)")
-        if mask is not None:
+        if mask is not None and not (options or {}).get("pq_mask", 0):
             raise NotImplementedError("divergence=':itakura_saito' is not available with mask=: the Itakura-Saito form of the MU rule "
-                                      "has no masked form")
+                                      "has no masked form unless the library option is set: options={'pq_mask': 1}")
         if devices is not None:
             raise NotImplementedError("divergence=':itakura_saito' is not available with devices=[...]: the Itakura-Saito form of the "
                                       "MU rule runs on one GPU")
@@ -1410,25 +1411,32 @@ def holdout_mask(N, T, frac=0.1, block=1, seed=None):
     return np.asfortranarray(np.where(held, 0.0, 1.0))
 
 
-def evaluate_heldout(r, mask, device=None, divergence=":square"):
+def evaluate_heldout(r, mask, device=None, divergence=":square", beta=None, options=None):
     """(train, test) = sqrt(sum of (est - data)^2 / sum of data^2) over the entries with ``mask == 1`` and over those with
     ``mask == 0``, for the fitted model ``r`` (cmf_masked_loss: one loss-only conv each, sums by select).
     ``divergence=":kl"``: D / sum(data) over the same two sets of entries, D the sum of the divergence terms there (no square
-    root): what ``fit_cnmf(divergence=":kl", mask=...)`` records in ``loss_hist``, and its held-out counterpart."""
+    root): what ``fit_cnmf(divergence=":kl", mask=...)`` records in ``loss_hist``, and its held-out counterpart.
+    ``divergence=":itakura_saito"`` or ``":beta"`` (with ``beta=``) under ``options={"pq_mask": 1}``: the mean divergence per entry
+    over the same two sets (sum of the terms / number of entries): what such a fit under the mask records, and its counterpart."""
     kl = _divergence_kind(divergence)
-    if kl == _DIV_BETA:
-        raise NotImplementedError("divergence=':beta' has no held-out score: the beta-divergence form of the MU rule has no masked form")
-    if kl == _DIV_IS:
+    pq = kl in (_DIV_IS, _DIV_BETA)
+    if kl == _DIV_BETA and not (options or {}).get("pq_mask", 0):
+        raise NotImplementedError("divergence=':beta' has no held-out score: the beta-divergence form of the MU rule has no masked form "
+                                  "unless the library option is set: options={'pq_mask': 1}")
+    if kl == _DIV_IS and not (options or {}).get("pq_mask", 0):
         raise NotImplementedError("divergence=':itakura_saito' has no held-out score: the Itakura-Saito form of the MU rule has no "
-                                  "masked form")
+                                  "masked form unless the library option is set: options={'pq_mask': 1}")
+    beta = _check_beta(kl, beta)
     mask = farr(mask, np.shape(r.data))
     rule = MultUpdate(r.data, r.W, r.H, device=device)
     try:
-        if kl:
+        if pq:
+            rule.set_option("pq_mask", 1)
+        elif kl:
             rule.set_option("kl_mask", 1)
         rule.set_mask(mask)
         if kl:
-            rule.set_divergence(":kl")
+            rule.set_divergence(_DIV_NAMES[kl], beta=beta)
         out = []
         for comp in (False, True):
             resid, dat = rule.masked_loss(complement=comp)
@@ -1457,17 +1465,19 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     """Held-out scores for choosing L and K: for every (L, K) and every repeat, draw ``holdout_mask(N, T, frac, block, seed')``,
     fit ``fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=seed', **fit_kw)`` and score it with ``evaluate_heldout``.
     ``divergence=":kl"`` (for counts) fits the KL form under the mask -- the library option "kl_mask" is set here, beside whatever
-    ``options=`` holds -- and scores with the same divergence.
+    ``options=`` holds -- and scores with the same divergence.  ``divergence=":itakura_saito"`` or ``":beta"`` (for power
+    spectrograms) proceed when ``options`` carries ``pq_mask=1`` and score by the mean divergence per entry.
     Returns ``{(L, K): {"train": array(repeats), "test": array(repeats)}}``.  ``block`` defaults to the combination's L.
     seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
     by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
     combinations and the scores gathered on all ranks."""
-    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_BETA:
+    pq_mask = bool((fit_kw.get("options") or {}).get("pq_mask", 0))
+    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_BETA and not pq_mask:
         raise NotImplementedError("cross_validate(divergence=':beta') is not available: the beta-divergence form of the MU rule "
-                                  "has no masked form, so nothing can be held out")
-    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_IS:
+                                  "has no masked form, so nothing can be held out (unless options={'pq_mask': 1})")
+    if _divergence_kind(fit_kw.get("divergence", ":square")) == _DIV_IS and not pq_mask:
         raise NotImplementedError("cross_validate(divergence=':itakura_saito') is not available: the Itakura-Saito form of the MU rule "
-                                  "has no masked form, so nothing can be held out")
+                                  "has no masked form, so nothing can be held out (unless options={'pq_mask': 1})")
     data = farr(data)
     N, T = data.shape
     if "mask" in fit_kw or "alg" in fit_kw:
@@ -1477,7 +1487,7 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     dist, rank, world = _process_group(group)
     device = fit_kw.get("device", None)
     divergence = fit_kw.get("divergence", ":square")
-    if _divergence_kind(divergence):
+    if _divergence_kind(divergence) == _DIV_KL:
         fit_kw["options"] = dict(fit_kw.get("options") or {}, kl_mask=1)
     mine = {}
     for idx, ((L, K), rep) in enumerate(jobs):
@@ -1486,7 +1496,8 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
         s = None if seed is None else int(seed) + idx
         mask = holdout_mask(N, T, frac=frac, block=L if block is None else block, seed=s)
         r = fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=s, **fit_kw)
-        mine[idx] = evaluate_heldout(r, mask, device=device, divergence=divergence)
+        mine[idx] = evaluate_heldout(r, mask, device=device, divergence=divergence, beta=fit_kw.get("beta", None),
+                                     options={"pq_mask": 1} if pq_mask else None)
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, mine, group=group)

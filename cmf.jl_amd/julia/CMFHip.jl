@@ -460,17 +460,27 @@ end
 # the entries with mask == 1 and over those with mask == 0, for a fitted model (cmf_masked_loss: one loss-only conv each, sums by
 # select, so NaNs among the held-out data stay out of the train score).  divergence=:kl: D / sum(data) over the same two sets of
 # entries (no square root), through the library option "kl_mask" (the KL form of the MU rule under a mask, include/cmf_hip.h).
-function evaluate_heldout(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Float64}, mask; device::Integer=0, divergence::Symbol=:square)
-    divergence in (:square, :kl) || throw(ArgumentError("divergence must be :square or :kl"))
+# divergence=:itakura_saito, or :beta with beta=, under options=Dict("pq_mask" => 1) (the Itakura-Saito and beta forms under a mask):
+# the mean divergence per entry over the same two sets (sum of the terms / number of entries).
+function evaluate_heldout(data::Matrix{Float64}, W::Tensor{Float64}, H::Matrix{Float64}, mask; device::Integer=0, divergence::Symbol=:square,
+                          beta=nothing, options=nothing)
+    divergence in (:square, :kl, :itakura_saito, :beta) || throw(ArgumentError("divergence must be :square, :kl, :itakura_saito or :beta"))
+    pq = divergence in (:itakura_saito, :beta)
+    pq && (options === nothing || get(options, "pq_mask", 0) != 1) &&
+        throw(ArgumentError("divergence=:$divergence has no held-out score: the form has no masked form unless the library option is set: options=Dict(\"pq_mask\" => 1)"))
+    divergence === :beta && beta === nothing && throw(ArgumentError("divergence=:beta needs beta="))
     rule = HIPMultUpdate(data, W, H; device=device, sync_every_call=false)
     divergence === :kl && set_option!(rule, "kl_mask", 1)
+    pq && set_option!(rule, "pq_mask", 1)
     select_mask!(rule, mask)
     divergence === :kl && set_divergence!(rule, :kl)
+    divergence === :itakura_saito && set_divergence!(rule, :itakura_saito)
+    divergence === :beta && set_beta_divergence!(rule, beta)
     scores = Float64[]
     for complement in (0, 1)
         r, d = Ref{Float64}(0.0), Ref{Float64}(0.0)
         check(ccall((:cmf_masked_loss, LIBCMF), Cint, (Ptr{Cvoid}, Cint, Ref{Float64}, Ref{Float64}), rule.handle, complement, r, d))
-        push!(scores, divergence === :kl ? r[] / d[] : sqrt(r[] / d[]))
+        push!(scores, divergence === :square ? sqrt(r[] / d[]) : r[] / d[])
     end
     finalize(rule)
     return scores[1], scores[2]
@@ -490,7 +500,7 @@ function iterate!(rule::HIPMultUpdate, n::Integer; l1W=0, l2W=0, l1H=0, l2H=0, e
     return losses
 end
 
-"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", \"kl_mask\" (set_divergence!(rule, :kl) together with a mask), ..."
+"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", \"kl_mask\" (set_divergence!(rule, :kl) together with a mask), \"pq_mask\" (set_divergence!(rule, :itakura_saito) / set_beta_divergence! together with a mask), ..."
 set_option!(rule::HIPMultUpdate, name::AbstractString, value::Integer) =
     check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), rule.handle, name, value))
 "The ANLS rule's options: \"anls_backup_only\", \"nnls_large\" (include/cmf_hip.h, the ANLS rule)."

@@ -456,6 +456,24 @@ int cmf_mu_set_divergence(cmf_handle h, int kind);
  * of data) over the selected entries.  Turning the option off while both are installed: CMF_ERR_STATE.  Off (the default), every
  * call answers as documented above: CMF_ERR_UNSUPPORTED for the combination.  Groups, the Gram forms, the HALS and PGD entries and
  * real-valued weights stay refused as above. */
+/* The Itakura-Saito and beta forms (below) under a mask: cmf_set_option(h, "pq_mask", 1), exactly in the manner of "kl_mask" (default
+ * 0; values other than 0 and 1: CMF_ERR_ARG; single-GPU handles only; cmf_option_names does not list it; turning it off while a
+ * mask and CMF_DIV_IS or a beta-divergence are both installed: CMF_ERR_STATE).  With it on, mask and divergence may be installed
+ * in either order and cleared in either order, and the MU entries run on
+ *   Q = M .* e.^(beta - 1)  (Itakura-Saito: M ./ e),     P = M .* data .* e.^(beta - 2)  (Itakura-Saito: (data .* Q) .* Q where M == 1)
+ * -- EXACT 0 in both arrays at the held-out entries, by a select: what data holds there (NaN, Inf, negatives) never enters -- with
+ * the contractions, the exponents, the step exponent gamma and the loss terms of the unmasked form.  LOSS (update_feature_maps!,
+ * cmf_compute_loss): the divergence terms summed over the entries with M == 1, divided by their number.  cmf_masked_loss then
+ * returns (sum of the divergence terms, number of entries) over the selected entries; with `complement` the terms are taken on the
+ * RAW data of the held-out entries, which no check has seen: a NaN there makes the sum NaN, and a value below 0 is left out of the
+ * sum while the count still includes it (the epilogue reads "below 0" as "not selected") -- score held-out data that passes the
+ * form's own check.  Data must pass the form's check WHERE
+ * OBSERVED (Itakura-Saito: finite and > 0; beta: finite and >= 0): installing the second of the two checks it, and whatever takes
+ * the MU mask away while the form is installed checks the raw data first -- CMF_ERR_ARG with the form's own text, and the handle as
+ * it was, when a check fails.  A unit or a sample never observed is legal (both sums are 0: its factor entries fall to eps); with
+ * an all-ones mask W and H are those of the unmasked form.  Every switch voids est, the speculated contraction and a deferred loss.
+ * Off (the default), every call answers as documented: CMF_ERR_UNSUPPORTED for the combination.  Groups, the Gram forms and the
+ * HALS and PGD entries stay refused. */
 /* CMF_DIV_IS: the multiplicative update of the Itakura-Saito divergence (beta = 0; beta_loss="itakura-saito" elsewhere), the
  * scale-invariant objective for POWER spectrograms: a quiet harmonic weighs as much as a loud one.  It is taken by
  * cmf_mu_set_divergence only after cmf_set_option(h, "is_div", 1) (default 0; values other than 0 and 1: CMF_ERR_ARG; single-GPU

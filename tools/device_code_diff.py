@@ -2,12 +2,18 @@
 """Are the gfx950 code objects of two checkouts the same device code?  (no GPU needed)
 
     python tools/device_code_diff.py <checkout A> <checkout B>
+    python tools/device_code_diff.py --kernels-of-a <checkout A> <checkout B>
 
 Per csrc/*.hip translation unit: the device-only compile line of tools/kernel_resources.py, clang-offload-bundler
 --unbundle, then `llvm-objdump -d` (without its file-name lines) and `llvm-readelf --notes` of both code objects.  Two
 builds of one source differ in a few bytes of the object file, but not in these two texts: equal texts mean the same
 kernels under the same names with the same instructions, registers, LDS and scratch.  Prints `equal` per translation
 unit, or the first kernel whose instructions or metadata differ; exits 1 if anything differs.
+
+--kernels-of-a: for a checkout B that ADDS kernels to A (a new conv family), where the whole texts cannot be equal: every symbol of
+A's disassembly is looked up by name in B's and its instructions compared with the addresses taken out (the symbol's own address
+and the `// address:` column; encodings stay), and every kernel of A's metadata note is compared with B's of the same name.  Prints
+per translation unit how many of A's kernels B holds unchanged and how many it adds; exits 1 if one of A's is missing or differs.
 """
 import os
 import re
@@ -48,6 +54,34 @@ def demangle(name):
         return name
 
 
+def by_name(text, split, name_of, strip_addresses):
+    """{name: block} of the blocks of `split`; strip_addresses: without the symbol's address and the address column of every line."""
+    out = {}
+    for blk in re.split(split, text)[1:]:
+        name = re.search(name_of, blk).group(1)
+        if strip_addresses:
+            blk = re.sub(r"(?m)^[0-9a-f]+ (<[^>]+>:)", r"\1", re.sub(r"// [0-9A-Fa-f]+:", "//", blk))
+        out[name] = blk.rstrip()
+    return out
+
+
+def kernels_of_a(src, da, na, db, nb):
+    """True when every symbol and every kernel note of A is in B unchanged."""
+    bad = []
+    for what, a, b in (("instructions", by_name(da, SYMBOL, SYMBOL_NAME, True), by_name(db, SYMBOL, SYMBOL_NAME, True)),
+                       ("metadata", by_name(na, NOTE, NOTE_NAME, False), by_name(nb, NOTE, NOTE_NAME, False))):
+        missing = [k for k in a if k not in b]
+        changed = [k for k in a if k in b and a[k] != b[k]]
+        for k in missing + changed:
+            bad.append(f"{src}: {what} of {demangle(k)} {'missing' if k in missing else 'differ'}")
+        if what == "metadata":
+            print(f"{src}: {len(a) - len(missing) - len(changed)} of A's {len(a)} kernels unchanged in B, {len(b) - len(a) + len(missing)} added"
+                  + ("" if not bad else f", {len(bad)} differences"))
+    for line in bad[:20]:
+        print(line)
+    return not bad
+
+
 def first_difference(a, b, split, name_of):
     """The name of the first block (of `split`) that differs between the two texts."""
     for x, y in zip(re.split(split, a), re.split(split, b)):
@@ -58,6 +92,9 @@ def first_difference(a, b, split, name_of):
 
 
 if __name__ == "__main__":
+    per_kernel = "--kernels-of-a" in sys.argv
+    if per_kernel:
+        sys.argv.remove("--kernels-of-a")
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     differ = False
@@ -69,6 +106,9 @@ if __name__ == "__main__":
                 differ = True
                 continue
             (da, na), (db, nb) = texts(src, *ja[src]), texts(src, *jb[src])
+            if per_kernel:
+                differ |= not kernels_of_a(src, da, na, db, nb)
+                continue
             n_kernels = len(re.findall(r"\.agpr_count:", na))
             if da == db and na == nb:
                 print(f"{src}: equal ({n_kernels} kernels, {da.count(chr(10))} lines of disassembly, {na.count(chr(10))} lines of notes)")
