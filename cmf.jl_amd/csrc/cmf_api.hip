@@ -281,7 +281,7 @@ int upload_cols(cmf_handle_s *h, const double *src, int64_t tc, int64_t ncols, b
 }
 
 int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, int64_t L,
-                       const double *data, int64_t t_offset, int64_t T_global, bool sharded)
+                       const double *data, int64_t t_offset, int64_t T_global, bool sharded, long long n_cu_asked)
 {
     if (!out) return fail(CMF_ERR_ARG, "handle pointer is NULL");
     *out = nullptr;
@@ -296,6 +296,11 @@ int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, i
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
+    // test hook CMF_TEST_N_CU (read by the creating entry): plan for fewer CUs than the device has.  Never for more: a plan for CUs that
+    // do not exist could launch a persistent grid whose workgroups are not all resident.
+    const int n_cu_real = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (n_cu_asked != kNoCuHook && (n_cu_asked < 1 || n_cu_asked > n_cu_real))
+        return fail(CMF_ERR_ARG, "CMF_TEST_N_CU=%lld is outside 1 .. %d, the compute units of device %d", n_cu_asked, n_cu_real, device);
 
     cmf_handle_s *h = new cmf_handle_s();
     h->device = device;
@@ -323,7 +328,7 @@ int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, i
         return fail(CMF_ERR_UNSUPPORTED, "W (L*N*K), H (T*K) or a 64-row block of est (64*T or 64*N) exceeds the 2 GiB the "
                                          "kernels' 32-bit buffer offsets address");
     }
-    h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->n_cu = n_cu_asked != kNoCuHook ? (int)n_cu_asked : n_cu_real;
     plan(h, h->n_cu);
     // the C2 kernel addresses a time chunk of X with 32-bit byte offsets: keep chunks below 2 GiB
     while ((double)(h->hxt_chunk_len + 16 * h->hxt_LP + 8) * d.Np * 4.0 >= 2147483648.0) {
@@ -1190,7 +1195,7 @@ int cmf_create(cmf_handle *h, int device, int64_t N, int64_t T, int64_t K, int64
         std::vector<int> devs((size_t)R, device);
         return cmf_create_multi(h, R, devs.data(), CMF_COMM_LOOPBACK, N, T, K, L, data);
     }
-    return create_impl(h, device, N, T, K, L, data, 0, T, false);
+    return create_impl(h, device, N, T, K, L, data, 0, T, false, n_cu_hook());
 }
 
 int cmf_create_shard(cmf_handle *h, int device, int64_t N, int64_t T_local, int64_t K, int64_t L,
@@ -1199,7 +1204,7 @@ int cmf_create_shard(cmf_handle *h, int device, int64_t N, int64_t T_local, int6
     if (!data_local) return fail(CMF_ERR_ARG, "data_local is NULL");
     if (T_local < L - 1 && T_local != T_global)
         return fail(CMF_ERR_UNSUPPORTED, "a shard must hold at least L-1 = %lld columns (got %lld)", (long long)(L - 1), (long long)T_local);
-    return create_impl(h, device, N, T_local, K, L, data_local, t_offset, T_global, true);
+    return create_impl(h, device, N, T_local, K, L, data_local, t_offset, T_global, true, n_cu_hook());
 }
 
 int cmf_shard_set_left_data(cmf_handle h, const double *cols)
@@ -1259,6 +1264,10 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
 {
     if (!h || !name || !value) return fail(CMF_ERR_ARG, "NULL argument");
     if (std::strcmp(name, "hals_pipeline_reruns") == 0) { *value = h->hals_reruns; return CMF_OK; }
+    if (std::strcmp(name, "plan:n_cu") == 0) { // the CU count the plan was dealt for (a group: its shards')
+        *value = (h->root_only && h->group && !h->group->sh.empty()) ? h->group->sh[0]->n_cu : h->n_cu;
+        return CMF_OK;
+    }
     if (std::strcmp(name, "writeback_calls") == 0) { *value = h->wb ? h->wb->armed_calls : 0; return CMF_OK; }            // cmf_arm_writeback calls
     if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss

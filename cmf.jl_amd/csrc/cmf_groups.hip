@@ -1142,10 +1142,11 @@ int cmf_create_multi(cmf_handle *out, int ndev, const int *devices, int transpor
     g->N = N; g->T = T; g->K = K; g->L = L;
     g->t0 = t0; g->t1 = t1;
     auto bail = [&](int rc) { cmf_destroy(root); return rc; };
+    const long long n_cu_asked = n_cu_hook(); // (test hook, read HERE by the calling thread: every shard is planned for it)
     for (int r = 0; r < ndev; ++r) {
         cmf_handle_s *s = nullptr;
         // column-major N x T: the block [t0, t1 + halo_r) is contiguous
-        int rc = create_impl(&s, devices[r], N, t1[r] - t0[r], K, L, data + (size_t)t0[r] * N, t0[r], T, ndev > 1);
+        int rc = create_impl(&s, devices[r], N, t1[r] - t0[r], K, L, data + (size_t)t0[r] * N, t0[r], T, ndev > 1, n_cu_asked);
         if (rc == CMF_OK && s->halo_ext) { // the L-1 columns of data in front of the shard (data' only: the operand of its transconv's front block)
             rc = upload_cols(s, data + (size_t)(t0[r] - s->halo_ext) * N, -s->halo_ext, s->halo_ext, false, false);
             s->left_data = rc == CMF_OK;

@@ -52,6 +52,10 @@ static long long test_hook(const char *name, long long dflt)
     const char *e = getenv(name);
     return e ? atoll(e) : dflt;
 }
+// CMF_TEST_N_CU: the CU count the plan of every handle a creating call makes is dealt for (create_impl), in 1 ... the device's own count.
+// Read by the creating entry (cmf_create, cmf_create_shard, cmf_create_multi) and handed down to create_impl; kNoCuHook: not asked for.
+constexpr long long kNoCuHook = -(1LL << 62);
+static inline long long n_cu_hook() { return test_hook("CMF_TEST_N_CU", kNoCuHook); }
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -635,7 +639,7 @@ void plan(cmf_handle_s *h, int n_cu);
 int upload_cols(cmf_handle_s *h, const double *src, int64_t tc, int64_t ncols, bool rows_layout, bool accumulate_sumsq,
                        float *rows_dst = nullptr, float *cols_dst = nullptr);
 int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, int64_t L,
-                       const double *data, int64_t t_offset, int64_t T_global, bool sharded);
+                       const double *data, int64_t t_offset, int64_t T_global, bool sharded, long long n_cu_asked = kNoCuHook);
 int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, int nsrc, float *slabs, int nchunks, int chunk_len,
                          int main_rows = -1);
 int launch_transconv(cmf_handle_s *h, int nsrc, const float *xt0 = nullptr, bool front_block = false);

@@ -22,7 +22,7 @@
  *   - There is no CPU fallback: without a usable HIP device every compute
  *     entry fails with CMF_ERR_HIP.
  *   - Environment.  Everything that selects a code path is an OPTION (cmf_set_option; cmf_option_names lists them).  The library
- *     reads these ten variables and no others:
+ *     reads these eleven variables and no others:
  *         CMF_WAIT_TIMEOUT_S     bound of every host-side wait (loss words, helper threads, collectives): seconds, default 300
  *         CMF_WRITEBACK_THREADS  widening helpers of cmf_arm_writeback: default 4, at most 16
  *         CMF_ENQUEUE_THREADS    0: the calling thread enqueues every shard of a one-process group (see cmf_create_multi)
@@ -34,6 +34,10 @@
  *           CMF_TEST_FORCE_WORKERS 1: an enqueue worker for a ONE-shard RCCL group too
  *           CMF_TEST_FAIL_SHARD    that shard's next all-reduce call fails (tests of the failure path)
  *           CMF_TEST_NO_ARENA      1: every buffer of a handle is an allocation of its own (an overrun cannot hide in a neighbour)
+ *           CMF_TEST_N_CU          compute units the launches of every handle cmf_create / cmf_create_shard / cmf_create_multi makes are
+ *                                  planned for (the shards of a group included), 1 .. the device's own count; a value outside that
+ *                                  range is CMF_ERR_ARG and no handle is made.  Only fewer CUs than exist can be claimed, so every grid
+ *                                  still fits the chip (tests of the plans of a partitioned device); cmf_get_counter "plan:n_cu"
  */
 #ifndef CMF_HIP_H
 #define CMF_HIP_H
@@ -199,7 +203,9 @@ int cmf_rccl_version(int *version, char *path, int64_t path_len);
  * (1 .. 3), g_gemm_fold_small_kernel:split (the reduction over n in more than one piece), g_gemm_fold_small_kernel:fused_h;
  * gram_w_kernel, gram_lag_corr, gram_w_taps, gram_h_mfma_kernel, gram_h_kernel;  slab_sum_kernel, slab_sum_kernel:carry,
  * slab_sum_small_kernel, slab_sum_small_kernel:carry (with a deferred loss reduction riding on it);  halo_pack2_kernel,
- * halo_unpack2_kernel, halo_pack3_kernel, halo_unpack3_kernel.  An unknown path is CMF_ERR_ARG. */
+ * halo_unpack2_kernel, halo_pack3_kernel, halo_unpack3_kernel.  An unknown path is CMF_ERR_ARG.
+ * "plan:n_cu": the compute-unit count the handle's launches are planned for -- the device's multiProcessorCount, or the test hook
+ * CMF_TEST_N_CU (a group: the value of its shards). */
 int cmf_get_counter(cmf_handle h, const char *name, int64_t *value);
 
 /* Run all work of this handle on an existing HIP stream (hipStream_t passed

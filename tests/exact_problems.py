@@ -192,8 +192,9 @@ def conv3_form(N, T, conv_split=1, n_cu=N_CU):
     return ("whole+" if cut < tiles else "pieces") + str(pieces)
 
 
-def small_k_plan(N, T, K, L, n_cu=N_CU):
-    """(C2 MBW, C2 RV, C3 MBW, C3 RV, C3 pieces NS, conv k pairs) of the few-component kernels (K <= 16, L <= 64)."""
+def small_k_plan(N, T, K, L, n_cu=N_CU, with_c3_ok=False):
+    """(C2 MBW, C2 RV, C3 MBW, C3 RV, C3 pieces NS, conv k pairs) of the few-component kernels (K <= 16, L <= 64); with_c3_ok: (NS,
+    whether the few-component C3 kernel runs) instead."""
     J = L * K
     mblocks = (J + 31) // 32
     MG = (mblocks + 9) // 10
@@ -218,6 +219,8 @@ def small_k_plan(N, T, K, L, n_cu=N_CU):
     ns = max(1, min(8, (8 * n_cu + waves - 1) // waves, max(1, rounds // 8)))
     rps = (rounds + ns - 1) // ns
     NS = (rounds + rps - 1) // rps
+    if with_c3_ok:  # (the few-component C3 runs at all: at least two waves per CU, else the general transconv_kernel)
+        return NS, waves * NS >= 2 * n_cu
     return MBW, RV, MBW3, RV3, NS, (K + 1) // 2
 
 
@@ -283,6 +286,139 @@ def conv_small_form(N, T, conv_split=1, n_cu=N_CU):
     if conv_split and tiles < per_round:
         cut = tiles
     return tiles - cut, cut
+
+
+def hxt_chunks(N, T, K, L, nsrc=2, n_cu=N_CU):
+    """(time chunks, rows per chunk, rows the chunks cover) of a C2 launch over nsrc sources (cmf_api.hip plan(): chunks).  Rows covered
+    < T: the rows behind the last whole ring rotation are left to the slab sum ("hxt_kernel:tail")."""
+    lp = hxt_lp(L)
+    groups = rup(L, 2 * lp) // (2 * lp)
+    slots = 4 * n_cu * (2 if lp <= 5 else 1)
+    per_chunk = rup(N, 128) // 32 * nsrc * ((K + 31) // 32) * groups
+    unit = 6 * lp
+    nch = max(1, (slots + per_chunk // 2) // per_chunk)
+    units_all, units_whole = (T + unit - 1) // unit, T // unit
+    per, main = (units_all + nch - 1) // nch, T
+    if units_whole > 0 and (units_whole + nch - 1) // nch < per:
+        per, main = (units_whole + nch - 1) // nch, units_whole * unit
+    return (main + per * unit - 1) // (per * unit), per * unit, main
+
+
+def tc_plan(N, T, K, nsrc=2, n_cu=N_CU, extra_blocks=0):
+    """(waves W, fragment slabs F, XCD placement) of a C3 launch over nsrc sources (cmf_api.hip plan(): tc_plan)."""
+    C = rup(N, 8) // 8
+    U = ((T + 127) // 128 + extra_blocks) * ((K + 31) // 32) * nsrc * C
+    W = min(8 * n_cu, U)
+    F = 1
+    for w in range(W):
+        pr = (w * U // W) // C
+        F = max(F, w - ((pr * C + 1) * W - 1) // U + 1)
+    return W, F, W >= 64 and W % 32 == 0
+
+
+# ---- the same kernel paths under plans for fewer compute units (tests/test_gpu_exact_cu_plans.py) ------------------------------
+# Every plan rule above is a function of the CU count the device reports; a partitioned MI355X shows 128, 64 or 32.  The library's test
+# hook CMF_TEST_N_CU plans a handle for such a count on the whole chip.  The integer problems are exact in any summation order, so the
+# assertions of tests/test_exact_parity.py hold unchanged under every plan, and the bits must be those of the handle planned for the
+# whole chip.  Rows: (N, T, K, L, configurations, {launch path: reached or not}) -- the paths a row was chosen for AT THAT COUNT, for a
+# one-device configuration without options unless the key carries one ("path|option=value"); tests/test_exact_problems.py holds every
+# claim to the mirrors, the GPU file to the launch counters.
+CU_COUNTS = (128, 64, 32, 1, 38)  # the partition sizes; the degenerate plan; a count that is no multiple of 4 (no XCD placement, no chase)
+CU_FULL = (128, 64, 32)           # the counts that run the whole table and must reach CU_PATHS
+_G2H, _G3 = dict(devices=[0] * 2, halo_in_allreduce=1), dict(devices=[0] * 3)
+_C32 = [dict(), dict(conv_split=0), dict(conv_split=4)]
+_SK = [dict(), dict(small_k=0), dict(conv_split=0), dict(small_k=2, small_k_fuse=2)]
+
+
+_TAIL_T = {128: 961, 64: 481, 32: 481, 38: 301, 1: 448}  # the shortest recordings of 130 units whose C2 chunks leave tail rows to the slab sum
+
+
+def _cu_rows(n_cu):
+    """The rows of one count: the K = 32, L = 20 rows scale with the count (a conv3 form is a statement about tiles per CU), the
+    few-component and general rows are the same shapes taking other branches.  The last entry names what the row is there for at
+    that count; cu_plan says which branches it takes."""
+    s = n_cu // 32
+    one = n_cu == 1
+    rows = [
+        (130, 448, 32, 20, _C32 + [dict(gram=1), dict(gram=2), _G2H, _G3], ["conv3_kernel:whole", "hxt_kernel:tail"] if one else ["conv3_kernel:pieces16"]),
+        (130, 700, 32, 20, _C32, ["conv3_kernel:whole"] if one else ["conv3_kernel:pieces4" if n_cu <= 44 else "conv3_kernel:pieces16"]),
+        (250, 1500, 32, 20, [dict(), _G2H], ["conv3_kernel:whole+4"] if one else ["transconv_kernel:xcd"] if n_cu % 4 == 0 else ["!transconv_kernel:xcd"]),
+        (70, 600, 20, 10, [dict(), dict(gram=1), dict(gram=2), dict(devices=[0] * 2)], ["hxt_kernel:no_tail"]),
+        (90, 610, 5, 7, _SK, ["conv_small_kernel:whole"] if one else ["conv_small_kernel:quarter", "conv_small_kernel:pre"]),
+        (250, 1500, 5, 20, _SK, ["g_gemm_fold_small_kernel<*>", "!g_gemm_fold_small_kernel:split"] if one else ["g_gemm_fold_small_kernel:split"]),
+    ]
+    if not one:
+        rows.append((130, _TAIL_T[n_cu], 32, 20, [dict()], ["hxt_kernel:tail"]))
+    if n_cu in CU_FULL:
+        rows += [
+            (250, 3200 * s, 32, 20, _C32, ["conv3_kernel:whole", "transconv_kernel:xcd"]),
+            (250, 6400 * s, 32, 20, _C32, ["conv3_kernel:whole+16"]),
+            (250, 7040 * s, 32, 20, _C32, ["conv3_kernel:whole+4"]),
+            (1000, 4100 * n_cu // 256 + 60, 8, 10, _SK, ["conv_small_kernel:whole", "conv_small_kernel:quarter", "conv_small_kernel:pre"]),
+            (90, 32 * n_cu, 5, 7, [dict()], ["g_gemm_fold_small_kernel<*>", "!g_gemm_fold_small_kernel:split"]),  # the few-component C3 in ONE piece
+        ]
+    return rows
+
+
+CU_SHAPES = {n_cu: _cu_rows(n_cu) for n_cu in CU_COUNTS}
+CU_SHAPES[32].append((500, 12800, 32, 20, [dict(), dict(conv_split=0)], ["conv3_kernel:whole+4"]))  # four whole rounds and the extra cut
+# what the union over the rows of each of CU_FULL must reach
+CU_PATHS = ["conv3_kernel:whole", "conv3_kernel:whole+4", "conv3_kernel:whole+16", "conv3_kernel:pieces4", "conv3_kernel:pieces16",
+            "conv_small_kernel:quarter", "conv_small_kernel:pre", "conv_small_kernel:whole", "hxt_kernel:tail", "hxt_kernel:no_tail",
+            "transconv_kernel:xcd", "transconv_kernel:front_block", "g_gemm_fold_small_kernel:split", "slab_sum_kernel:carry",
+            "gram_w_kernel", "gram_h_mfma_kernel"]
+
+
+def cu_plan(N, T, K, L, cfg=None, n_cu=N_CU):
+    """What the mirrors say a ONE-DEVICE handle of the shape launches under cfg at n_cu: {launch path: True (reached) / False (not)} for
+    the paths whose choice depends on the count."""
+    cfg = cfg or {}
+    split = cfg.get("conv_split", 1)
+    out = {}
+    small = K <= 16 and L <= 64 and cfg.get("small_k", 1) != 0
+    if small:
+        whole, cut = conv_small_form(N, T, split, n_cu)
+        tiles = whole + cut
+        ns, c3 = small_k_plan(N, T, K, L, n_cu, True)
+        c3 = c3 or cfg.get("small_k") == 2  # (2: the few-component C3 whatever the plan says)
+        out.update({"conv_small_kernel:quarter": cut > 0, "conv_small_kernel:whole": whole > 0,
+                    "conv_small_kernel:pre": (K + 1) // 2 <= 4 and tiles <= 16 * n_cu,
+                    "g_gemm_fold_small_kernel<*>": c3,  # (any instance: the few-component C3 runs)
+                    "g_gemm_fold_small_kernel:split": c3 and ns > 1})
+    elif K % 32 == 0:
+        out.update({"conv3_kernel:" + f: f == conv3_form(N, T, split, n_cu) for f in ("whole", "whole+4", "whole+16", "pieces4", "pieces16")})
+    if not small or cfg.get("gram"):
+        nch, clen, main = hxt_chunks(N, T, K, L, 1 if cfg.get("gram") == 1 else 2, n_cu)
+        out.update({"hxt_kernel:tail": main < T, "hxt_kernel:no_tail": main == T})
+    if not small:
+        out["transconv_kernel:xcd"] = tc_plan(N, T, K, 1 if cfg.get("gram") else 2, n_cu)[2]
+    return out
+
+
+# The storing epilogues and the cut tiles' loss partials differ per conv family: the masked MU rule, the PGD rule and the divergence
+# forms "is" and "kl_mask" run at 32 CUs on one row per conv3 form and two few-component rows (quarter pieces only; whole tiles + tail)
+CU_EPILOGUE_N_CU = 32
+CU_EPILOGUE_ROWS = [r for r in CU_SHAPES[32] if r[:4] in {(130, 448, 32, 20), (130, 700, 32, 20), (250, 3200, 32, 20), (250, 6400, 32, 20),
+                                                         (250, 7040, 32, 20), (90, 610, 5, 7), (1000, 572, 8, 10)}]
+CU_EPILOGUE_FORMS = ("is", "kl_mask")
+
+# The HALS sweeps under fewer CUs: rows of HALS_SHAPES (the bars of profiles/exact_hals.txt are made from them), each with the sweep
+# configurations to run and what hals_plan must say at that count: (cfg, pullers per row -- 0: the stage pipeline --, chased or not).
+# 134 is for the chase alone: divisible by 2 but not by 8, and large enough that every other condition of the chase holds.
+_CHASE2 = dict(hals_chase=65, hals_persist=2)
+CU_HALS_SHAPES = {
+    128: [(37, 700, 18, 20, [(dict(), 4, False), (dict(hals_persist=3), 3, False)]),
+          (37, 768, 32, 8, [(dict(), 3, False), (dict(hals_persist=2), 2, False)]),         # K = 32: (128 - 32) / 31 = 3 pullers fit
+          (37, 1300, 64, 20, [(dict(), 0, False)]),                                       # K = 64: one puller per row fits -- the stage pipeline
+          (130, 9000, 32, 20, [(_CHASE2, 2, True), (dict(hals_chase=65), 3, False)])],    # chased with 8 (16 - 12) = 32 CUs beside the pipeline (256 CUs: 128); 3 pullers leave none
+    64: [(37, 150, 5, 4, [(dict(), 4, False)]),
+         (37, 700, 18, 20, [(dict(), 2, False)]),                                         # (64 - 18) / 17 = 2
+         (37, 700, 32, 20, [(dict(), 0, False)])],                                        # K = 32 at 64 CUs: (64 - 32) / 31 = 1 < 2 -- the stage pipeline
+    32: [(37, 150, 5, 4, [(dict(), 4, False), (dict(hals_persist=2), 2, False), (dict(hals_persist=3), 3, False)]),
+         (37, 700, 18, 20, [(dict(), 0, False)])],
+    38: [(37, 150, 5, 4, [(dict(), 4, False)]), (9, 200, 4, 64, [(dict(), 4, False)])],
+    134: [(130, 9000, 32, 20, [(_CHASE2, 2, False)])],                                    # 134 / 8 - 12 >= 4 as at 128, but 134 % 8 != 0: no chase
+}
 
 
 # ---- the divergence forms of the MU rule on these problems (tests/test_gpu_divergence_paths.py) ------------------------------
@@ -797,7 +933,8 @@ def hals_plan(N, T, K, L, cfg=None, n_cu=N_CU):
             P = 3
     p["P"] = P
     rows, ra = (T + 63) // 64, 0
-    if chase != 0 and P > 0 and K % 32 == 0 and cfg.get("hals_gram", 2) != 1 and n_cu // 8 - (K + (K - 1) * P + 7) // 8 >= 4 and rows >= 64:
+    if (chase != 0 and P > 0 and K % 32 == 0 and cfg.get("hals_gram", 2) != 1 and n_cu % 8 == 0 and n_cu <= 256  # (the CU masks cut inside every XCD)
+            and n_cu // 8 - (K + (K - 1) * P + 7) // 8 >= 4 and rows >= 64):
         pct = chase
         if pct < 0:
             conv_ms = 2.0 * K * N * (L * T) / (0.87 * 157.3e12) * 1e3

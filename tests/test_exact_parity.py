@@ -9,7 +9,8 @@ also give the same bits: num and den are exact, and every path applies the same 
 
 The shape table (exact_problems.SHAPES, shared with tests/test_gpu_divergence_paths.py) is derived from the plan rules (cmf_api.hip plan(), cmf_internal.h launch_conv) on a 256-CU MI355X; the
 launch counters (cmf_get_counter "launches:<path>") record which instances each shape reached, and the last test asserts
-that the table reaches every named path."""
+that the table reaches every named path.  tests/test_gpu_exact_cu_plans.py makes the same assertions (mu_references, run_mu_config
+below) on handles planned for 128, 64, 32, 38 and 1 CUs, where the same shapes take other branches."""
 import os
 import time
 
@@ -110,65 +111,82 @@ def check_same(got, base, names, what, cfg, base_cfg, c):
         raise AssertionError(f"{what} {cfg} differs from {base_cfg} at {first_bad(got != base, names)}; launches {reached(c)}")
 
 
+def mu_references(oracle, shape):
+    """The two integer problems of a shape, their fp64 halves and losses, with the preconditions asserted from the arrays: computed once
+    per shape (tests/test_gpu_exact_cu_plans.py shares them across the CU counts)."""
+    N, T, K, L = shape
+    r = dict(shape=shape)
+    r["Ww"], r["Hw"], r["X"] = make_problem(N, T, K, L, "W")
+    est_w, numW, denW, r["W_ref"] = oracle_w_half(oracle, r["X"], r["Ww"], r["Hw"])
+    assert_preconditions(numW, denW, est_w, shape)
+    r["Wh"], r["Hh"], _ = make_problem(N, T, K, L, "H")
+    est_h, numH, denH, r["H_ref"], r["lossH_ref"] = oracle_h_half(oracle, r["X"], r["Wh"], r["Hh"])
+    assert_preconditions(numH, denH, est_h, shape)
+    r["loss_w_ref"], r["loss_h_ref"] = oracle.compute_loss(r["X"], r["Ww"], r["Hw"]), oracle.compute_loss(r["X"], r["Wh"], r["Hh"])
+    r["loss_exact"] = max(max_tile_sumsq(est_w, r["X"]), max_tile_sumsq(est_h, r["X"])) <= EXACT
+    return r
+
+
+def run_mu_config(cmf, cfg, r, record=lambda c: None):
+    """One configuration of a row against the references r: (W after the W half, H after the H half, launch counters), everything
+    test_exact_mu_paths asserts per configuration asserted."""
+    X, Ww, Hw, Wh, Hh = r["X"], r["Ww"], r["Hw"], r["Wh"], r["Hh"]
+    rule = make_rule(cmf, cfg, X, Ww, Hw)
+    try:
+        lw = rule.compute_loss()
+        rule.update_motifs(l1W=L1, l2W=L2)
+        Wg, _ = rule.download()
+        rule.upload(Ww, Hw)
+        rule.iterate(1, l1W=L1, l2W=L2, l1H=L1, l2H=L2)
+        Wi, _ = rule.download()
+        # pipelined iterations (the loss reduction deferred onto the next launch) are the call-by-call loop, bit for bit
+        rule.upload(Ww, Hw)
+        li = list(rule.iterate(2, l1W=L1, l2W=L2, l1H=L1, l2H=L2))
+        Wi2, Hi2 = rule.download()
+        rule.upload(Ww, Hw)
+        lc = []
+        for _ in range(2):
+            rule.update_motifs(l1W=L1, l2W=L2)
+            lc.append(rule.update_feature_maps(l1H=L1, l2H=L2))
+        Wc2, Hc2 = rule.download()
+        c = counters(rule)
+    finally:
+        rule.close()
+    assert li == lc, f"{cfg}: iterate(2) losses {li} != call by call {lc}"
+    check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
+    check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
+    rule = make_rule(cmf, cfg, X, Wh, Hh)
+    try:
+        lh = rule.compute_loss()
+        lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
+        _, Hg = rule.download()
+        ch = counters(rule)
+    finally:
+        rule.close()
+    c = {p: c[p] + ch[p] for p in c}
+    record(c)
+    if r["loss_exact"]:
+        assert (lw, lh) == (r["loss_w_ref"], r["loss_h_ref"]), f"loss {cfg}: {(lw, lh)} != {(r['loss_w_ref'], r['loss_h_ref'])}; launches {reached(c)}"
+    else:  # (some 64 x 64 tile sum of (est - X)^2 may exceed 2^24: not exact by construction)
+        np.testing.assert_allclose([lw, lh], [r["loss_w_ref"], r["loss_h_ref"]], rtol=1e-6)
+    np.testing.assert_allclose(lh1, r["lossH_ref"], rtol=1e-5)  # (H is no longer integer: today's bar)
+    check_factor(Wg, r["W_ref"], "knl", "W half: W", cfg, c)
+    check_factor(Hg, r["H_ref"], "kt", "H half: H", cfg, c)
+    check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+    return Wg, Hg, c
+
+
 @pytest.mark.parametrize("N,T,K,L,configs,why", SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in SHAPES])
 def test_exact_mu_paths(cmf, oracle, N, T, K, L, configs, why):
     shape = (N, T, K, L)
     t0 = time.perf_counter()
-    Ww, Hw, X = make_problem(N, T, K, L, "W")
-    est_w, numW, denW, W_ref = oracle_w_half(oracle, X, Ww, Hw)
-    assert_preconditions(numW, denW, est_w, shape)
-    Wh, Hh, _ = make_problem(N, T, K, L, "H")
-    est_h, numH, denH, H_ref, lossH_ref = oracle_h_half(oracle, X, Wh, Hh)
-    assert_preconditions(numH, denH, est_h, shape)
-    loss_w_ref, loss_h_ref = oracle.compute_loss(X, Ww, Hw), oracle.compute_loss(X, Wh, Hh)
-    loss_exact = max(max_tile_sumsq(est_w, X), max_tile_sumsq(est_h, X)) <= EXACT
+    r = mu_references(oracle, shape)
     t_oracle = time.perf_counter() - t0
     base = None
     for cfg in configs:
         if T // len(cfg.get("devices", [0])) < 2 * L:
             continue  # (shards shorter than two lag windows: not a shape a group takes)
-        rule = make_rule(cmf, cfg, X, Ww, Hw)
-        try:
-            lw = rule.compute_loss()
-            rule.update_motifs(l1W=L1, l2W=L2)
-            Wg, _ = rule.download()
-            rule.upload(Ww, Hw)
-            rule.iterate(1, l1W=L1, l2W=L2, l1H=L1, l2H=L2)
-            Wi, _ = rule.download()
-            # pipelined iterations (the loss reduction deferred onto the next launch) are the call-by-call loop, bit for bit
-            rule.upload(Ww, Hw)
-            li = list(rule.iterate(2, l1W=L1, l2W=L2, l1H=L1, l2H=L2))
-            Wi2, Hi2 = rule.download()
-            rule.upload(Ww, Hw)
-            lc = []
-            for _ in range(2):
-                rule.update_motifs(l1W=L1, l2W=L2)
-                lc.append(rule.update_feature_maps(l1H=L1, l2H=L2))
-            Wc2, Hc2 = rule.download()
-            c = counters(rule)
-        finally:
-            rule.close()
-        assert li == lc, f"{cfg}: iterate(2) losses {li} != call by call {lc}"
-        check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
-        check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
-        rule = make_rule(cmf, cfg, X, Wh, Hh)
-        try:
-            lh = rule.compute_loss()
-            lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
-            _, Hg = rule.download()
-            ch = counters(rule)
-        finally:
-            rule.close()
-        c = {p: c[p] + ch[p] for p in c}
-        record(c)
-        if loss_exact:
-            assert (lw, lh) == (loss_w_ref, loss_h_ref), f"loss {cfg}: {(lw, lh)} != {(loss_w_ref, loss_h_ref)}; launches {reached(c)}"
-        else:  # (some 64 x 64 tile sum of (est - X)^2 may exceed 2^24: not exact by construction)
-            np.testing.assert_allclose([lw, lh], [loss_w_ref, loss_h_ref], rtol=1e-6)
-        np.testing.assert_allclose(lh1, lossH_ref, rtol=1e-5)  # (H is no longer integer: today's bar)
-        check_factor(Wg, W_ref, "knl", "W half: W", cfg, c)
-        check_factor(Hg, H_ref, "kt", "H half: H", cfg, c)
-        check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+        Wg, Hg, c = run_mu_config(cmf, cfg, r, record=record)
         if base is None:
             base = (cfg, Wg, Hg)
         else:

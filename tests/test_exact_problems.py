@@ -772,3 +772,107 @@ def test_hals_check_reports_the_worst_element():
     got[j] = 1e-30  # within any bar of 0, but not ON the clamp
     worst, msg = ep.check_hals(got, a, 8.0, "kt")
     assert worst < 1 and msg.startswith(f"zero pattern differs at k={j[0]}, t={j[1]}")
+
+
+# ---- the plans for fewer compute units (tests/test_gpu_exact_cu_plans.py) ----------------------------------------------------------
+def _claims(row, n_cu):
+    """[(launch path, reached or not)] a row of CU_SHAPES is there for at its count, and what the mirrors say about each."""
+    N, T, K, L, configs, why = row
+    plan = ep.cu_plan(N, T, K, L, {}, n_cu)
+    return [(w.lstrip("!"), not w.startswith("!"), plan.get(w.lstrip("!"))) for w in why]
+
+
+def test_cu_plan_rows_take_the_branches_they_are_there_for():
+    """From the mirrors alone: every row of CU_SHAPES reaches, at its count, the form its last entry claims; each of 128, 64 and 32 CUs
+    reaches every count-dependent path; the candidate rows of the 32-CU table are the forms they were chosen for; and the same shapes
+    take OTHER branches on the whole chip (which is why the whole-chip table cannot stand in for them)."""
+    assert set(ep.CU_COUNTS) == {128, 64, 32, 1, 38} and all(n % 4 for n in ep.CU_COUNTS if n not in ep.CU_FULL)
+    for n_cu in ep.CU_COUNTS:
+        assert dict() in [c for row in ep.CU_SHAPES[n_cu] for c in row[4]]
+        for row in ep.CU_SHAPES[n_cu]:
+            assert row[4][0] == dict() and row[5], row  # (the claims are about the configuration without options)
+            for path, want, got in _claims(row, n_cu):
+                assert got is want, f"{row[:4]} at {n_cu} CUs: the row is there for {path} = {want}, the mirror says {got}"
+            for family in ("W", "H"):
+                b = ep.preconditions(*row[:4], family)
+                assert b["exact"] and b["sensitive"] and b["loss_exact"], (row[:4], family, b)
+        if n_cu not in ep.CU_FULL:
+            assert max(r[0] * r[1] for r in ep.CU_SHAPES[n_cu]) <= 250 * 1500  # (1 and the odd count: the small rows only)
+    assert max(r[0] * r[1] for n in ep.CU_COUNTS for r in ep.CU_SHAPES[n]) <= 1.15 * 500 * 12800
+    for n_cu in ep.CU_FULL:
+        reached = set()
+        for N, T, K, L, configs, why in ep.CU_SHAPES[n_cu]:
+            for cfg in configs:
+                if "devices" in cfg:
+                    if cfg.get("halo_in_allreduce") == 1 and K % 32 == 0 and T // len(cfg["devices"]) >= 2 * L:
+                        reached.add("transconv_kernel:front_block")
+                    continue
+                reached |= {p for p, v in ep.cu_plan(N, T, K, L, cfg, n_cu).items() if v}
+                if cfg.get("gram"):
+                    reached |= {"gram_w_kernel", "gram_h_mfma_kernel"}
+            if K > 16:
+                reached.add("slab_sum_kernel:carry")  # (iterate(2) of the general kernels: the deferred loss rides on the slab sum)
+        assert reached >= set(ep.CU_PATHS), (n_cu, sorted(set(ep.CU_PATHS) - reached))
+        assert {r[:4] for r in ep.CU_SHAPES[n_cu] if r[2] == 32} >= {(130, 448, 32, 20), (130, 700, 32, 20)}
+        plans = [ep.cu_plan(*r[:4], {}, n_cu) for r in ep.CU_SHAPES[n_cu] if r[2] > 16]
+        assert {p["transconv_kernel:xcd"] for p in plans} == {True, False} and {p["hxt_kernel:tail"] for p in plans} == {True, False}
+        small = [ep.cu_plan(*r[:4], {}, n_cu) for r in ep.CU_SHAPES[n_cu] if r[2] <= 16]
+        assert {(p["g_gemm_fold_small_kernel<*>"], p["g_gemm_fold_small_kernel:split"]) for p in small} >= {(True, True), (True, False)}
+    forms32 = {(130, 448): "pieces16", (130, 700): "pieces4", (250, 3200): "whole", (250, 6400): "whole+16", (250, 7040): "whole+4", (500, 12800): "whole+4"}
+    for (N, T), form in forms32.items():
+        assert ep.conv3_form(N, T, n_cu=32) == form and (N, T, 32, 20) in [r[:4] for r in ep.CU_SHAPES[32]]
+    assert ep.conv3_cut(500, 12800, n_cu=32) == (1440, 160, 4) and 1600 // (12 * 32) >= 4  # four whole rounds and the extra cut
+    assert ep.conv3_form(130, 700) == "pieces16" and ep.conv3_form(500, 12800) == "whole" and ep.conv3_form(250, 3200) == "pieces16"  # (256 CUs)
+    assert ep.hxt_chunks(130, 700, 32, 20, n_cu=1) == (1, 690, 690) and ep.tc_plan(130, 700, 32, n_cu=1)[0] == 8  # the degenerate plan
+    assert not ep.tc_plan(250, 1500, 32, n_cu=38)[2] and ep.tc_plan(250, 1500, 32, n_cu=38)[0] == 8 * 38 and ep.tc_plan(250, 1500, 32, n_cu=32)[2]
+    assert {r[:4] for r in ep.CU_EPILOGUE_ROWS if r[2] == 32} == {(N, T, 32, 20) for (N, T) in forms32 if N < 500} and len(ep.CU_EPILOGUE_ROWS) == 7
+
+
+def test_cu_plan_mirrors_restate_the_library_rules():
+    """The constants the new mirrors share with cmf_api.hip plan(): a change there must be made here."""
+    src = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_api.hip")).read()
+    for text in ("const int wave_slots = 4 * n_cu * (best <= 5 ? 2 : 1);", "const int unit = 6 * best;", "(wave_slots + waves_per_chunk / 2) / waves_per_chunk",
+                 "const long long W = std::min<long long>(8LL * n_cu, U);", "if (W >= 64 && W % 32 == 0) {", "h->sk_tc_ok = waves * h->sk3_NS >= 2LL * n_cu;"):
+        assert text in src, text
+    rules = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_rules.hip")).read()
+    assert "if (h->n_cu % 8 != 0 || h->n_cu > 256) return 0;" in rules
+    # the whole-chip values the library's comments state: T = 6250 over 8 chunks is 26 rotations + 10 rows (config 2's T / 8 shard)
+    assert ep.hxt_chunks(2000, 6250, 32, 20) == (8, 780, 6240)
+    assert ep.hxt_chunks(2000, 50000, 32, 20)[0] == 8 and ep.tc_plan(2000, 6250, 32)[0] == 2048
+
+
+def test_cu_hals_rows_take_the_pipelines_they_are_there_for():
+    rows = {s[:4] for s in ep.HALS_SHAPES}
+    got = {}
+    for n_cu, table in ep.CU_HALS_SHAPES.items():
+        for N, T, K, L, configs in table:
+            assert (N, T, K, L) in rows  # (the bars of profiles/exact_hals.txt are made from the rows of HALS_SHAPES)
+            for cfg, P, chased in configs:
+                plan = ep.hals_plan(N, T, K, L, cfg, n_cu=n_cu)
+                assert (plan["P"], plan["chase"] > 0) == (P, chased), (n_cu, (N, T, K, L), cfg, plan)
+                got.setdefault(n_cu, set()).add((P, chased))
+    assert {p for n in (128, 64, 32) for p, _ in got[n]} >= {0, 2, 3, 4}
+    assert (0, False) in got[64] and ep.hals_plan(37, 700, 32, 20, {}, n_cu=64)["P"] == 0 and ep.hals_plan(37, 700, 32, 20, {})["P"] == 4
+    assert {p for p, _ in got[32]} >= {2, 3, 4}
+    # the chased form with fewer CUs beside the pipeline than on the whole chip: 8 (16 - 12) = 32 at 128 CUs, 8 (32 - 16) = 128 at 256
+    assert (2, True) in got[128] and 128 // 8 - (32 + 31 * 2 + 7) // 8 == 4 and 256 // 8 - (32 + 31 * 3 + 7) // 8 == 16
+    # ... and off where the count is no multiple of 8, although every other condition holds as at 128
+    assert got[134] == {(2, False)} and 134 // 8 - (32 + 31 * 2 + 7) // 8 >= 4 and got[38] == {(4, False)}
+
+
+def test_two_ulp_check_sees_the_errors_a_replanned_chunking_could_make():
+    """What a seam error of a plan for fewer CUs does to the W half of the row chosen for the tail rows at 32 CUs, (130, 481, 32, 20):
+    8 chunks of 60 rows cover 480 rows and row 480 is left to the slab sum.  That one row lost, or every chunk one ring rotation (30
+    rows) short, fails the 2 ulp bar by orders of magnitude -- and so does the bit-identity with the whole-chip plan."""
+    N, T, K, L = 130, 481, 32, 20
+    nch, clen, main = ep.hxt_chunks(N, T, K, L, n_cu=32)
+    assert (nch, clen, main) == (8, 60, 480) and ep.hxt_chunks(N, T, K, L) != (nch, clen, main)
+    W, H, X = ep.make_problem(N, T, K, L, "W")
+    ref = _w_half(W, H, X)
+    assert ep.ulps(ref.astype(np.float32), ref).max() <= 1
+    tail = _w_half(W, H, X, drop_t=np.arange(main, T))
+    short = _w_half(W, H, X, drop_t=np.concatenate([np.arange(c * clen + clen - 30, c * clen + clen) for c in range(nch)]))
+    u_tail, u_short = ep.ulps(tail.astype(np.float32), ref), ep.ulps(short.astype(np.float32), ref)
+    print(f"tail row lost: {u_tail.max():.0f} ulp on {(u_tail > 2).sum()} elements; chunks one rotation short: {u_short.max():.0f} ulp on {(u_short > 2).sum()} elements")
+    assert u_tail.max() > 1000 and (u_tail > 2).sum() >= 0.9 * N  # (row 480's component: its lag-0 entry of every unit whose X there is not 0)
+    assert u_short.max() > 1000 and (u_short > 2).mean() > 0.9

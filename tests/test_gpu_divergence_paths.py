@@ -108,63 +108,74 @@ def reference(form, shape, family, zeros):
 IDS = [f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in SHAPES]
 
 
+def references(form, shape, zeros):
+    """(the W family's reference(), the H family's) of a form on a row, once per shape."""
+    return reference(form, shape, "W", zeros), reference(form, shape, "H", zeros)
+
+
+def run_divergence_config(cmf, form, cfg, K, refs, record=record):
+    """One configuration of a row under a form against references(): (W after the W half, H after the H half, launch counters),
+    everything test_divergence_mu_paths asserts per configuration asserted."""
+    (Ww, Hw, Xw, mask, aw), (Wh, Hh, Xh, _, ah) = refs
+    W_ref, H_ref, lossH_ref = aw["new"], ah["new"], ah["loss"]
+    rule = make_rule(cmf, form, cfg, Xw, mask, Ww, Hw)
+    try:
+        rule.update_motifs(l1W=L1, l2W=L2)
+        Wg, _ = rule.download()
+        rule.upload(Ww, Hw)
+        rule.iterate(1, **REG)
+        Wi, _ = rule.download()
+        # pipelined iterations (the loss reduction deferred onto the next launch) are the call-by-call loop, bit for bit
+        rule.upload(Ww, Hw)
+        li = list(rule.iterate(2, **REG))
+        Wi2, Hi2 = rule.download()
+        rule.upload(Ww, Hw)
+        lc = []
+        for _ in range(2):
+            rule.update_motifs(l1W=L1, l2W=L2)
+            lc.append(rule.update_feature_maps(l1H=L1, l2H=L2))
+        Wc2, Hc2 = rule.download()
+        c = counters(rule)
+    finally:
+        rule.close()
+    assert li == lc, f"{form} {cfg}: iterate(2) losses {li} != call by call {lc}"
+    assert np.isfinite(li).all() and np.isfinite(Wi2).all() and np.isfinite(Hi2).all() and min(Wi2.min(), Hi2.min()) >= EPS
+    check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
+    check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
+    rule = make_rule(cmf, form, cfg, Xh, mask, Wh, Hh)
+    try:
+        lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
+        Wd, Hg = rule.download()
+        if cfg == dict(conv_kernel=3) and K % 32 == 0:
+            # The loss + store base (what update_feature_maps! ran: est is kept) and the loss-only base (reuse_est = 0) run on the
+            # same one-wave tiles with the same cut, and their terms are rounded alike (cmf_kernels.h at cmf_is_term): the same
+            # partials in the same order, so the same bits.  The factors are uploaded again so that the loss is computed anew.
+            rule.set_option("reuse_est", 0)
+            rule.upload(Wd, Hg)
+            l_only = rule.compute_loss()
+            assert l_only == lh1, f"{form} {cfg}: the loss-only base gives {l_only!r}, loss + store gave {lh1!r}"
+        ch = counters(rule)
+    finally:
+        rule.close()
+    c = {p: c[p] + ch[p] for p in c}
+    record(form, c)
+    check_loss(form, lh1, lossH_ref, "update_feature_maps!", cfg, c)
+    check_factor(form, Wg, W_ref, "knl", "W half: W", cfg, c)
+    check_factor(form, Hg, H_ref, "kt", "H half: H", cfg, c)
+    check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+    return Wg, Hg, c
+
+
 @pytest.mark.parametrize("form,zeros", VARIANTS, ids=[f + ("+zeros" if z else "") for f, z in VARIANTS])
 @pytest.mark.parametrize("N,T,K,L,configs,why", SHAPES, ids=IDS)
 def test_divergence_mu_paths(cmf, N, T, K, L, configs, why, form, zeros):
     shape = (N, T, K, L)
     t0 = time.perf_counter()
-    Ww, Hw, Xw, mask, aw = reference(form, shape, "W", zeros)
-    Wh, Hh, Xh, _, ah = reference(form, shape, "H", zeros)
-    W_ref, H_ref, lossH_ref = aw["new"], ah["new"], ah["loss"]
-    del aw, ah
+    refs = references(form, shape, zeros)
     t_ref = time.perf_counter() - t0
     base = None
     for cfg in ep.divergence_configs(configs, form):
-        rule = make_rule(cmf, form, cfg, Xw, mask, Ww, Hw)
-        try:
-            rule.update_motifs(l1W=L1, l2W=L2)
-            Wg, _ = rule.download()
-            rule.upload(Ww, Hw)
-            rule.iterate(1, **REG)
-            Wi, _ = rule.download()
-            # pipelined iterations (the loss reduction deferred onto the next launch) are the call-by-call loop, bit for bit
-            rule.upload(Ww, Hw)
-            li = list(rule.iterate(2, **REG))
-            Wi2, Hi2 = rule.download()
-            rule.upload(Ww, Hw)
-            lc = []
-            for _ in range(2):
-                rule.update_motifs(l1W=L1, l2W=L2)
-                lc.append(rule.update_feature_maps(l1H=L1, l2H=L2))
-            Wc2, Hc2 = rule.download()
-            c = counters(rule)
-        finally:
-            rule.close()
-        assert li == lc, f"{form} {cfg}: iterate(2) losses {li} != call by call {lc}"
-        assert np.isfinite(li).all() and np.isfinite(Wi2).all() and np.isfinite(Hi2).all() and min(Wi2.min(), Hi2.min()) >= EPS
-        check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
-        check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
-        rule = make_rule(cmf, form, cfg, Xh, mask, Wh, Hh)
-        try:
-            lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
-            Wd, Hg = rule.download()
-            if cfg == dict(conv_kernel=3) and K % 32 == 0:
-                # The loss + store base (what update_feature_maps! ran: est is kept) and the loss-only base (reuse_est = 0) run on the
-                # same one-wave tiles with the same cut, and their terms are rounded alike (cmf_kernels.h at cmf_is_term): the same
-                # partials in the same order, so the same bits.  The factors are uploaded again so that the loss is computed anew.
-                rule.set_option("reuse_est", 0)
-                rule.upload(Wd, Hg)
-                l_only = rule.compute_loss()
-                assert l_only == lh1, f"{form} {cfg}: the loss-only base gives {l_only!r}, loss + store gave {lh1!r}"
-            ch = counters(rule)
-        finally:
-            rule.close()
-        c = {p: c[p] + ch[p] for p in c}
-        record(form, c)
-        check_loss(form, lh1, lossH_ref, "update_feature_maps!", cfg, c)
-        check_factor(form, Wg, W_ref, "knl", "W half: W", cfg, c)
-        check_factor(form, Hg, H_ref, "kt", "H half: H", cfg, c)
-        check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+        Wg, Hg, c = run_divergence_config(cmf, form, cfg, K, refs)
         if base is None:
             base = (cfg, Wg, Hg)
         elif set(cfg) <= CONV_ONLY and set(base[0]) <= CONV_ONLY:
@@ -181,13 +192,13 @@ assert all(s[:4] in [r[:4] for r in SHAPES] for s in SPOT_SHAPES)
 IS_BACKGROUND = 2.0 ** -44  # |(r - 1) - log r| of a background entry in fp32: r = est * fl(1 / est) is within an ulp of 1, the term within a few ulp(2^-23) of 0
 
 
-def spotlight_tiles(N, T, K):
+def spotlight_tiles(N, T, K, n_cu=ep.N_CU):
     """(t block, n block) of the six chosen 64 x 64 tiles of the loss conv's one-wave grid (tile index = n block fastest): the first, the
     last whole tile before the cut, the first and last cut tile, one of the last (partial) tile row, one of the last, partly padded
-    n block.  Grids without a cut take the middle and the last tile instead."""
+    n block.  Grids without a cut take the middle and the last tile instead.  n_cu: the CU count the grid is planned for."""
     gx, rows = ep.rup(N, 128) // 64, (T + 63) // 64
     live_gx = (N + 63) // 64  # (n blocks that are all padding hold no entry)
-    n_full, cut = ep.conv3_cut(N, T)[:2] if K % 32 == 0 else ep.conv_small_form(N, T)
+    n_full, cut = ep.conv3_cut(N, T, n_cu=n_cu)[:2] if K % 32 == 0 else ep.conv_small_form(N, T, n_cu=n_cu)
     tiles = gx * rows
     ids = [0, max(n_full - 1, 0), n_full % tiles, tiles - 1] if 0 < cut < tiles else [0, tiles // 3, tiles // 2, tiles - 1]
     out = [(i // gx, min(i % gx, live_gx - 1)) for i in ids]
@@ -195,7 +206,7 @@ def spotlight_tiles(N, T, K):
     return list(dict.fromkeys(out))
 
 
-def spotlight_problem(form, N, T, K, L):
+def spotlight_problem(form, N, T, K, L, n_cu=ep.N_CU):
     """(W, H, X, mask, spots, held): the W family's factors with H's first column raised to L (est is then 20 ... 78 at L = 20 from the
     first column on, not 1 ...), data = est except at the spotlights: 64 per chosen tile, one per row and per column and four in every
     16 x 16 block, each 2 est or est / 2.  held: the
@@ -208,7 +219,7 @@ def spotlight_problem(form, N, T, K, L):
     assert est.min() >= 1 and est.max() < ep.EXACT and np.all(est == np.round(est))
     i = np.arange(64)
     nn, tt = [], []
-    for tb, nb in spotlight_tiles(N, T, K):
+    for tb, nb in spotlight_tiles(N, T, K, n_cu):
         n, t = nb * 64 + i, tb * 64 + (i % 4) * 16 + i // 4
         ok = (n < N) & (t < T)
         nn.append(n[ok]), tt.append(t[ok])
@@ -238,10 +249,9 @@ def spot_terms(form, x, e):
     return br.terms_direct(x, e, beta)
 
 
-@pytest.mark.parametrize("form", list(FORMS))
-@pytest.mark.parametrize("N,T,K,L,cfg", SPOT_SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in SPOT_SHAPES])
-def test_spotlight_loss(cmf, N, T, K, L, cfg, form):
-    W, H, X, mask, (nn, tt, terms, half), held = spotlight_problem(form, N, T, K, L)
+def run_spotlight(cmf, N, T, K, L, cfg, form, n_cu=ep.N_CU, record=record):
+    """The spotlight loss of a form on a shape whose handle is planned for n_cu CUs: everything test_spotlight_loss asserts."""
+    W, H, X, mask, (nn, tt, terms, half), held = spotlight_problem(form, N, T, K, L, n_cu)
     masked = FORMS[form][2]
     counted = ~held if masked else np.ones(len(nn), bool)
     total = terms[counted].sum()
@@ -266,6 +276,12 @@ def test_spotlight_loss(cmf, N, T, K, L, cfg, form):
     record(form, c)
     print(f"spotlight {form} {(N, T, K, L)} {cfg}: {len(nn)} spotlights, smallest {terms[counted].min() / total:.2e} of the sum, loss rel {abs(got - want) / want:.2e}; {reached(c)}")
     assert abs(got - want) <= SPOT_BAR * want, f"{form} {cfg}: compute_loss {got!r}, want {want!r}; launches {reached(c)}"
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("N,T,K,L,cfg", SPOT_SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in SPOT_SHAPES])
+def test_spotlight_loss(cmf, N, T, K, L, cfg, form):
+    run_spotlight(cmf, N, T, K, L, cfg, form)
     _done.add(("spot", (N, T, K, L), form))
 
 

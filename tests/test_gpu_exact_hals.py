@@ -58,9 +58,10 @@ def reached(c):
     return sorted(p for p, v in c.items() if v)
 
 
-def record(c):
+def record(c, seen=None):
+    seen = _seen if seen is None else seen
     for p, v in c.items():
-        _seen[p] = _seen.get(p, 0) + v
+        seen[p] = seen.get(p, 0) + v
 
 
 def make_rule(cmf, cfg, X, W, H):
@@ -125,19 +126,19 @@ def run_half(rule, family, W, H, reg):
     return rule.download()[1], loss
 
 
-@pytest.mark.parametrize("N,T,K,L,configs,why", HALS_SHAPES, ids=IDS)
-def test_exact_hals_paths(cmf, N, T, K, L, configs, why):
-    shape = (N, T, K, L)
-    _attempted.add(shape)
-    t0 = time.perf_counter()
-    refs = references(shape)
-    t_ref = time.perf_counter() - t0
+def run_hals_row(cmf, shape, configs, refs, n_cu=ep.N_CU, seen=None, worst=None, worst_loss=None):
+    """Every sweep configuration of a row under hals_gram = 2, 0 and 1 against the references refs (references(shape)): the list of
+    element-wise, zero-pattern and loss failures; the launch names, the reruns and the bit-identities are asserted on the spot.
+    n_cu: the CU count the handles are planned for (the plan mirror's);
+    seen, worst, worst_loss: where the counters and the worst errors are kept (default: this file's)."""
+    N, T, K, L = shape
+    seen, worst, worst_loss = _seen if seen is None else seen, _worst if worst is None else worst, _worst_loss if worst_loss is None else worst_loss
     failures = []
     for cfg in configs:
         base, base_loss = {}, {}
         for gram in GRAMS:
             opts = dict(cfg, hals_gram=gram)
-            plan = ep.hals_plan(N, T, K, L, opts)
+            plan = ep.hals_plan(N, T, K, L, opts, n_cu=n_cu)
             want_w, want_h = expected_launches(plan, gram, K, 3 if opts.get("hals_lag") == 3 else 2)
             for family, names, bar, want in (("W", "knl", BAR_W, want_w), ("H", "kt", BAR_H, want_h)):
                 W, H, X, halves = refs[family]
@@ -150,20 +151,20 @@ def test_exact_hals_paths(cmf, N, T, K, L, configs, why):
                         c = counters(rule)
                         what = f"{family} half {shape} {opts} reg {reg}"
                         if r == 0:
-                            record(c)  # (the names do not depend on the regularisers: counted before anything can fail)
+                            record(c, seen)  # (the names do not depend on the regularisers: counted before anything can fail)
                         assert set(reached(c)) == want, (f"{what}: the plan mirror expects exactly {sorted(want)}; missing {sorted(want - set(reached(c)))}, "
                                                          f"not expected {sorted(set(reached(c)) - want)}")
                         assert rule.counter("hals_pipeline_reruns") == 0, f"{what}: a wait of the persistent pipeline ran out and the sweep was redone on the stage pipeline"
                         a = halves[r]
                         u, msg = ep.check_hals(got, a, bar, names, reached(c))
                         key = (family, pipe)
-                        _worst[key] = max(_worst.get(key, 0.0), u if np.isfinite(u) else 1e30)
+                        worst[key] = max(worst.get(key, 0.0), u if np.isfinite(u) else 1e30)
                         print(f"{what}: worst {u:.2f} units (bar {bar:g})" + (f", loss {loss!r} want {a['loss']!r}" if family == "H" else ""))
                         if msg:
                             failures.append(f"{what}: {msg}")
                         if family == "H":
                             rel = abs(loss - a["loss"]) / a["loss"]
-                            _worst_loss[0] = max(_worst_loss[0], rel)
+                            worst_loss[0] = max(worst_loss[0], rel)
                             if not rel <= BAR_LOSS:
                                 failures.append(f"{what}: loss {loss!r}, want {a['loss']!r}: {rel:.2e} relative (bar {BAR_LOSS:.2e}); launches {reached(c)}")
                         same_bits(again, got, names, f"{what}: the second run against the first", reached(c))
@@ -178,6 +179,17 @@ def test_exact_hals_paths(cmf, N, T, K, L, configs, why):
                             assert loss == loss0, f"{what}: loss {loss!r}, under hals_gram = {g0} on the same pipeline {loss0!r}"
                 finally:
                     rule.close()
+    return failures
+
+
+@pytest.mark.parametrize("N,T,K,L,configs,why", HALS_SHAPES, ids=IDS)
+def test_exact_hals_paths(cmf, N, T, K, L, configs, why):
+    shape = (N, T, K, L)
+    _attempted.add(shape)
+    t0 = time.perf_counter()
+    refs = references(shape)
+    t_ref = time.perf_counter() - t0
+    failures = run_hals_row(cmf, shape, configs, refs)
     assert not failures, "\n".join(failures)
     _done.add(shape)
     print(f"{shape} {why}: reference {t_ref:.2f} s, total {time.perf_counter() - t0:.2f} s")

@@ -112,46 +112,61 @@ def flat(loss, sums):
     return [loss] + [v for pair in sums for v in pair]
 
 
+def references(shape):
+    """(mask, X, the W family's (W, H) and reference(), the H family's) of a row, once per shape."""
+    N, T, K, L = shape
+    mask = ep.mu_mask(N, T)
+    Ww, Hw, X = make_problem(N, T, K, L, "W")
+    ref_w = reference("W", Ww, Hw, X, mask, shape)
+    Wh, Hh, _ = make_problem(N, T, K, L, "H")
+    ref_h = reference("H", Wh, Hh, X, mask, shape)
+    return mask, X, (Ww, Hw, ref_w), (Wh, Hh, ref_h)
+
+
+def run_masked_config(cmf, cfg, refs, record=record, worst=_worst):
+    """One configuration of a row against references(shape): (W after the W half, H after the H half, launch counters), everything
+    test_exact_masked_mu_paths asserts per configuration asserted."""
+    mask, X, (Ww, Hw, (W_ref, lw_ref, _, sums_w_ref, exact_w)), (Wh, Hh, (H_ref, lh_ref, lossH_ref, sums_h_ref, exact_h)) = refs
+    rule = masked_rule(cmf, cfg, X, Ww, Hw, mask)
+    try:
+        lw, sums_w, Wg, Wi, (li, Wi2, Hi2), (lc, Wc2, Hc2) = run_w_half(rule, Ww, Hw)
+        c = counters(rule)
+    finally:
+        rule.close()
+    assert li == lc, f"{cfg}: iterate(2) losses {li} != call by call {lc}"
+    check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
+    check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
+    rule = masked_rule(cmf, cfg, X, Wh, Hh, mask)
+    try:
+        lh = rule.compute_loss()
+        sums_h = [rule.masked_loss(complement=comp) for comp in (False, True)]
+        lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
+        _, Hg = rule.download()
+        ch = counters(rule)
+    finally:
+        rule.close()
+    c = {p: c[p] + ch[p] for p in c}
+    record(c)
+    check_losses(flat(lw, sums_w), flat(lw_ref, sums_w_ref), exact_w, "loss and held-out sums, W family", cfg, c)
+    check_losses(flat(lh, sums_h), flat(lh_ref, sums_h_ref), exact_h, "loss and held-out sums, H family", cfg, c)
+    np.testing.assert_allclose(lh1, lossH_ref, rtol=1e-5)  # (H is no longer integer: the bar of tests/test_exact_parity.py)
+    check_factor(Wg, W_ref, "knl", "masked W half: W", cfg, c)
+    check_factor(Hg, H_ref, "kt", "masked H half: H", cfg, c)
+    worst["W"] = max(worst["W"], float(ep.ulps(Wg, W_ref).max()))
+    worst["H"] = max(worst["H"], float(ep.ulps(Hg, H_ref).max()))
+    check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+    return Wg, Hg, c
+
+
 @pytest.mark.parametrize("N,T,K,L,configs,why", SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in SHAPES])
 def test_exact_masked_mu_paths(cmf, N, T, K, L, configs, why):
     shape = (N, T, K, L)
     t0 = time.perf_counter()
-    mask = ep.mu_mask(N, T)
-    Ww, Hw, X = make_problem(N, T, K, L, "W")
-    W_ref, lw_ref, _, sums_w_ref, exact_w = reference("W", Ww, Hw, X, mask, shape)
-    Wh, Hh, _ = make_problem(N, T, K, L, "H")
-    H_ref, lh_ref, lossH_ref, sums_h_ref, exact_h = reference("H", Wh, Hh, X, mask, shape)
+    refs = references(shape)
     t_ref = time.perf_counter() - t0
     base = None
     for cfg in ep.divergence_configs(configs, "masked"):
-        rule = masked_rule(cmf, cfg, X, Ww, Hw, mask)
-        try:
-            lw, sums_w, Wg, Wi, (li, Wi2, Hi2), (lc, Wc2, Hc2) = run_w_half(rule, Ww, Hw)
-            c = counters(rule)
-        finally:
-            rule.close()
-        assert li == lc, f"{cfg}: iterate(2) losses {li} != call by call {lc}"
-        check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
-        check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
-        rule = masked_rule(cmf, cfg, X, Wh, Hh, mask)
-        try:
-            lh = rule.compute_loss()
-            sums_h = [rule.masked_loss(complement=comp) for comp in (False, True)]
-            lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
-            _, Hg = rule.download()
-            ch = counters(rule)
-        finally:
-            rule.close()
-        c = {p: c[p] + ch[p] for p in c}
-        record(c)
-        check_losses(flat(lw, sums_w), flat(lw_ref, sums_w_ref), exact_w, "loss and held-out sums, W family", cfg, c)
-        check_losses(flat(lh, sums_h), flat(lh_ref, sums_h_ref), exact_h, "loss and held-out sums, H family", cfg, c)
-        np.testing.assert_allclose(lh1, lossH_ref, rtol=1e-5)  # (H is no longer integer: the bar of tests/test_exact_parity.py)
-        check_factor(Wg, W_ref, "knl", "masked W half: W", cfg, c)
-        check_factor(Hg, H_ref, "kt", "masked H half: H", cfg, c)
-        _worst["W"] = max(_worst["W"], float(ep.ulps(Wg, W_ref).max()))
-        _worst["H"] = max(_worst["H"], float(ep.ulps(Hg, H_ref).max()))
-        check_same(Wi, Wg, "knl", "W after iterate(1)", cfg, "update_motifs!", c)
+        Wg, Hg, c = run_masked_config(cmf, cfg, refs)
         if base is None:
             base = (cfg, Wg, Hg)
         else:

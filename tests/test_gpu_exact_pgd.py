@@ -127,55 +127,66 @@ def references(oracle, shape, family, check):
     return W, H, X, mask, oracle.compute_loss(X, W, H), refs
 
 
+def run_pgd_config(cmf, cfg, ref_w, ref_h, variants_w, variants_h, record=record, worst=_worst):
+    """One configuration of a row against references(..., "W") and references(..., "H"): {(family, variant): updated factor}, launch
+    counters; everything test_exact_pgd_paths asserts per configuration asserted."""
+    Ww, Hw, Xw, mask_w, loss_w_ref, refs_w = ref_w
+    Wh, Hh, Xh, mask_h, loss_h_ref, refs_h = ref_h
+    got = {}
+    rule = make_rule(cmf, cfg, Xw, Ww, Hw)
+    try:
+        lw = rule.compute_loss()
+        for v, var in variants_w.items():
+            fresh(cmf, rule, Ww, Hw)
+            var.w_half(rule)
+            got[("W", v)] = (rule.download()[0], rule.steps, None)
+        c = counters(rule)
+    finally:
+        rule.close()
+    rule = make_rule(cmf, cfg, Xh, Wh, Hh)
+    try:
+        lh = rule.compute_loss()
+        for v, var in variants_h.items():
+            fresh(cmf, rule, Wh, Hh)
+            loss = var.h_half(rule)  # (est is void: the transposing conv CONV_RESID_T / CONV_MASKED_RESID_T)
+            got[("H", v)] = (rule.download()[1], rule.steps, loss)
+        ch = counters(rule)
+    finally:
+        rule.close()
+    c = {p: c[p] + ch[p] for p in c}
+    record(c)
+    assert (lw, lh) == (loss_w_ref, loss_h_ref), f"loss {cfg}: {(lw, lh)} != {(loss_w_ref, loss_h_ref)}; launches {reached(c)}"
+    for (family, v), (x, steps, loss) in got.items():
+        ref, steps_ref, loss_ref = (refs_w if family == "W" else refs_h)[v]
+        names = "knl" if family == "W" else "kt"
+        what = f"{family} half, {v}"
+        worst[family] = max(worst[family], check_factor(x, ref, names, what, cfg, c))
+        assert steps == steps_ref, f"{what} {cfg}: steps {steps}, the oracle's {steps_ref}; launches {reached(c)}"
+        if family == "H":
+            np.testing.assert_allclose(loss, loss_ref, rtol=1e-5)  # (H is no longer integer: the bar of tests/test_exact_parity.py)
+    return {key: x for key, (x, _, _) in got.items()}, c
+
+
 @pytest.mark.parametrize("N,T,K,L,configs,why", SHAPES, ids=IDS)
 def test_exact_pgd_paths(cmf, oracle, N, T, K, L, configs, why):
     shape = (N, T, K, L)
     t0 = time.perf_counter()
-    Ww, Hw, Xw, mask_w, loss_w_ref, refs_w = references(oracle, shape, "W", N < 1000)
-    Wh, Hh, Xh, mask_h, loss_h_ref, refs_h = references(oracle, shape, "H", N < 1000)
-    variants_w = {v: Variant(cmf, v, mask_w) for v in refs_w}
-    variants_h = {v: Variant(cmf, v, mask_h) for v in refs_h}
+    ref_w = references(oracle, shape, "W", N < 1000)
+    ref_h = references(oracle, shape, "H", N < 1000)
+    variants_w = {v: Variant(cmf, v, ref_w[3]) for v in ref_w[5]}
+    variants_h = {v: Variant(cmf, v, ref_h[3]) for v in ref_h[5]}
     t_ref = time.perf_counter() - t0
     base = {}
     for cfg in pgd_configs(configs):
         if T // len(cfg.get("devices", [0])) < 2 * L:
             continue  # (shards shorter than two lag windows: not a shape a group takes)
-        got = {}
-        rule = make_rule(cmf, cfg, Xw, Ww, Hw)
-        try:
-            lw = rule.compute_loss()
-            for v, var in variants_w.items():
-                fresh(cmf, rule, Ww, Hw)
-                var.w_half(rule)
-                got[("W", v)] = (rule.download()[0], rule.steps, None)
-            c = counters(rule)
-        finally:
-            rule.close()
-        rule = make_rule(cmf, cfg, Xh, Wh, Hh)
-        try:
-            lh = rule.compute_loss()
-            for v, var in variants_h.items():
-                fresh(cmf, rule, Wh, Hh)
-                loss = var.h_half(rule)  # (est is void: the transposing conv CONV_RESID_T / CONV_MASKED_RESID_T)
-                got[("H", v)] = (rule.download()[1], rule.steps, loss)
-            ch = counters(rule)
-        finally:
-            rule.close()
-        c = {p: c[p] + ch[p] for p in c}
-        record(c)
-        assert (lw, lh) == (loss_w_ref, loss_h_ref), f"loss {cfg}: {(lw, lh)} != {(loss_w_ref, loss_h_ref)}; launches {reached(c)}"
-        for (family, v), (x, steps, loss) in got.items():
-            ref, steps_ref, loss_ref = (refs_w if family == "W" else refs_h)[v]
+        got, c = run_pgd_config(cmf, cfg, ref_w, ref_h, variants_w, variants_h)
+        for (family, v), x in got.items():
             names = "knl" if family == "W" else "kt"
-            what = f"{family} half, {v}"
-            _worst[family] = max(_worst[family], check_factor(x, ref, names, what, cfg, c))
-            assert steps == steps_ref, f"{what} {cfg}: steps {steps}, the oracle's {steps_ref}; launches {reached(c)}"
-            if family == "H":
-                np.testing.assert_allclose(loss, loss_ref, rtol=1e-5)  # (H is no longer integer: the bar of tests/test_exact_parity.py)
             if (family, v) not in base:
                 base[(family, v)] = (cfg, x)
             else:
-                check_same(x, base[(family, v)][1], names, what, cfg, base[(family, v)][0], c)
+                check_same(x, base[(family, v)][1], names, f"{family} half, {v}", cfg, base[(family, v)][0], c)
     _done.add(shape)
     print(f"{shape} {why}: oracle {t_ref:.2f} s, total {time.perf_counter() - t0:.2f} s; worst so far W {_worst['W']:.2f} ulp, H {_worst['H']:.2f} ulp")
 
