@@ -221,6 +221,7 @@ static void destroy_impl(cmf_handle_s *h)
         if (mine(p)) (void)hipFree(p);
     if (h->kl_denH) (void)hipFree(h->kl_denH);
     if (h->kl_sums) (void)hipFree(h->kl_sums);
+    xo_free(h);
     if (h->est2) (void)hipFree(h->est2);
     if (h->est2T) (void)hipFree(h->est2T);
     for (int v = 0; v < 3; ++v)
@@ -430,13 +431,13 @@ int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, i
 // ------------------------------------------------------------------------------------------
 
 int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, int nsrc, float *slabs, int nchunks, int chunk_len,
-                         int main_rows)
+                         int main_rows, const float *left)
 {
     ProfScope prof_(h, hxt_prof_class(h, X0, nsrc));
     const CmfDims &d = h->d;
     h->spec_gen = -1; // (the slabs of a speculated contraction are being overwritten)
     HxtParams p;
-    p.H = h->H; p.X0 = X0; p.X1 = X1; p.slabs = slabs;
+    p.H = left ? left : h->H; p.X0 = X0; p.X1 = X1; p.slabs = slabs;
     p.Np = NpX; p.K32 = d.K32; p.KB = d.KB; p.PADL = d.PADL; p.L = d.L; p.Tl = main_rows >= 0 ? main_rows : d.Tl; p.chunk_len = chunk_len;
     p.G = h->hxt_groups; p.nsrc = nsrc;
     p.CG = hxt_cg(nchunks);
@@ -508,15 +509,17 @@ int launch_slab_sum(cmf_handle_s *h, float *out, const float *in, int nslabs, si
 
 // The C2 contraction of one (nsrc = 1: X0) or two sources with H_shift, complete: kernel, slab sum, and the rows the kernel
 // leaves to the slab sum.   out: [nsrc][L][K32][Np]
-int hxt_contract(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only)
+int hxt_contract(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only, const float *left,
+                 const float *leftT)
 {
     const CmfDims &d = h->d;
     h->spec_gen = -1; // (the slabs / sums of a speculated contraction are being overwritten)
-    if (h->small_k) return hxt_contract_small(h, X0, X1, nsrc, out, take_carry, slabs_only); // few components (cmf_small.hip)
+    if ((left == nullptr) != (leftT == nullptr)) return fail(CMF_ERR_STATE, "internal: a left operand of the C2 contraction needs both layouts");
+    if (h->small_k) return hxt_contract_small(h, X0, X1, nsrc, out, take_carry, slabs_only, leftT); // few components (cmf_small.hip)
     const int nch = nsrc == 2 ? h->hxt_nchunks : h->hxt_nchunks1, clen = nsrc == 2 ? h->hxt_chunk_len : h->hxt_chunk_len1;
     const int main_rows = nsrc == 2 ? h->hxt_main : h->hxt_main1;
-    CMFTRY(launch_hxt_on(h, X0, X1, d.Np, nsrc, h->wslabs, nch, clen, main_rows));
-    const CmfHxtTail tail{h->H, X0, X1, d.Tl - main_rows, d.PADL + main_rows, d.L, d.K32, d.Np};
+    CMFTRY(launch_hxt_on(h, X0, X1, d.Np, nsrc, h->wslabs, nch, clen, main_rows, left));
+    const CmfHxtTail tail{left ? left : h->H, X0, X1, d.Tl - main_rows, d.PADL + main_rows, d.L, d.K32, d.Np};
     return launch_slab_sum(h, out, h->wslabs, hxt_nslabs(nch), (size_t)nsrc * d.L * d.K32 * d.Np, take_carry, tail);
 }
 
@@ -584,7 +587,7 @@ static bool mu_est_current(const cmf_handle_s *h) { return h->reuse_est && h->es
 // update_feature_maps! before): est is current and nothing has touched H, W, est or the slabs since.
 static bool w_speculated(cmf_handle_s *h)
 {
-    const bool hit = mu_form(h).square_fusions && h->spec_gen >= 0 && h->spec_gen == h->est_gen && mu_est_current(h) && !h->carry.partial;
+    const bool hit = mu_fusions(h) && h->spec_gen >= 0 && h->spec_gen == h->est_gen && mu_est_current(h) && !h->carry.partial;
     h->spec_gen = -1;
     if (hit) h->spec_hits += 1;
     return hit;
@@ -656,7 +659,7 @@ static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
 {
     const CmfDims &d = h->d;
     const MuForm &f = mu_form(h);
-    if (!(h->small_k && f.square_fusions)) {
+    if (!(h->small_k && mu_fusions(h))) {
         CMFTRY(w_partial_impl(h));
         if (f.kl_den()) { // KL: denomW[l][k] broadcast over n from the row sums of H, behind numW in h->numden
             hipLaunchKernelGGL(kl_hsum_kernel, dim3(d.K, KL_HCHUNKS), dim3(256), 0, h->stream, h->Ht, d.TP, d.PADL, d.Tl, h->kl_sums);
@@ -665,7 +668,11 @@ static int w_phase_impl(cmf_handle_s *h, double l1W, double l2W)
                                d.K32, d.Np);
             KCHK("kl_den_w_kernel");
         }
-        return w_apply_impl(h, l1W, l2W);
+        if (!xo_active(h)) return w_apply_impl(h, l1W, l2W);
+        CMFTRY(xo_fold_w(h)); // denomW + (lambda xW + lambda_W oW), before the regularisers (cmf_xortho.hip)
+        CMFTRY(w_apply_impl(h, l1W, l2W));
+        xo_after_w(h);
+        return CMF_OK;
     }
     CMFTRY(mu_contract_w(h, true));
     CmfLossCarry carry{};
@@ -727,7 +734,7 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
     }
     const MuForm &f = mu_form(h);
     CMFTRY(mu_conv(h, CONV_BASE_STORE_T, h->estT, d.Tl + h->halo_r, h->conv_gy_ext)); // mult.jl:44 (est with the new W)
-    if (f.square_fusions && sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
+    if (mu_fusions(h) && sk_can_fuse_h(h)) { // few components: mult.jl:47-48 and :51-52 in ONE launch (whoever completes a block's slabs updates the block)
         CMFTRY(launch_transconv_small(h, 2, mu_buf(h, f.c3_first), true, (float)l1H, (float)(2.0 * l2H)));
         ++h->sk_fused_h;
         set_est(h, EST_NONE);
@@ -742,6 +749,11 @@ int h_update_impl(cmf_handle_s *h, double l1H, double l2H, bool front)
         KCHK("kl_den_h_kernel");
     }
     const int S = f.c3_nsrc == 2 ? h->tc_S : h->tc_S1;
+    if (xo_active(h)) { // numH as a finished table, denomH + (lambda xH + lambda_H oH) as another (cmf_xortho.hip)
+        const float *num = nullptr, *den = nullptr;
+        CMFTRY(xo_h_tables(h, S, stride, f.h_num, f.h_den, &num, &den));
+        return launch_h_update(h, mu_step_kind(h, f), num, (size_t)0, 1, den, (size_t)0, 1, d.Tl, d.PADL, l1H, l2H);
+    }
     if (f.kl_den()) return launch_h_update(h, mu_step_kind(h, f), h->hslabs + f.h_num * TK, stride, S, h->kl_denH, (size_t)0, 1, d.Tl, d.PADL, l1H, l2H);
     return launch_h_update(h, mu_step_kind(h, f), h->hslabs + f.h_num * TK, stride, S, h->hslabs + f.h_den * TK, stride, S, d.Tl, d.PADL, l1H, l2H);
 }
@@ -763,7 +775,7 @@ int launch_loss_conv(cmf_handle_s *h)
 // (the call before this one was update_motifs!); a caller that stops pays one contraction nobody reads.
 static int w_speculate(cmf_handle_s *h)
 {
-    if (!mu_est_current(h) || h->gram || h->group || h->carry.partial || !mu_form(h).square_fusions) return CMF_OK;
+    if (!mu_est_current(h) || h->gram || h->group || h->carry.partial || !mu_fusions(h)) return CMF_OK;
     CMFTRY(mu_contract_c2(h, h->small_k));
     h->spec_gen = h->est_gen;
     return CMF_OK;
@@ -1272,6 +1284,7 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
     if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
     if (std::strcmp(name, "pow_update_launches") == 0) { *value = h->pow_launches; return CMF_OK; }                          // launches of w_update_pow_kernel / h_update_pow_kernel (the beta form outside 1 < beta <= 2)
+    if (std::strcmp(name, "xortho_launches") == 0) { *value = h->xo_launches; return CMF_OK; }                               // launches of the kernels of cmf_xortho.h (0 while the weights of cmf_mu_set_xortho are 0 and no cost / terms entry was called)
     if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
     if (sep_counter(h, name, value)) return CMF_OK;                                                      // pivoting rounds of the last NNLS step of the separable fit
     if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
@@ -1450,6 +1463,8 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
                                                                  "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
         if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
                                                                   "which is not a product of Gram matrices): clear the mask of cmf_mu_set_mask first");
+        if (value && xo_active(h)) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms do not take the cross-orthogonality penalties of cmf_mu_set_xortho (their terms enter the "
+                                                                    "denominators the Gram form rewrites): set the weights to 0 first");
         h->gram = value;
         set_est(h, EST_NONE);
         return CMF_OK;
@@ -1934,6 +1949,7 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
     if (h->mu_div == CMF_DIV_KL && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
     if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
                                                   "which is not a product of Gram matrices; set gram = 0 first");
+    if (xo_active(h)) return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho have no masked form: set the weights to 0 first");
     const CmfDims &d = h->d;
     const size_t NT = (size_t)d.N * d.Tl;
     size_t ones = 0;
@@ -1990,6 +2006,8 @@ int cmf_mu_set_divergence(cmf_handle h, int kind)
         return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
     HIPCHK(hipSetDevice(h->device));
     if (kind == h->mu_div) return CMF_OK;
+    if (kind != CMF_DIV_SQUARE && xo_active(h))
+        return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho are terms of the squared-error rule and have no divergence form: set the weights to 0 first");
     if (h->wb && h->wb->armed) wb_disarm(h);
     drop_carry(h);
     h->spec_gen = -1;
@@ -2045,6 +2063,8 @@ int cmf_mu_set_beta_divergence(cmf_handle h, double beta)
     if (h->group || h->root_only || h->sharded)
         return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
     HIPCHK(hipSetDevice(h->device));
+    if (xo_active(h))
+        return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho are terms of the squared-error rule and have no divergence form: set the weights to 0 first");
     if (h->mu_div == CMF_DIV_BETA && beta == h->mu_beta) return CMF_OK;
     if (h->wb && h->wb->armed) wb_disarm(h);
     drop_carry(h);

@@ -376,7 +376,21 @@ struct cmf_handle_s {
     struct SepState *sep = nullptr;       // the separable fit's fp64 state (cmf_sep_prepare; cmf_sep.hip)
     int anls_backup_only = 0;             // cmf_set_option "anls_backup_only": every exchange of the ANLS solver is a backup-rule exchange
     int nnls_large = 0;                   // cmf_set_option "nnls_large": 129 .. 1024 unknowns run in nnls_large_kernel (cmf_nnls_large.h) instead of being refused
+    // seqNMF's cross-orthogonality penalties on the squared-error MU rule (cmf_mu_set_xortho; cmf_xortho.hip): the weights lambda, lambda_H, lambda_W
+    // (all 0: today's path, launch for launch), the tables of the penalty terms (allocated with the first non-zero weight or the first
+    // cmf_mu_xortho_cost / cmf_mu_xortho_terms) and the launches of the kernels of cmf_xortho.h (cmf_get_counter "xortho_launches")
+    double xo_lam[3] = {0.0, 0.0, 0.0};
+    struct XoState *xo = nullptr;
+    int64_t xo_launches = 0;
 };
+static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
+// cmf_xortho.hip: frees the tables (destroy_impl); the W side -- lambda xW + lambda_W oW folded into denomW behind numW in h->numden,
+// between the C2 contraction and w_apply_impl --; W has been updated and H has not (G stays current); the H side -- numH summed into a
+// finished table and the finished denominator table denomH + (lambda xH + lambda_H G), both in the single-slab form of launch_h_update
+void xo_free(cmf_handle_s *h);
+int xo_fold_w(cmf_handle_s *h);
+void xo_after_w(cmf_handle_s *h);
+int xo_h_tables(cmf_handle_s *h, int nslabs, size_t stride, int num_pos, int den_pos, const float **num, const float **den);
 
 // cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)
 void admm_free(cmf_handle_s *h);
@@ -600,6 +614,9 @@ static inline const MuForm &mu_form(const cmf_handle_s *h)
 {
     return kMuForms[h->mu_div == CMF_DIV_BETA ? (h->mu_mask ? MU_BETA_MASKED : MU_BETA) : h->mu_div == CMF_DIV_IS ? (h->mu_mask ? MU_IS_MASKED : MU_IS) : h->mu_div ? (h->mu_mask ? MU_KL_MASKED : MU_KL) : (h->mu_mask ? MU_SQUARE_MASKED : MU_SQUARE)];
 }
+// the few-component fusions and the speculated C2 of the active form; never under the penalties of cmf_mu_set_xortho, whose terms enter
+// the denominators between the contractions and the element-wise updates
+static inline bool mu_fusions(const cmf_handle_s *h) { return mu_form(h).square_fusions && !xo_active(h); }
 static inline float *mu_buf(const cmf_handle_s *h, MuBuf b) { return b ? h->*b : nullptr; }
 // What the MU entries read for data / "est is current".  reuse_est, the speculated C2 contraction and the deferred loss carry all
 // compare against mu_est_kind.
@@ -641,12 +658,16 @@ int upload_cols(cmf_handle_s *h, const double *src, int64_t tc, int64_t ncols, b
 int create_impl(cmf_handle *out, int device, int64_t N, int64_t Tl, int64_t K, int64_t L,
                        const double *data, int64_t t_offset, int64_t T_global, bool sharded, long long n_cu_asked = kNoCuHook);
 int launch_hxt_on(cmf_handle_s *h, const float *X0, const float *X1, int NpX, int nsrc, float *slabs, int nchunks, int chunk_len,
-                         int main_rows = -1);
+                         int main_rows = -1, const float *left = nullptr);
 int launch_transconv(cmf_handle_s *h, int nsrc, const float *xt0 = nullptr, bool front_block = false);
 int launch_slab_sum(cmf_handle_s *h, float *out, const float *in, int nslabs, size_t stride, bool take_carry = false,
                            CmfHxtTail tail = CmfHxtTail{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0});
-int hxt_contract(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry = false, bool slabs_only = false);
-int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only); // cmf_small.hip
+// left / leftT (NULL: H / Ht of the handle): the left operand of the contraction in the layouts of H and Ht -- an H-shaped table whose padding
+// rows and columns k >= K are exact zeros (the penalty contraction of cmf_mu_set_xortho puts G = off(S(H)) there)
+int hxt_contract(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry = false, bool slabs_only = false,
+                 const float *left = nullptr, const float *leftT = nullptr);
+int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only,
+                       const float *leftT = nullptr); // cmf_small.hip
 bool sk_can_fuse_h(const cmf_handle_s *h); // cmf_small.hip
 int launch_transconv_small(cmf_handle_s *h, int nsrc, const float *xt0, bool update_h = false, float l1 = 0.f, float two_l2 = 0.f);                                                          // cmf_small.hip
 int read_scalar(cmf_handle_s *h, int slot, double *v);

@@ -4,12 +4,12 @@
 
 // The C2 contraction for few components: the rows j = l*K + k on the MFMA axis (hxt_small_kernel), compact slabs, their sum expanded to
 // [L][K32][Np] (hxt_contract, cmf_api.hip, sends K <= 16 here)
-int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only)
+int hxt_contract_small(cmf_handle_s *h, const float *X0, const float *X1, int nsrc, float *out, bool take_carry, bool slabs_only, const float *leftT)
 {
     const CmfDims &d = h->d;
     ProfScope prof_(h, hxt_prof_class(h, X0, nsrc));
     SkHxtParams p;
-    p.Ht = h->Ht; p.X0 = X0; p.X1 = X1; p.slabs = h->sk_slabs;
+    p.Ht = leftT ? leftT : h->Ht; p.X0 = X0; p.X1 = X1; p.slabs = h->sk_slabs;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.L = d.L; p.J = h->sk_J; p.JP = h->sk_JP; p.MG = h->sk_MG; p.Tl = d.Tl;
     p.chunk_len = h->sk_chunk_len; p.nsrc = nsrc; p.RV = h->sk_RV;
     size_t lds = std::max<size_t>((size_t)8 * (d.K + 1) * SK_HS_STRIDE, 4 * 16 * 64) * sizeof(float); // (two strips per wave | the chunk reduction)

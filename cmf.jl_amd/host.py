@@ -167,6 +167,20 @@ def _check_beta(kind_code, beta):
     return b
 
 
+_XORTHO_KW = ("lambda_xortho", "lambda_ortho_H", "lambda_ortho_W")
+
+
+def _check_xortho(*weights):
+    """The three penalty weights as cmf_mu_set_xortho accepts them: finite and >= 0."""
+    out = []
+    for name, w in zip(_XORTHO_KW, weights):
+        w = float(w)
+        if not math.isfinite(w) or w < 0.0:
+            raise ValueError(f"{name} must be finite and >= 0, got {w!r}")
+        out.append(w)
+    return tuple(out)
+
+
 class AbstractCFUpdate:
     """An update rule that updates both W and H (src/algs/alternating.jl:1-8).
 
@@ -371,6 +385,32 @@ class MultUpdate(AbstractCFUpdate):
         if code == _DIV_IS:
             self.set_option("is_div", 1)
         check(self._lib.cmf_mu_set_divergence(self._h, code))
+
+    # -- seqNMF's cross-orthogonality penalties (cmf_mu_set_xortho) ---------------------------
+    def set_xortho(self, lam, ortho_H=0.0, ortho_W=0.0):
+        """The weights of seqNMF's penalties on the squared-error rule: ``lam`` of the cross-orthogonality term
+        sum_{i != j} (transconv(W, data) S H')_ij, ``ortho_H`` of sum_{i != j} (H S H')_ij / 2 and ``ortho_W`` of
+        sum_{i != j} (Wflat' Wflat)_ij / 2 (S: the box smoothing of width 2L - 1 along time).  Each rule call then adds the term's
+        gradient to its denominator (include/cmf_hip.h has the formulas); the loss stays norm(est - data) / norm(data).  All zeros
+        restore the plain rule launch for launch.  One GPU, no mask, no divergence, no Gram form."""
+        w = _check_xortho(lam, ortho_H, ortho_W)
+        check(self._lib.cmf_mu_set_xortho(self._h, *w))
+
+    def xortho_cost(self):
+        """(xortho, ortho_H, ortho_W): the three penalty sums of the resident factors without their weights and without the 1/2
+        (cmf_mu_xortho_cost; fp64 sums)."""
+        c = [ctypes.c_double() for _ in range(3)]
+        check(self._lib.cmf_mu_xortho_cost(self._h, *[ctypes.byref(v) for v in c]))
+        return tuple(v.value for v in c)
+
+    def xortho_terms(self):
+        """(xW, xH, oH, oW): the four unweighted denominator terms for the resident factors, in the shapes of W, H, H and W
+        (cmf_mu_xortho_terms)."""
+        K, N, L, T = self.K, self.N, self.L, self.T
+        xW, oW = np.zeros((K, N, L), order="F"), np.zeros((K, N, L), order="F")
+        xH, oH = np.zeros((K, T), order="F"), np.zeros((K, T), order="F")
+        check(self._lib.cmf_mu_xortho_terms(self._h, ptr(xW), ptr(xH), ptr(oH), ptr(oW)))
+        return xW, xH, oH, oW
 
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
@@ -1199,6 +1239,7 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "thresh", "refit_H", "refit_W", "refit_H_itr", "spectral", "pre",  # alg=:sep (separable.jl:14-18)
              "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
              "mask",  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
+             "lambda_xortho", "lambda_ortho_H", "lambda_ortho_W",  # alg=:mult: seqNMF's penalties (MultUpdate.set_xortho)
              "divergence", "beta"}  # alg=:mult: ":square" (default), ":kl", ":itakura_saito" or ":beta" with beta= (MultUpdate.set_divergence)
 
 
@@ -1284,6 +1325,14 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
                                       "unless the library option is set: options={'kl_mask': 1}")
         if devices is not None:
             raise NotImplementedError("divergence=':kl' is not available with devices=[...]: the KL form of the MU rule runs on one GPU")
+    xortho = _check_xortho(*[kw.get(k, 0.0) for k in _XORTHO_KW])
+    if any(xortho):
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("lambda_xortho / lambda_ortho_H / lambda_ortho_W are implemented for alg=:mult; the HALS, PGD, ADMM, "
+                                      "ANLS and separable fits have no cross-orthogonality penalties")
+        if mask is not None or divergence or devices is not None or (options or {}).get("gram", 0):
+            raise NotImplementedError("the cross-orthogonality penalties run on the squared-error MU rule on one GPU: not with mask=, "
+                                      "divergence=, devices=[...] or the Gram form")
     if rule_type is Separable:
         # The separable fit has no iteration and HEAD has no mapping for it (model.jl:3-8 is commented out): the result holds
         # the loss of the fit and the wall time it took; max_itr, max_time, W_init and H_init do not apply.
@@ -1320,8 +1369,10 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
             rule.set_mask(mask)  # (before the loop: loss_hist[0] is the masked loss too)
         if divergence:
             rule.set_divergence(_DIV_NAMES[divergence], beta=beta)  # (before the loop: loss_hist[0] is the divergence too)
+        if any(xortho):
+            rule.set_xortho(*xortho)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
-        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence", "beta")}
+        loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence", "beta") + _XORTHO_KW}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
     finally:
         if hasattr(rule, "close"):
@@ -1361,6 +1412,33 @@ def evaluate_divergence(r, kind=":kl", device=None, beta=None):
         return rule.compute_loss()
     finally:
         rule.close()
+
+
+def evaluate_xortho(r, device=None):
+    """(xortho, ortho_H, ortho_W) of the fitted model ``r``: seqNMF's three penalty sums without their weights and without the 1/2
+    (MultUpdate.xortho_cost)."""
+    rule = MultUpdate(r.data, r.W, r.H, device=device)
+    try:
+        return rule.xortho_cost()
+    finally:
+        rule.close()
+
+
+def xortho_sweep(data, lambdas, L, K, **fit_kw):
+    """One ``fit_cnmf(data, L=L, K=K, alg=":mult", lambda_xortho=lam, **fit_kw)`` per ``lam`` in ``lambdas``, all from the same
+    initial factors (``seed=`` or ``W_init`` / ``H_init`` of ``fit_kw``; without either one seed is drawn for the whole sweep).
+    Returns ``{lam: {"loss": final loss, "xortho": cross-orthogonality cost, "res": CNMF_results}}``: the two curves whose
+    crossover seqNMF's procedure picks lambda from."""
+    if "alg" in fit_kw or "lambda_xortho" in fit_kw:
+        raise TypeError("xortho_sweep fits with alg=':mult' and its own lambda_xortho")
+    fit_kw = dict(fit_kw)
+    if "seed" not in fit_kw and not ("W_init" in fit_kw and "H_init" in fit_kw):
+        fit_kw["seed"] = int.from_bytes(os.urandom(4), "little")
+    out = {}
+    for lam in lambdas:
+        r = fit_cnmf(data, L=L, K=K, alg=":mult", lambda_xortho=lam, **fit_kw)
+        out[lam] = {"loss": float(r.loss_hist[-1]), "xortho": evaluate_xortho(r, device=fit_kw.get("device", None))[0], "res": r}
+    return out
 
 
 def evaluate_test(r, test, num_iter=30, device=None):
@@ -1561,7 +1639,7 @@ def parameter_sweep(data, L_vals=(7,), K_vals=(3,), alg_vals=(":mult",), max_itr
 _MODEL_KEYS = ("W", "H", "data", "loss_hist", "time_hist")
 
 
-_META_KEYS = ("l1_H", "l2_H", "l1_W", "l2_W", "alg")
+_META_KEYS = ("l1_H", "l2_H", "l1_W", "l2_W", "alg", "lambda_xortho", "lambda_ortho_H", "lambda_ortho_W")
 
 
 def _is_hdf5_path(path):

@@ -197,6 +197,32 @@ end
 # P = data .* e.^(beta - 2), the step raised to gamma(beta); 0.01 <= beta <= 4, at least 0.01 away from 1; data finite and non-negative.
 set_beta_divergence!(rule::HIPMultUpdate, beta::Real) = check(ccall((:cmf_mu_set_beta_divergence, LIBCMF), Cint, (Ptr{Cvoid}, Float64), rule.handle, Float64(beta)))
 
+# set_xortho!(rule; lambda_xortho=0, lambda_ortho_H=0, lambda_ortho_W=0): seqNMF's cross-orthogonality penalties on the squared-error rule
+# (cmf_mu_set_xortho): with S the box smoothing of width 2L-1 along t, off the sum over the OTHER components and G = off(S(H)),
+# mult.jl:37 gets lambda xW + lambda_W off(Wflat) added to denomW (xW: mult.jl:32 with G in H's place) and mult.jl:51 gets
+# lambda off(S(numH)) + lambda_H G added to denomH, before the regularisers.  The loss stays norm(est - data) / norm(data).  All zeros
+# restore the plain rule.  One GPU; no mask, no divergence, no Gram form.
+function set_xortho!(rule::HIPMultUpdate; lambda_xortho::Real=0, lambda_ortho_H::Real=0, lambda_ortho_W::Real=0)
+    check(ccall((:cmf_mu_set_xortho, LIBCMF), Cint, (Ptr{Cvoid}, Float64, Float64, Float64), rule.handle,
+                Float64(lambda_xortho), Float64(lambda_ortho_H), Float64(lambda_ortho_W)))
+    return rule
+end
+# xortho_cost(rule) -> (xortho, ortho_H, ortho_W): the three penalty sums of the resident factors without their weights and without
+# the 1/2, summed in fp64 (cmf_mu_xortho_cost)
+function xortho_cost(rule::HIPMultUpdate)
+    x, oh, ow = Ref{Float64}(0.0), Ref{Float64}(0.0), Ref{Float64}(0.0)
+    check(ccall((:cmf_mu_xortho_cost, LIBCMF), Cint, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}, Ref{Float64}), rule.handle, x, oh, ow))
+    return x[], oh[], ow[]
+end
+# xortho_terms(rule, K, N, L, T) -> (xW, xH, oH, oW): the four unweighted denominator terms for the resident factors, in the shapes
+# of W, H, H and W (cmf_mu_xortho_terms)
+function xortho_terms(rule::HIPMultUpdate, K::Integer, N::Integer, L::Integer, T::Integer)
+    xW, oW = zeros(Float64, K, N, L), zeros(Float64, K, N, L)
+    xH, oH = zeros(Float64, K, T), zeros(Float64, K, T)
+    check(ccall((:cmf_mu_xortho_terms, LIBCMF), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), rule.handle, xW, xH, oH, oW))
+    return xW, xH, oH, oW
+end
+
 # update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
 function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)
     select_mask!(rule, mask)

@@ -71,7 +71,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -527,6 +527,36 @@ int cmf_mu_set_divergence(cmf_handle h, int kind);
 #define CMF_BETA_WINDOW 0.01
 #define CMF_BETA_MAX 4.0
 int cmf_mu_set_beta_divergence(cmf_handle h, double beta);
+/* seqNMF's cross-orthogonality penalties (Mackevicius et al., eLife 2019) on the squared-error MU rule.  With
+ *   S(A)[k,t]   = sum of A[k,t'] over |t' - t| <= L-1, 0 <= t' < T     (seqNMF's conv2(A, ones(1, 2L-1), 'same'))
+ *   off(A)[k,:] = sum of A[k',:] over k' != k,    A = tensor_transconv(W, data) (the rule's numH),    G = off(S(H)),
+ *   Wflat[k,n]  = sum_l W[k,n,l]
+ * the objective is 1/2 |data - tensor_conv(W,H)|^2 + lambda sum_{i != j} (A S H')_ij + lambda_H / 2 sum_{i != j} (H S H')_ij
+ * + lambda_W / 2 sum_{i != j} (Wflat' Wflat)_ij, and the MU entries run mult.jl:23-58 with each denominator enlarged BEFORE the
+ * regularisers:
+ *   update_motifs!:        xW[k,n,l] = sum_t G[k,t] data[n,t+l]  (the contraction of mult.jl:32 with G in H's place);  oW[k,n,l] = off(Wflat)[k,n];
+ *                          denomW + (lambda xW + lambda_W oW) in place of denomW in mult.jl:37
+ *   update_feature_maps!:  xH = off(S(numH)) (numH of the same call: from the new W);  oH = G (from the H being updated);
+ *                          denomH + (lambda xH + lambda_H oH) in place of denomH in mult.jl:51
+ * xW and xH are the exact gradients of the lambda term, oH and oW seqNMF's terms (the gradients of the halved sums).  Everything else
+ * is the plain rule: the eps clamp, est recomputed with the new W, the loss norm(est - data) / norm(data) -- the penalties are
+ * reported by cmf_mu_xortho_cost, not added to it.  The update is not guaranteed monotone (seqNMF's is not either).
+ * All weights 0 (the default): the plain rule, launch for launch.  With any weight non-zero the few-component fusions and the
+ * speculated contraction are not taken (results do not depend on "small_k_fuse" or "speculate"); est reuse stays; eval_mode works.
+ * The weights are state of the handle: cmf_update_motifs / cmf_update_feature_maps, cmf_iterate and cmf_fit all see them; they
+ * survive cmf_set_factors and are changed by this entry alone.  The HALS, PGD, ADMM, ANLS and separable entries ignore them.
+ * CMF_ERR_ARG for a negative, NaN or infinite weight.  CMF_ERR_UNSUPPORTED for non-zero weights on a group handle, under a mask
+ * of cmf_mu_set_mask, under a divergence other than CMF_DIV_SQUARE or with the Gram forms -- and for installing any of those while a
+ * weight is non-zero.  cmf_get_counter "xortho_launches" counts the launches of the penalties' own kernels. */
+int cmf_mu_set_xortho(cmf_handle h, double lambda_xortho, double lambda_ortho_H, double lambda_ortho_W);
+/* The three penalty sums of the resident factors WITHOUT their weights and without the 1/2, summed in fp64:
+ * *xortho = sum_{i != j} (A S H')_ij,  *ortho_H = sum_{i != j} (H S H')_ij,  *ortho_W = sum_{i != j} (Wflat' Wflat)_ij.  Any pointer
+ * may be NULL.  Costs one one-source transconv of data (mult.jl:47) plus the small kernels.  Single-GPU handles only. */
+int cmf_mu_xortho_cost(cmf_handle h, double *xortho, double *ortho_H, double *ortho_W);
+/* The four unweighted denominator terms above for the resident factors: xW and oW in the shape of W (K x N x L), xH and oH in the
+ * shape of H (K x T), Julia memory order.  Any pointer may be NULL.  They show which component pairs the penalty acts on (what
+ * mult.jl:37 and :51 get added to their denominators is lambda xW + lambda_W oW and lambda xH + lambda_H oH).  Single-GPU handles only. */
+int cmf_mu_xortho_terms(cmf_handle h, double *xW, double *xH, double *oH, double *oW);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
