@@ -39,6 +39,9 @@ SYMBOLS = [
     "cmf_sep_prepare", "cmf_sep_gram", "cmf_sep_spa", "cmf_sep_nnls", "cmf_sep_shift_table", "cmf_sep_construct",
     "cmf_tensor_conv", "cmf_tensor_transconv", "cmf_init_rand", "cmf_gen_synthetic",
     "cmf_time_kernel", "cmf_kernel_times",
+    "cmf_events_create", "cmf_events_destroy", "cmf_events_set_factors", "cmf_events_get_factors", "cmf_events_update_motifs",
+    "cmf_events_update_feature_maps", "cmf_events_compute_loss", "cmf_events_iterate", "cmf_events_terms", "cmf_events_set_option",
+    "cmf_events_get_counter",
 ]
 
 
@@ -150,6 +153,18 @@ def load():
     sig("cmf_gen_synthetic", [cint, i64, i64, i64, i64, dbl, dbl, dbl, dbl, u64, pd, pd, pd])
     sig("cmf_kernel_times", [vp, ctypes.c_char_p, pd, pi64])
     sig("cmf_time_kernel", [vp, ctypes.c_char_p, cint, pd, pd])
+    pi32 = ctypes.POINTER(ctypes.c_int32)
+    sig("cmf_events_create", [pvp, cint, i64, i64, i64, i64, i64, pi32, pi32, pd])
+    sig("cmf_events_destroy", [vp])
+    sig("cmf_events_set_factors", [vp, pd, pd])
+    sig("cmf_events_get_factors", [vp, pd, pd])
+    sig("cmf_events_update_motifs", [vp, dbl, dbl])
+    sig("cmf_events_update_feature_maps", [vp, dbl, dbl, pd])
+    sig("cmf_events_compute_loss", [vp, pd])
+    sig("cmf_events_iterate", [vp, i64, cint, dbl, dbl, dbl, dbl, pd])
+    sig("cmf_events_terms", [vp, pd, pd, pd, pd, pd])
+    sig("cmf_events_set_option", [vp, ctypes.c_char_p, cint])
+    sig("cmf_events_get_counter", [vp, ctypes.c_char_p, pi64])
     if lib.cmf_abi_version() != ABI_VERSION:
         raise CMFError(CMF_ERR_STATE, f"{LIB_PATH} implements ABI {lib.cmf_abi_version()}, this binding expects {ABI_VERSION}")
     _lib = lib

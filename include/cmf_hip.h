@@ -71,7 +71,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -683,6 +683,60 @@ int cmf_tensor_conv(int device, int64_t N, int64_t T, int64_t K, int64_t L,
 /* tensor_transconv(W, X) -> out (K x T): src/common.jl:62-81. */
 int cmf_tensor_transconv(int device, int64_t N, int64_t T, int64_t K, int64_t L,
                          const double *W, const double *X, double *out);
+
+/* ---- the KL form of the MU rule on an event list ----------------------------
+ * For counts that are mostly zeros (binned spikes, photon counts): data is given as its non-zero entries, events
+ * (unit[j], time[j], count[j]) with data[unit[j], time[j]] = count[j], and the rule of cmf_mu_set_divergence with CMF_DIV_KL above runs
+ * with every sum over the data taken over the events only.  The semantics are that rule's, unchanged (src/algs/mult.jl:23-58 with
+ * data -> R; eps = eps(Float64), src/CMF.jl:20; the denominator and the clamp of mult.jl:37-38 and :51-52): R = data ./ e is zero where
+ * data is zero, so with e_j = sum over l <= min(L-1, t_j), over k, of W[k, n_j, l] H[k, t_j - l] + eps and r_j = x_j / e_j
+ *   update_motifs!:        numW[k, n, l] = sum over the events of unit n with t_j >= l of r_j H[k, t_j - l];  denomW as in the dense rule
+ *   update_feature_maps!:  r_j from the new W;  numH[k, t] = sum over the events with t <= t_j <= t + L - 1 of W[k, n_j, t_j - t] r_j;
+ *                          denomH as in the dense rule
+ *   LOSS:                  (sum_j x_j log(x_j / e_j) - sum_j x_j + sum_all e) / sum_j x_j  with e from the new W and H, where
+ *                          sum_all e = sum_k sum_{l < min(L, T)} (sum_n W[k, n, l]) (sum_{t < T - l} H[k, t]) + N T eps  (a closed form:
+ *                          the sum of e over ALL N T entries, without forming them); event sums and the closed form are added in fp64,
+ *                          in a fixed order
+ * The cost of an iteration is O(nnz K L + K T L + K N L) and the handle holds O(nnz + K T + K N L) bytes: nothing of size N x T is ever
+ * allocated (cmf_events_get_counter "device_bytes").  r_j and the log term are computed by the dense rule's own device functions, so
+ * the two paths differ only in the order in which e is summed.  No float atomics: a unit or a column window with more events than
+ * "unit_chunk" / "time_chunk" is cut into chunks whose partial sums are added in chunk order, so results are reproducible bit for bit.
+ * One GPU; no mask, no other divergence, no T sharding, no Gram form, no cmf_arm_writeback. */
+typedef struct cmf_events_s *cmf_events;
+/* Events must be sorted by (unit, time), strictly increasing (so: no duplicates), with 0 <= unit < N, 0 <= time < T and counts that are
+ * finite and > 0 (in their fp32 rounding too).  A unit or a time column without events is legal: its factor entries fall to eps, as
+ * in the dense rule.  Errors, all raised BEFORE anything touches a device: CMF_ERR_ARG for N, T, K or L < 1, nnz < 1, a NULL
+ * pointer, an index out of range, a count that is not finite and positive, or events out of order; CMF_ERR_UNSUPPORTED (the message names
+ * the limit) for K > 256 or 32 * ceil(K / 32) * L > 4096 -- the kernels keep W[:, n, :] of one unit in LDS --, for nnz >= 2^31 and for
+ * sizes the dense cmf_create refuses.  The arrays are copied: the handle keeps the events twice, unit-major and time-major (a stable
+ * counting sort) with the permutation between the two. */
+int cmf_events_create(cmf_events *h, int device, int64_t N, int64_t T, int64_t K, int64_t L,
+                      int64_t nnz, const int32_t *unit, const int32_t *time, const double *count);
+int cmf_events_destroy(cmf_events h);
+/* W (K x N x L) and H (K x T) in Julia order, like cmf_set_factors and cmf_get_factors (get: either pointer may be NULL). */
+int cmf_events_set_factors(cmf_events h, const double *W, const double *H);
+int cmf_events_get_factors(cmf_events h, double *W, double *H);
+/* update_motifs! (mult.jl:23-39) and update_feature_maps! (mult.jl:42-58; *loss receives the loss from the new W and H) in the event
+ * form above; cmf_events_compute_loss is the loss of the resident factors (alternating.jl:37). */
+int cmf_events_update_motifs(cmf_events h, double l1W, double l2W);
+int cmf_events_update_feature_maps(cmf_events h, double l1H, double l2H, double *loss);
+int cmf_events_compute_loss(cmf_events h, double *loss);
+/* n_iter iterations of alternating.jl:45-60 (eval_mode != 0: update_motifs! is skipped, :51-53) without a host round trip per call;
+ * loss_hist (n_iter values, may be NULL) is written at the end.  Bit for bit what the two rule calls give. */
+int cmf_events_iterate(cmf_events h, int64_t n_iter, int eval_mode, double l1W, double l2W, double l1H, double l2H, double *loss_hist);
+/* The terms of both updates for the resident W and H, element by element (tests): ratio[j] = r_j (nnz values, input order), numW and
+ * denomW (K x N x L), numH and denomH (K x T), Julia order, each the fp32 value the update kernels read.  Any pointer may be NULL. */
+int cmf_events_terms(cmf_events h, double *ratio, double *numW, double *numH, double *denomW, double *denomH);
+/* Options: "unit_chunk" (default 128) and "time_chunk" (default 2048): the most events one workgroup sums for a unit (numW, the ratio)
+ * and for a column's window (numH), values >= 1 -- the work tables are rebuilt; a small value on a long list costs one slab per chunk.
+ * "keep_ratio" (default 1): update_motifs! reads the r_j the loss pass before it left, the way the dense rule keeps R; 0 computes them
+ * again -- the results are bitwise the same.  CMF_ERR_ARG for another name or value. */
+int cmf_events_set_option(cmf_events h, const char *name, int value);
+/* Counters: "device_bytes" (everything the handle holds on the device), "launches" (kernel launches so far), "ratio_passes", "nnz",
+ * "unit_chunk", "time_chunk", "keep_ratio", "unit_items" / "time_items" (workgroups of the two work tables), "unit_split" /
+ * "time_split" (destinations cut into several chunks), "w_block_units" / "h_block_columns" (units and columns one workgroup of the
+ * element-wise updates owns), "ratio_waves" (events a workgroup of the ratio pass has in flight). */
+int cmf_events_get_counter(cmf_events h, const char *name, int64_t *value);
 
 /* ---- initialisation / synthetic inputs -------------------------------------
  * init_rand(data, L, K): src/model.jl:113-125, with a portable counter-based
