@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libcmf_hip.so")
 # ANLS rules, the separable fit, the cross-orthogonality penalties of the MU rule, and the KL rule on event lists
 SOURCES = [os.path.join(CSRC, f) for f in ("cmf_api.hip", "cmf_rules.hip", "cmf_groups.hip", "cmf_small.hip", "cmf_admm.hip", "cmf_anls.hip", "cmf_sep.hip", "cmf_xortho.hip", "cmf_events.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("cmf_internal.h", "cmf_kernels.h", "cmf_conv_modes.h", "cmf_small_k.h", "cmf_workers.h", "cmf_writeback.h", "cmf_rng.h",
-                                                  "cmf_fp64.h", "cmf_admm.h", "cmf_anls.h", "cmf_nnls_large.h", "cmf_sep.h", "cmf_xortho.h", "cmf_events.h")] + [
+                                                  "cmf_fp64.h", "cmf_admm.h", "cmf_anls.h", "cmf_nnls_large.h", "cmf_sep.h", "cmf_xortho.h", "cmf_events.h", "cmf_mu_install.h")] + [
     os.path.join(ROOT, "include", "cmf_hip.h")]
 
 

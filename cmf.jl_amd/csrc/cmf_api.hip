@@ -1354,41 +1354,26 @@ int cmf_option_names(char *buf, int64_t len)
     return CMF_OK;
 }
 
+// The 0/1 options that cmf_option_names does not list (off by default, see the header; not paths of the listed rules): the field, who
+// may set it, and whether it is a gate of the MU forms -- one that cannot be switched off while what it let in is installed (mu_refusal)
+struct FlagOption { const char *name; int cmf_handle_s::*field; const char *who; bool gate; };
+static const FlagOption kFlagOptions[] = {
+    {"anls_backup_only", &cmf_handle_s::anls_backup_only, "the ANLS rule runs", false}, // plain principal pivoting
+    {"nnls_large", &cmf_handle_s::nnls_large, "the ANLS rule and the separable fit run", false}, // cmf_anls_update_motifs / cmf_sep_nnls: 129 .. 1024 unknowns through global scratch
+    {"kl_mask", &cmf_handle_s::kl_mask, "the mask and the divergence of the MU rule are chosen", true}, // cmf_mu_set_mask + cmf_mu_set_divergence(KL) together
+    {"pq_mask", &cmf_handle_s::pq_mask, "the mask and the divergence of the MU rule are chosen", true}, // cmf_mu_set_mask + the Itakura-Saito / beta form together
+    {"is_div", &cmf_handle_s::is_div, "the divergence of the MU rule is chosen", true}, // lets cmf_mu_set_divergence take CMF_DIV_IS
+};
+
 int cmf_set_option(cmf_handle h, const char *name, int value)
 {
     if (!h || !name) return fail(CMF_ERR_ARG, "NULL argument");
-    if (std::strcmp(name, "anls_backup_only") == 0) { // the ANLS rule's only option (not a path of the rules cmf_option_names lists): plain principal pivoting
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "anls_backup_only: the ANLS rule runs on single-GPU handles only");
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "anls_backup_only must be 0 or 1");
-        h->anls_backup_only = value;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "nnls_large") == 0) { // cmf_anls_update_motifs / cmf_sep_nnls: 129 .. 1024 unknowns through global scratch (not a path of the listed rules either)
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "nnls_large: the ANLS rule and the separable fit run on single-GPU handles only");
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "nnls_large must be 0 or 1");
-        h->nnls_large = value;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "kl_mask") == 0) { // cmf_mu_set_mask + cmf_mu_set_divergence(KL) together (not listed by cmf_option_names: off by default, see the header)
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "kl_mask: the mask and the divergence of the MU rule are chosen on single-GPU handles only");
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "kl_mask must be 0 or 1");
-        if (!value && h->mu_mask && h->mu_div) return fail(CMF_ERR_STATE, "kl_mask: the KL form and a mask are both installed; clear the mask or restore CMF_DIV_SQUARE first");
-        h->kl_mask = value;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "pq_mask") == 0) { // cmf_mu_set_mask + the Itakura-Saito / beta form together (not listed by cmf_option_names: off by default, see the header)
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "pq_mask: the mask and the divergence of the MU rule are chosen on single-GPU handles only");
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "pq_mask must be 0 or 1");
-        if (!value && h->mu_mask && (h->mu_div == CMF_DIV_IS || h->mu_div == CMF_DIV_BETA))
-            return fail(CMF_ERR_STATE, "pq_mask: the Itakura-Saito or beta form and a mask are both installed; clear the mask or restore CMF_DIV_SQUARE first");
-        h->pq_mask = value;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "is_div") == 0) { // lets cmf_mu_set_divergence take CMF_DIV_IS (not listed by cmf_option_names: off by default, see the header)
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "is_div: the divergence of the MU rule is chosen on single-GPU handles only");
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "is_div must be 0 or 1");
-        if (!value && h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "is_div: the Itakura-Saito divergence is installed; restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-        h->is_div = value;
+    for (const FlagOption &o : kFlagOptions) {
+        if (std::strcmp(name, o.name) != 0) continue;
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "%s: %s on single-GPU handles only", name, o.who);
+        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "%s must be 0 or 1", name);
+        if (o.gate && !value) CMFTRY(mu_ask(h, MuAsk{MU_ASK_GATE_OFF, 0, 0.0, 0, name}));
+        h->*o.field = value;
         return CMF_OK;
     }
     if (h->group) {
@@ -1455,16 +1440,7 @@ int cmf_set_option(cmf_handle h, const char *name, int value)
     if (std::strcmp(name, "gram") == 0) {
         if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "gram must be 0, 1 or 2");
         if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
-        if (value && h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no Itakura-Saito form: "
-                                                                               "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-        if (value && h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no beta-divergence form: "
-                                                                                 "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-        if (value && h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms rewrite the squared-error denominators and have no KL form: "
-                                                                 "restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-        if (value && h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms have no masked form (the Gram rewriting of the denominators needs mask .* est, "
-                                                                  "which is not a product of Gram matrices): clear the mask of cmf_mu_set_mask first");
-        if (value && xo_active(h)) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms do not take the cross-orthogonality penalties of cmf_mu_set_xortho (their terms enter the "
-                                                                    "denominators the Gram form rewrites): set the weights to 0 first");
+        CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_GRAM, 0, 0.0, value}));
         h->gram = value;
         set_est(h, EST_NONE);
         return CMF_OK;
@@ -1712,10 +1688,7 @@ int cmf_hals_update_motifs(cmf_handle h, double l1W, double l2W)
 {
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     CMFTRY(check_ready(h, true));
-    if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
-    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "HALS"}));
     h->last_rule_call = 1;
     return hals_w_impl(h, l1W, l2W);
 }
@@ -1725,10 +1698,7 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     if (h && h->group) return fail(CMF_ERR_STATE, "this rule needs a single-GPU handle (its sweeps / step control do not shard over T)");
     if (!loss) return fail(CMF_ERR_ARG, "loss is NULL");
     CMFTRY(check_ready(h, true));
-    if (h->mu_mask) return fail(CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
-    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "HALS"}));
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates (alternating.jl:51-54): update_motifs! comes next
     h->last_rule_call = 2;
     CMFTRY(hals_h_impl(h, l1H, l2H));
@@ -1779,95 +1749,6 @@ static int flat_reduce(cmf_handle_s *h, const char *name, int nsums, double *sum
     return CMF_OK;
 }
 
-// What the KL form asks of the data it reads (X, or Xm under a mask): finite and non-negative with a positive sum.  One pass;
-// *sum_out is what the divergence is divided by.
-static int kl_check_data(cmf_handle_s *h, const float *X, double *sum_out)
-{
-    double sb[2]; // sum | bad entries
-    CMFTRY(flat_reduce(h, "kl_data_check_kernel", 2, sb, [&](int nb, size_t n4) {
-        hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, X, n4, h->partial);
-    }));
-    if (sb[1] > 0.0) return fail(CMF_ERR_ARG, "the KL divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", sb[1]);
-    if (!(sb[0] > 0.0)) return fail(CMF_ERR_ARG, "the KL divergence needs data with a positive sum");
-    *sum_out = sb[0];
-    return CMF_OK;
-}
-
-// the tables of the KL denominators go when the KL form is left (towards either other divergence)
-static int kl_free_tables(cmf_handle_s *h)
-{
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->kl_denH) (void)hipFree(h->kl_denH);
-    if (h->kl_sums) (void)hipFree(h->kl_sums);
-    h->kl_denH = nullptr;
-    h->kl_sums = nullptr;
-    return CMF_OK;
-}
-
-static bool mu_div_pq(const cmf_handle_s *h) { return h->mu_div == CMF_DIV_IS || h->mu_div == CMF_DIV_BETA; }
-static int is_check_data(cmf_handle_s *h);
-static int beta_check_data(cmf_handle_s *h);
-
-// the sentinel copies of data exist while a mask and the Itakura-Saito / beta form are both installed (the stream has been drained)
-static void pq_free_sentinel(cmf_handle_s *h)
-{
-    if (h->Xs) (void)hipFree(h->Xs);
-    if (h->XsT) (void)hipFree(h->XsT);
-    h->Xs = h->XsT = nullptr;
-}
-
-// Itakura-Saito / beta under the installed mask (option "pq_mask"): the data check over the observed entries alone and, when it passes,
-// fresh sentinel copies Xs / XsT (one more pass: a mask that fails has written nothing).  *count_out: the observed entries.
-static int pq_mask_sentinel(cmf_handle_s *h, int div, double *count_out)
-{
-    const CmfDims &d = h->d;
-    const size_t TPNp = (size_t)d.TP * d.Np;
-    const int strict = div == CMF_DIV_IS ? 1 : 0;
-    double cb[2]; // observed | bad among them
-    CMFTRY(flat_reduce(h, "pq_mask_sentinel_kernel", 2, cb, [&](int nb, size_t n4) {
-        hipLaunchKernelGGL(pq_mask_sentinel_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, (float *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                           (float *)nullptr, n4, strict, h->partial);
-    }));
-    if (cb[1] > 0.0 && strict)
-        return fail(CMF_ERR_ARG, "Itakura-Saito divergence needs finite, strictly positive data (%.0f entries are zero, negative, NaN or infinite): "
-                                 "add a small floor to the spectrogram, e.g. data + 1e-6 * max(data)", cb[1]);
-    if (cb[1] > 0.0) return fail(CMF_ERR_ARG, "the beta-divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", cb[1]);
-    if (!h->Xs) CMFTRY(dalloc_zero(&h->Xs, TPNp));
-    if (!h->XsT) CMFTRY(dalloc_zero(&h->XsT, TPNp));
-    CMFTRY(flat_reduce(h, "pq_mask_sentinel_kernel", 2, cb, [&](int nb, size_t n4) {
-        hipLaunchKernelGGL(pq_mask_sentinel_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, h->Xs, h->XT, h->MT, h->XsT, n4, strict, h->partial);
-    }));
-    *count_out = cb[0];
-    return CMF_OK;
-}
-
-// The MU entries leave the masked rule: est, the speculated contraction and a deferred loss are void, the masked copies of data freed.
-// While the KL form is installed (option "kl_mask") the rule goes back to the raw data, which must pass the KL check first: a failure
-// returns CMF_ERR_ARG and leaves the handle as it was.
-static int mu_mask_off(cmf_handle_s *h)
-{
-    if (h->mu_mask && mu_div_pq(h)) { // (option "pq_mask": the same re-check by the form's own rule; data_sum is the entry count again)
-        CMFTRY(h->mu_div == CMF_DIV_IS ? is_check_data(h) : beta_check_data(h));
-        h->data_sum = (double)h->d.N * (double)h->d.Tl;
-    } else if (h->mu_mask && h->mu_div) {
-        double sum = 0.0;
-        CMFTRY(kl_check_data(h, h->X, &sum));
-        h->data_sum = sum;
-    }
-    drop_carry(h);
-    h->spec_gen = -1;
-    set_est(h, EST_NONE);
-    if (!h->mu_mask && !h->Xm && !h->XmT && !h->Xs && !h->XsT) return CMF_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    pq_free_sentinel(h);
-    if (h->Xm) (void)hipFree(h->Xm);
-    if (h->XmT) (void)hipFree(h->XmT);
-    h->Xm = h->XmT = nullptr;
-    h->mu_mask = false;
-    h->xm_sumsq = h->xm_norm = 0.0;
-    return CMF_OK;
-}
-
 // sum over the flat [TP][Np] array of select(mask, data, 0)^2 (comp: mask == 0), optionally writing the masked copies (mask_select_kernel)
 static int mask_select(cmf_handle_s *h, bool write, int comp, double *sumsq)
 {
@@ -1877,81 +1758,131 @@ static int mask_select(cmf_handle_s *h, bool write, int comp, double *sumsq)
     });
 }
 
-// the mask and the masked copies of data, into whichever of h->M, h->MT is not there yet and into fresh h->Xm, h->XmT
-static int mu_install_mask(cmf_handle_s *h, const double *mask)
+// Itakura-Saito / beta under the mask in h->M: the observed count and the entries among them the form cannot take (sums[0], sums[1]);
+// write: into the sentinel copies h->Xs / h->XsT as well
+static int pq_sentinel_pass(cmf_handle_s *h, int kind, bool write, double *sums)
+{
+    return flat_reduce(h, "pq_mask_sentinel_kernel", 2, sums, [&](int nb, size_t n4) {
+        hipLaunchKernelGGL(pq_mask_sentinel_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, h->M, write ? h->Xs : nullptr, write ? h->XT : nullptr, write ? h->MT : nullptr,
+                           write ? h->XsT : nullptr, n4, kMuDivs[kind].data_rule == MU_DATA_STRICT ? 1 : 0, h->partial);
+    });
+}
+
+// What `kind` asks of the data it reads (kMuDivs' data_rule) -- the raw data, or under the mask in h->M / h->Xm the observed entries
+// alone -- in one pass; *norm is what the divergence is then divided by.  A failure is CMF_ERR_ARG with the form's own text.
+static int mu_check_data(cmf_handle_s *h, int kind, bool masked, double *norm)
 {
     const CmfDims &d = h->d;
-    const size_t TPNp = (size_t)d.TP * d.Np;
-    if (!h->M) CMFTRY(dalloc_zero(&h->M, TPNp));
-    if (!h->MT) CMFTRY(dalloc_zero(&h->MT, TPNp));
-    CMFTRY(upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT));
-    CMFTRY(dalloc_zero(&h->Xm, TPNp));
-    CMFTRY(dalloc_zero(&h->XmT, TPNp));
-    CMFTRY(mask_select(h, true, 0, &h->xm_sumsq));
-    h->xm_norm = std::sqrt(h->xm_sumsq);
-    h->mu_mask = true;
-    set_est(h, EST_NONE);
+    const MuDivRow &row = kMuDivs[kind];
+    double s[2] = {0.0, 0.0}; // sum or observed count | bad entries
+    if (row.data_rule == MU_DATA_POSITIVE_SUM || (row.data_rule == MU_DATA_NONNEG && !masked)) { // (the padding of X is zero and passes)
+        const float *X = masked ? h->Xm : h->X;
+        CMFTRY(flat_reduce(h, "kl_data_check_kernel", 2, s, [&](int nb, size_t n4) {
+            hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, X, n4, h->partial);
+        }));
+    } else if (masked) {
+        CMFTRY(pq_sentinel_pass(h, kind, false, s));
+    } else { // strictly positive at every entry that exists
+        CMFTRY(flat_reduce(h, "is_data_check_kernel", 1, &s[1], [&](int nb, size_t n4) {
+            hipLaunchKernelGGL(is_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, d.Np, d.N, d.PADL, d.Tl, h->partial);
+        }));
+    }
+    if (s[1] > 0.0) return fail(CMF_ERR_ARG, row.bad_data, s[1]);
+    if (row.data_rule == MU_DATA_POSITIVE_SUM && !(s[0] > 0.0)) return fail(CMF_ERR_ARG, "the %s needs data with a positive sum", row.noun);
+    *norm = !row.count_norm ? s[0] : masked ? s[0] : (double)d.N * (double)d.Tl;
     return CMF_OK;
 }
 
-// cmf_mu_set_mask while the KL form is installed (option "kl_mask"): the mask goes into buffers of its own, Xm must pass the KL check
-// (finite and non-negative where observed, a positive sum), and only then does it replace what the handle had -- a mask that fails
-// returns CMF_ERR_ARG and leaves the handle as it was (est, the speculation and a deferred loss are void either way).
-static int kl_install_mask(cmf_handle_s *h, const double *mask)
+// The one transition between the forms of the MU rule (divergence x mask): cmf_mu_set_mask, cmf_mu_set_divergence,
+// cmf_mu_set_beta_divergence and cmf_set_mask (which takes the handle's one mask for the PGD entries: MU_MASK_RELEASE keeps M / MT) are
+// argument checks and a call.  Refusals (cmf_mu_install.h) touch nothing; then est, the speculation and the carry are void; then the
+// target's data check -- a new mask goes into fresh buffers first -- and its buffers; only then does the handle change, so a failure
+// leaves the form it had, working; last, what the target's row of kMuDivs does not list is freed.
+enum MuMaskRequest { MU_MASK_KEEP, MU_MASK_SET, MU_MASK_CLEAR, MU_MASK_RELEASE };
+static int mu_set_form(cmf_handle_s *h, int kind, double beta, int mask_req, const double *mask = nullptr)
 {
+    const bool to_beta = kind == CMF_DIV_BETA;
+    MuAsk ask{mask_req == MU_MASK_SET ? MU_ASK_SET_MASK : mask_req != MU_MASK_KEEP ? MU_ASK_CLEAR_MASK : to_beta ? MU_ASK_SET_BETA : MU_ASK_SET_KIND, kind, beta, mask_req == MU_MASK_RELEASE};
+    CMFTRY(mu_ask(h, ask));
+    if (mask_req == MU_MASK_KEEP && kind == h->mu_div && (!to_beta || beta == h->mu_beta)) return CMF_OK; // the same again: nothing happens
+    HIPCHK(hipSetDevice(h->device));
+    if (mask_req != MU_MASK_RELEASE && h->wb && h->wb->armed) wb_disarm(h);
     drop_carry(h);
     h->spec_gen = -1;
     set_est(h, EST_NONE);
     HIPCHK(hipStreamSynchronize(h->stream));
-    float *const old[6] = {h->M, h->MT, h->Xm, h->XmT, h->Xs, h->XsT};
-    const bool old_on = h->mu_mask;
-    const double old_ss = h->xm_sumsq, old_norm = h->xm_norm;
-    h->M = h->MT = h->Xm = h->XmT = h->Xs = h->XsT = nullptr;
-    double sum = 0.0;
-    int rc = mu_install_mask(h, mask);
-    // (Itakura-Saito / beta, option "pq_mask": the form's own check over the observed entries, the sentinel copies, the observed count)
-    if (rc == CMF_OK) rc = mu_div_pq(h) ? pq_mask_sentinel(h, h->mu_div, &sum) : kl_check_data(h, h->Xm, &sum);
-    if (rc != CMF_OK) {
+    const CmfDims &d = h->d;
+    const size_t TPNp = (size_t)d.TP * d.Np;
+    const bool was_masked = h->mu_mask, masked = mask_req == MU_MASK_SET || (mask_req == MU_MASK_KEEP && was_masked);
+    const unsigned bufs = masked ? kMuDivs[kind].bufs_masked : kMuDivs[kind].bufs;
+    // the data is checked again when what the rule reads or what it asks of it changes (another beta alone changes neither)
+    const bool recheck = kind != CMF_DIV_SQUARE && (mask_req == MU_MASK_SET || masked != was_masked || kind != h->mu_div);
+    float *cmf_handle_s::*const mbufs[6] = {&cmf_handle_s::M, &cmf_handle_s::MT, &cmf_handle_s::Xm, &cmf_handle_s::XmT, &cmf_handle_s::Xs, &cmf_handle_s::XsT};
+    float *old[6];
+    for (int i = 0; i < 6; ++i) old[i] = h->*mbufs[i];
+    const double old_ss = h->xm_sumsq;
+    double norm = h->data_sum;
+    int rc = CMF_OK;
+    auto ensure = [&](float **p, size_t n) { return (rc != CMF_OK || *p) ? rc : (rc = dalloc_zero(p, n)); };
+    if (mask_req == MU_MASK_SET) { // the mask and the masked copies of data, in buffers of their own
+        for (int i = 0; i < 6; ++i) h->*mbufs[i] = nullptr;
+        for (int i = 0; i < 4; ++i) ensure(&(h->*mbufs[i]), TPNp);
+        if (rc == CMF_OK) rc = upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT);
+        if (rc == CMF_OK) rc = mask_select(h, true, 0, &h->xm_sumsq);
+    }
+    if (rc == CMF_OK && recheck) rc = mu_check_data(h, kind, masked, &norm);
+    if (bufs & MU_BUF_XS) { ensure(&h->Xs, TPNp); ensure(&h->XsT, TPNp); }
+    if (bufs & MU_BUF_EST2) { ensure(&h->est2, TPNp); ensure(&h->est2T, TPNp); }
+    if (bufs & MU_BUF_KL) {
+        ensure(&h->kl_denH, (size_t)d.Tl * d.K32);
+        if (rc == CMF_OK && !h->kl_sums) rc = dalloc_zero(&h->kl_sums, (size_t)d.K32 * std::max(d.L, KL_HCHUNKS));
+    }
+    // (the sentinel copies of one mask are the same for Itakura-Saito and beta: written over, they still serve the form the handle has)
+    double again[2];
+    if (rc == CMF_OK && recheck && (bufs & MU_BUF_XS)) rc = pq_sentinel_pass(h, kind, true, again);
+    if (rc != CMF_OK) { // the form the handle had, with its buffers
         (void)hipStreamSynchronize(h->stream);
-        for (float *q : {h->M, h->MT, h->Xm, h->XmT, h->Xs, h->XsT})
-            if (q) (void)hipFree(q);
-        h->M = old[0]; h->MT = old[1]; h->Xm = old[2]; h->XmT = old[3]; h->Xs = old[4]; h->XsT = old[5];
-        h->mu_mask = old_on;
+        for (int i = 0; i < 6; ++i) {
+            if (h->*mbufs[i] != old[i]) (void)hipFree(h->*mbufs[i]);
+            h->*mbufs[i] = old[i];
+        }
         h->xm_sumsq = old_ss;
-        h->xm_norm = old_norm;
         return rc;
     }
-    for (float *q : old)
-        if (q) (void)hipFree(q);
-    h->data_sum = sum;
+    h->mu_div = kind;
+    h->mu_mask = masked;
+    h->data_sum = norm;
+    if (!masked) h->xm_sumsq = 0.0;
+    h->xm_norm = std::sqrt(h->xm_sumsq);
+    if (to_beta) {
+        float *c = h->beta_consts; // ConvParams::beta_m1 .. beta_c: the exponents and phi's constants (cmf_beta_term), rounded once from fp64
+        c[0] = (float)(beta - 1.0); c[1] = (float)(beta - 2.0); c[2] = (float)beta; c[3] = (float)(1.0 / beta); c[4] = (float)(1.0 / (beta * (beta - 1.0)));
+        double prod = 1.0, fact = 2.0; // c_k = 2 (beta - 2) ... (beta - k - 1) / (k + 2)!
+        for (int k = 1; k <= 6; ++k) {
+            prod *= beta - (double)(k + 1);
+            fact *= (double)(k + 2);
+            c[4 + k] = (float)(2.0 * prod / fact);
+        }
+        h->mu_beta = beta;
+        h->mu_gamma = (float)(beta < 1.0 ? 1.0 / (2.0 - beta) : beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); // Fevotte & Idier 2011
+    }
+    // what the target does not list goes: the buffers a new mask replaces, the mask with cmf_mu_set_mask(NULL), the masked and sentinel
+    // copies without a mask or a form that reads them, the KL tables on leaving KL
+    auto drop = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    for (int i = 0; i < 6; ++i) {
+        if (mask_req == MU_MASK_SET) { if (old[i]) (void)hipFree(old[i]); }
+        else if (i < 2 ? mask_req == MU_MASK_CLEAR : !(bufs & (i < 4 ? MU_BUF_XM : MU_BUF_XS))) drop(h->*mbufs[i]);
+    }
+    if (!(bufs & MU_BUF_KL)) { drop(h->kl_denH); drop(h->kl_sums); }
     return CMF_OK;
 }
 
 int cmf_mu_set_mask(cmf_handle h, const double *mask)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the masked MU rule runs on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
-    HIPCHK(hipSetDevice(h->device));
-    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
-    if (h->wb && h->wb->armed) wb_disarm(h);
-    if (!mask) { // the unmasked rule again; the mask itself goes too
-        CMFTRY(mu_mask_off(h));
-        if (h->M) (void)hipFree(h->M);
-        if (h->MT) (void)hipFree(h->MT);
-        h->M = h->MT = nullptr;
-        return CMF_OK;
-    }
-    if (h->mu_div == CMF_DIV_BETA && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form (its Q = e.^(beta - 1) would need the mask tile in the "
-                                                                     "storing epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-    if (h->mu_div == CMF_DIV_IS && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form (its Q = 1 ./ e would need the mask tile in the storing "
-                                                                   "epilogues): restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-    if (h->mu_div == CMF_DIV_KL && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: restore CMF_DIV_SQUARE with cmf_mu_set_divergence first");
-    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") have no masked form: the Gram rewriting of the denominators needs mask .* est, "
-                                                  "which is not a product of Gram matrices; set gram = 0 first");
-    if (xo_active(h)) return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho have no masked form: set the weights to 0 first");
-    const CmfDims &d = h->d;
-    const size_t NT = (size_t)d.N * d.Tl;
+    if (!mask) return mu_set_form(h, h->mu_div, h->mu_beta, MU_MASK_CLEAR); // the unmasked rule again; the mask itself goes too
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_MASK})); // (the refusals come before the look at the mask's entries)
+    const size_t NT = (size_t)h->d.N * h->d.Tl;
     size_t ones = 0;
     for (size_t i = 0; i < NT; ++i) {
         if (mask[i] == 1.0) ++ones;
@@ -1959,141 +1890,20 @@ int cmf_mu_set_mask(cmf_handle h, const double *mask)
             return fail(CMF_ERR_ARG, "the MU rule takes a mask of 0 and 1 only (entry %zu is %g); real-valued weights exist for the PGD rule (cmf_set_mask)", i, mask[i]);
     }
     if (ones == 0) return fail(CMF_ERR_ARG, "the mask observes nothing (every entry is 0)");
-    if (h->mu_div) return kl_install_mask(h, mask);
-    CMFTRY(mu_mask_off(h));
-    return mu_install_mask(h, mask);
-}
-
-// What the Itakura-Saito form asks of data: finite and strictly positive at every entry that exists.  One pass (is_data_check_kernel).
-static int is_check_data(cmf_handle_s *h)
-{
-    const CmfDims &d = h->d;
-    double bad = 0.0;
-    CMFTRY(flat_reduce(h, "is_data_check_kernel", 1, &bad, [&](int nb, size_t n4) {
-        hipLaunchKernelGGL(is_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, d.Np, d.N, d.PADL, d.Tl, h->partial);
-    }));
-    if (bad > 0.0)
-        return fail(CMF_ERR_ARG, "Itakura-Saito divergence needs finite, strictly positive data (%.0f entries are zero, negative, NaN or infinite): "
-                                 "add a small floor to the spectrogram, e.g. data + 1e-6 * max(data)", bad);
-    return CMF_OK;
-}
-
-// cmf_mu_set_divergence(CMF_DIV_IS) (est, the speculation and the carry have been voided): refusals, the data check, the second pair
-// of est-shaped buffers.  A failure leaves the divergence the handle had.
-static int is_install(cmf_handle_s *h)
-{
-    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no Itakura-Saito form; set gram = 0 first");
-    if (h->mu_mask && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the Itakura-Saito form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
-    const CmfDims &d = h->d;
-    double count = (double)d.N * (double)d.Tl;
-    if (h->mu_mask) CMFTRY(pq_mask_sentinel(h, CMF_DIV_IS, &count)); // (option "pq_mask": the check over the observed entries, the sentinel copies)
-    else CMFTRY(is_check_data(h));
-    if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
-    if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
-    if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
-    h->data_sum = count; // (under a mask: the observed entries)
-    h->mu_div = CMF_DIV_IS;
-    return CMF_OK;
+    return mu_set_form(h, h->mu_div, h->mu_beta, MU_MASK_SET, mask);
 }
 
 int cmf_mu_set_divergence(cmf_handle h, int kind)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    // (CMF_DIV_IS is taken only with option "is_div" set; without it every call answers as it did before the form existed)
-    if (kind != CMF_DIV_SQUARE && kind != CMF_DIV_KL && !(kind == CMF_DIV_IS && h->is_div))
-        return fail(CMF_ERR_ARG, h->is_div ? "kind must be CMF_DIV_SQUARE (0), CMF_DIV_KL (1) or CMF_DIV_IS (2)" : "kind must be CMF_DIV_SQUARE (0) or CMF_DIV_KL (1)");
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
-    HIPCHK(hipSetDevice(h->device));
-    if (kind == h->mu_div) return CMF_OK;
-    if (kind != CMF_DIV_SQUARE && xo_active(h))
-        return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho are terms of the squared-error rule and have no divergence form: set the weights to 0 first");
-    if (h->wb && h->wb->armed) wb_disarm(h);
-    drop_carry(h);
-    h->spec_gen = -1;
-    set_est(h, EST_NONE);
-    if (kind == CMF_DIV_SQUARE) { // today's rule again, launch for launch
-        CMFTRY(kl_free_tables(h));
-        pq_free_sentinel(h); // (the stream has been drained)
-        h->mu_div = CMF_DIV_SQUARE;
-        return CMF_OK;
-    }
-    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
-    if (kind == CMF_DIV_IS) return is_install(h);
-    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no KL form; set gram = 0 first");
-    if (h->mu_mask && !h->kl_mask) return fail(CMF_ERR_UNSUPPORTED, "the KL form of the MU rule has no masked form yet: clear the mask of cmf_mu_set_mask first");
-    // data must be finite and non-negative with a positive sum: one pass (the padding of X is zero).  Under a mask: where observed (Xm)
-    const CmfDims &d = h->d;
-    double sum = 0.0;
-    CMFTRY(kl_check_data(h, h->mu_mask ? h->Xm : h->X, &sum));
-    if (!h->kl_denH) CMFTRY(dalloc_zero(&h->kl_denH, (size_t)d.Tl * d.K32));
-    if (!h->kl_sums) CMFTRY(dalloc_zero(&h->kl_sums, (size_t)d.K32 * std::max(d.L, KL_HCHUNKS)));
-    if (h->Xs || h->XsT) { // (from Itakura-Saito / beta under a mask: their sentinel copies go)
-        HIPCHK(hipStreamSynchronize(h->stream));
-        pq_free_sentinel(h);
-    }
-    h->data_sum = sum;
-    h->mu_div = CMF_DIV_KL;
-    return CMF_OK;
-}
-
-// What the beta form asks of data: finite and non-negative.  The KL form's pass (its sum is not asked for: the padding of X is zero and passes).
-static int beta_check_data(cmf_handle_s *h)
-{
-    double sb[2]; // sum | bad entries
-    CMFTRY(flat_reduce(h, "kl_data_check_kernel", 2, sb, [&](int nb, size_t n4) {
-        hipLaunchKernelGGL(kl_data_check_kernel, dim3(nb), dim3(256), 0, h->stream, h->X, n4, h->partial);
-    }));
-    if (sb[1] > 0.0) return fail(CMF_ERR_ARG, "the beta-divergence needs finite, non-negative data (%.0f entries are negative, NaN or infinite)", sb[1]);
-    return CMF_OK;
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_KIND, kind})); // (CMF_DIV_BETA is no kind of this entry: refused here, before mu_set_form would take it for a beta)
+    return mu_set_form(h, kind, 0.0, MU_MASK_KEEP);
 }
 
 int cmf_mu_set_beta_divergence(cmf_handle h, double beta)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    // the accepted set (include/cmf_hip.h; the window's edges are accepted, whatever rounding made of 1 - 0.01)
-    const double w = CMF_BETA_WINDOW * (1.0 - 1e-9);
-    if (!std::isfinite(beta)) return fail(CMF_ERR_ARG, "beta must be finite");
-    if (beta == 0.0 || beta == 1.0)
-        return fail(CMF_ERR_ARG, "beta = %g is CMF_DIV_IS (beta = 0) or CMF_DIV_KL (beta = 1): the beta formula is 0/0 there, use cmf_mu_set_divergence with those kinds", beta);
-    if (beta < 0.0 || beta > CMF_BETA_MAX) return fail(CMF_ERR_ARG, "beta must lie in (0, %g], got %.17g", (double)CMF_BETA_MAX, beta);
-    if (beta < w || std::fabs(beta - 1.0) < w)
-        return fail(CMF_ERR_ARG, "beta = %.17g lies within %g of 0 or 1, where the float32 loss loses its digits to the factor 1 / (beta (beta - 1)): use CMF_DIV_IS / CMF_DIV_KL, "
-                                 "or a beta at least %g away", beta, (double)CMF_BETA_WINDOW, (double)CMF_BETA_WINDOW);
-    if (h->group || h->root_only || h->sharded)
-        return fail(CMF_ERR_UNSUPPORTED, "the divergence of the MU rule is chosen on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
-    HIPCHK(hipSetDevice(h->device));
-    if (xo_active(h))
-        return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties of cmf_mu_set_xortho are terms of the squared-error rule and have no divergence form: set the weights to 0 first");
-    if (h->mu_div == CMF_DIV_BETA && beta == h->mu_beta) return CMF_OK;
-    if (h->wb && h->wb->armed) wb_disarm(h);
-    drop_carry(h);
-    h->spec_gen = -1;
-    set_est(h, EST_NONE);
-    if (!h->have_data) return fail(CMF_ERR_STATE, "handle was created without data");
-    if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") rewrite the squared-error denominators and have no beta-divergence form; set gram = 0 first");
-    if (h->mu_mask && !h->pq_mask) return fail(CMF_ERR_UNSUPPORTED, "the beta-divergence form of the MU rule has no masked form: clear the mask of cmf_mu_set_mask first");
-    const CmfDims &d = h->d;
-    double count = (double)d.N * (double)d.Tl;
-    if (h->mu_mask && h->mu_div == CMF_DIV_BETA) count = h->data_sum; // (another beta under the same mask: checked, the copies are there)
-    else if (h->mu_mask) CMFTRY(pq_mask_sentinel(h, CMF_DIV_BETA, &count)); // (option "pq_mask"; from Itakura-Saito too: the copies are the same, the check is not run twice for nothing)
-    else if (h->mu_div != CMF_DIV_BETA) CMFTRY(beta_check_data(h)); // (a failure leaves the divergence the handle had)
-    if (!h->est2) CMFTRY(dalloc_zero(&h->est2, (size_t)d.TP * d.Np));
-    if (!h->est2T) CMFTRY(dalloc_zero(&h->est2T, (size_t)d.TP * d.Np));
-    if (h->mu_div == CMF_DIV_KL) CMFTRY(kl_free_tables(h)); // (leaving the KL form: its tables go as they do towards CMF_DIV_SQUARE)
-    float *c = h->beta_consts; // ConvParams::beta_m1 .. beta_c: the exponents and phi's constants (cmf_beta_term), rounded once from fp64
-    c[0] = (float)(beta - 1.0); c[1] = (float)(beta - 2.0); c[2] = (float)beta; c[3] = (float)(1.0 / beta); c[4] = (float)(1.0 / (beta * (beta - 1.0)));
-    double prod = 1.0, fact = 2.0; // c_k = 2 (beta - 2) ... (beta - k - 1) / (k + 2)!
-    for (int k = 1; k <= 6; ++k) {
-        prod *= beta - (double)(k + 1);
-        fact *= (double)(k + 2);
-        c[4 + k] = (float)(2.0 * prod / fact);
-    }
-    h->mu_beta = beta;
-    h->mu_gamma = (float)(beta < 1.0 ? 1.0 / (2.0 - beta) : beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); // Fevotte & Idier 2011
-    h->data_sum = count; // (under a mask: the observed entries)
-    h->mu_div = CMF_DIV_BETA;
-    return CMF_OK;
+    return mu_set_form(h, CMF_DIV_BETA, beta, MU_MASK_KEEP);
 }
 
 int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *data_sumsq)
@@ -2136,8 +1946,7 @@ int cmf_set_mask(cmf_handle h, const double *mask)
     HIPCHK(hipSetDevice(h->device));
     if (h->sharded) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
     const CmfDims &d = h->d;
-    set_est(h, EST_NONE);
-    CMFTRY(mu_mask_off(h)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
+    CMFTRY(mu_set_form(h, h->mu_div, h->mu_beta, MU_MASK_RELEASE)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
     if (!mask) { // back to the plain SquareLoss
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->M) (void)hipFree(h->M);
@@ -2179,9 +1988,7 @@ int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int nonne
         return group_pgd_w(h, h->group, pen_sq, pen_abs, nonneg);
     }
     CMFTRY(check_ready(h, true));
-    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "PGD"}));
     return pgd_w_impl(h, pen_sq, pen_abs, nonneg);
 }
 
@@ -2194,9 +2001,7 @@ static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_
         return group_pgd_h(h, h->group, pen_sq, pen_abs, nonneg, loss);
     }
     CMFTRY(check_ready(h, true));
-    if (h->mu_div == CMF_DIV_IS) return fail(CMF_ERR_STATE, "the Itakura-Saito divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div == CMF_DIV_BETA) return fail(CMF_ERR_STATE, "the beta-divergence is installed (cmf_mu_set_beta_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
-    if (h->mu_div) return fail(CMF_ERR_STATE, "the KL divergence is installed (cmf_mu_set_divergence): this rule minimises the squared error only; restore CMF_DIV_SQUARE first");
+    CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "PGD"}));
     return pgd_h_impl(h, pen_sq, pen_abs, nonneg, loss);
 }
 

@@ -190,8 +190,7 @@ static const char *const kHalsLaunchNames[] = {
     "hals_h_stage_kernel", "hals_h_stage_kernel:lag2", "hals_h_stage_kernel:lag3", "hals_h_row_gen_kernel", "hals_h_push_gen_kernel"};
 static_assert(sizeof(kHalsLaunchNames) / sizeof(kHalsLaunchNames[0]) == HL_NCLS, "one name per HALS launch path");
 
-// mu_div of a handle under cmf_mu_set_beta_divergence: behind the kinds of cmf_mu_set_divergence, which does not take it
-#define CMF_DIV_BETA 3
+#include "cmf_mu_install.h" // CMF_DIV_BETA; what each divergence needs to be installed and when a request is refused (free of HIP)
 
 // What est / estT hold for the resident W, H (cmf_handle_s::est_kind): a reader recomputes on a mismatch, every writer passes through set_est.
 enum EstKind : int {
@@ -384,6 +383,14 @@ struct cmf_handle_s {
     int64_t xo_launches = 0;
 };
 static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
+// the refusals of cmf_mu_install.h asked of this handle: CMF_OK, or the code with its text as the thread's last error
+static inline int mu_ask(const cmf_handle_s *h, const MuAsk &q)
+{
+    const MuFacts f{h->mu_div, h->mu_beta, h->mu_mask, h->kl_mask, h->pq_mask, h->is_div, h->gram, xo_active(h), h->group || h->root_only || h->sharded, h->have_data};
+    std::string msg;
+    const int rc = mu_refusal(f, q, &msg);
+    return rc == CMF_OK ? rc : fail(rc, "%s", msg.c_str());
+}
 // cmf_xortho.hip: frees the tables (destroy_impl); the W side -- lambda xW + lambda_W oW folded into denomW behind numW in h->numden,
 // between the C2 contraction and w_apply_impl --; W has been updated and H has not (G stays current); the H side -- numH summed into a
 // finished table and the finished denominator table denomH + (lambda xH + lambda_H G), both in the single-slab form of launch_h_update
@@ -561,7 +568,8 @@ static inline void set_est(cmf_handle_s *h, int kind) // every change of what es
 }
 // ---- the forms of the MU rule: one row each ----
 // The single-handle MU path (cmf_api.hip: w_phase_impl, h_update_impl, launch_loss_conv, w_speculate, cmf_masked_loss) reads the active form from
-// mu_form(h).  A new form: a row here, its conv modes in mu_launch_conv (cmf_api.hip), its install / refusal entry (cmf_mu_set_mask, cmf_mu_set_divergence).
+// mu_form(h).  A new form: a row here, its conv modes in mu_launch_conv (cmf_api.hip), and what it needs to be installed in its divergence's row of kMuDivs
+// (cmf_mu_install.h: gates, data rule, buffers; mu_refusal there for what it cannot live beside) -- mu_set_form (cmf_api.hip) installs every form from those.
 using MuBuf = float *cmf_handle_s::*; // a buffer of the handle
 constexpr MuBuf MU_NONE = nullptr, MU_X = &cmf_handle_s::X, MU_XT = &cmf_handle_s::XT, MU_XM = &cmf_handle_s::Xm, MU_XMT = &cmf_handle_s::XmT, MU_M = &cmf_handle_s::M,
                 MU_XS = &cmf_handle_s::Xs, MU_XST = &cmf_handle_s::XsT,

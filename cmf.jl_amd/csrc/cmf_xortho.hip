@@ -173,10 +173,7 @@ int cmf_mu_set_xortho(cmf_handle h, double lambda_xortho, double lambda_ortho_H,
     if (any) {
         if (h->group || h->root_only || h->sharded)
             return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties run on a single-GPU handle: T-sharded groups (cmf_create_multi, cmf_create_shard) are not supported");
-        if (h->mu_mask) return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties have no masked form: clear the mask of cmf_mu_set_mask first");
-        if (h->mu_div) return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties are terms of the squared-error rule and have no divergence form: restore CMF_DIV_SQUARE "
-                                                        "with cmf_mu_set_divergence first");
-        if (h->gram) return fail(CMF_ERR_UNSUPPORTED, "the cross-orthogonality penalties enter the denominators the Gram forms (option \"gram\") rewrite: set gram = 0 first");
+        CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_XORTHO})); // (under a mask, a divergence or the Gram forms: cmf_mu_install.h)
         HIPCHK(hipSetDevice(h->device));
         CMFTRY(xo_ensure(h));
     }

@@ -141,6 +141,8 @@ _DIV_KL = 1
 _DIV_IS = 2
 _DIV_BETA = 3
 _DIV_NAMES = {0: ":square", 1: ":kl", 2: ":itakura_saito", 3: ":beta"}
+# per divergence form: its label in fit_cnmf's messages, the library option that lets it run under mask=, the KL text's "yet"
+_DIV_FIT = {_DIV_KL: ("KL", "kl_mask", " yet"), _DIV_IS: ("Itakura-Saito", "pq_mask", ""), _DIV_BETA: ("beta-divergence", "pq_mask", "")}
 BETA_WINDOW = 0.01  # CMF_BETA_WINDOW (include/cmf_hip.h; profiles/mu_beta_precision.txt: window)
 BETA_MAX = 4.0      # CMF_BETA_MAX
 
@@ -1594,35 +1596,17 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
             raise ValueError("mask must hold 0 and 1 only (1 = observed)")
     divergence = _divergence_kind(kw.get("divergence", ":square"))
     beta = _check_beta(divergence, kw.get("beta", None))
-    if divergence == _DIV_BETA:
+    if divergence:  # what the divergence forms of the MU rule do not go with (the library refuses the same: csrc/cmf_mu_install.h)
+        name, (label, mask_option, yet) = _DIV_NAMES[divergence], _DIV_FIT[divergence]
         if rule_type is not MultUpdate:
-            raise NotImplementedError("divergence=':beta' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
+            raise NotImplementedError(f"divergence='{name}' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
                                       "fits minimise the squared error (PGD also the absolute error)")
-        if mask is not None and not (options or {}).get("pq_mask", 0):
-            raise NotImplementedError("divergence=':beta' is not available with mask=: the beta-divergence form of the MU rule "
-                                      "has no masked form unless the library option is set: options={'pq_mask': 1}")
+        if mask is not None and not (options or {}).get(mask_option, 0):
+            raise NotImplementedError(f"divergence='{name}' is not available with mask=: the {label} form of the MU rule "
+                                      f"has no masked form{yet} unless the library option is set: options={{'{mask_option}': 1}}")
         if devices is not None:
-            raise NotImplementedError("divergence=':beta' is not available with devices=[...]: the beta-divergence form of the "
+            raise NotImplementedError(f"divergence='{name}' is not available with devices=[...]: the {label} form of the "
                                       "MU rule runs on one GPU")
-    elif divergence == _DIV_IS:
-        if rule_type is not MultUpdate:
-            raise NotImplementedError("divergence=':itakura_saito' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable "
-                                      "fits minimise the squared error (PGD also the absolute error)")
-        if mask is not None and not (options or {}).get("pq_mask", 0):
-            raise NotImplementedError("divergence=':itakura_saito' is not available with mask=: the Itakura-Saito form of the MU rule "
-                                      "has no masked form unless the library option is set: options={'pq_mask': 1}")
-        if devices is not None:
-            raise NotImplementedError("divergence=':itakura_saito' is not available with devices=[...]: the Itakura-Saito form of the "
-                                      "MU rule runs on one GPU")
-    elif divergence:
-        if rule_type is not MultUpdate:
-            raise NotImplementedError("divergence=':kl' is implemented for alg=:mult; the HALS, PGD, ADMM, ANLS and separable fits "
-                                      "minimise the squared error (PGD also the absolute error)")
-        if mask is not None and not (options or {}).get("kl_mask", 0):
-            raise NotImplementedError("divergence=':kl' is not available with mask=: the KL form of the MU rule has no masked form yet "
-                                      "unless the library option is set: options={'kl_mask': 1}")
-        if devices is not None:
-            raise NotImplementedError("divergence=':kl' is not available with devices=[...]: the KL form of the MU rule runs on one GPU")
     xortho = _check_xortho(*[kw.get(k, 0.0) for k in _XORTHO_KW])
     if any(xortho):
         if rule_type is not MultUpdate:

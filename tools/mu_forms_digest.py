@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bit-level digest of the MU rule's five forms (square, square + mask, KL, KL + mask, Itakura-Saito) through every driver.
+"""Bit-level digest of the MU rule's eight forms (square, KL, Itakura-Saito and beta = 0.5, each with and without a mask) through every driver.
 
     python3 tools/mu_forms_digest.py > digest.txt
 
@@ -8,7 +8,7 @@ counters (cmf_get_counter).  Two builds of the library compute the same thing th
 are the same text: run it on both and `diff` (profiles/mu_forms_digest_*.txt).  The cases: the forms x the shapes (48, 300, 4, 8),
 (96, 1000, 32, 12), (37, 150, 33, 7) (few components / the one-wave tiles with their cut tail / the general-K kernel) x reuse_est 1, 0
 x three iterations call by call, cmf_iterate(3), cmf_fit(max_itr = 3); option conv_kernel = 2 at K = 32; cmf_masked_loss with both
-values of `complement` under the two masked forms; non-zero l1 / l2 once per form.  Data is strictly positive (Itakura-Saito accepts
+values of `complement` under the four masked forms; non-zero l1 / l2 once per form.  Data is strictly positive (Itakura-Saito accepts
 it) and comes, like the initial factors, from the library's counter RNG.
 """
 import hashlib
@@ -25,7 +25,7 @@ from exact_problems import LAUNCH_PATHS  # noqa: E402
 
 SHAPES = [(48, 300, 4, 8), (96, 1000, 32, 12), (37, 150, 33, 7)]
 FORMS = [("square", ":square", False), ("square+mask", ":square", True), ("kl", ":kl", False), ("kl+mask", ":kl", True),
-         ("is", ":itakura_saito", False)]
+         ("is", ":itakura_saito", False), ("is+mask", ":itakura_saito", True), ("beta", ":beta", False), ("beta+mask", ":beta", True)]
 COUNTERS = ["launches:" + p for p in LAUNCH_PATHS] + ["speculated_contractions", "small_k_fused_h_updates"]
 REG = dict(l1W=0.01, l2W=0.02, l1H=0.03, l2H=0.005)
 _PROBLEMS = {}
@@ -48,9 +48,10 @@ def make_rule(shape, kind, masked, options):
     data, W0, H0, mask = problem(shape)
     rule = cmf.MultUpdate(data, W0, H0)
     rule.set_option("kl_mask", 1)
+    rule.set_option("pq_mask", 1)
     for k, v in options.items():
         rule.set_option(k, v)
-    rule.set_divergence(kind)
+    rule.set_divergence(kind, beta=0.5 if kind == ":beta" else None)
     if masked:
         rule.set_mask(mask)
     return rule
