@@ -557,10 +557,10 @@ static int check_ready(cmf_handle_s *h, bool need_data)
 }
 
 // A conv family and base known at run time reach launch_conv's template argument here: exactly the modes the MU rule launches.
-static int mu_launch_conv(cmf_handle_s *h, int family, int base, float *out, int T_store, int gy, const float *data)
+static int mu_launch_conv(cmf_handle_s *h, int family, int base, float *out, int T_store, int gy, const float *data, int loss_abs = 0)
 {
     switch (conv_mode(family, base)) {
-#define CASE(M_) case M_: return launch_conv<M_>(h, out, T_store, gy, data);
+#define CASE(M_) case M_: return launch_conv<M_>(h, out, T_store, gy, data, loss_abs);
         CASE(CONV_EST) CASE(CONV_EST_T) CASE(CONV_LOSS) CASE(CONV_LOSS_EST)
         CASE(CONV_MUM_EST) CASE(CONV_MUM_EST_T) CASE(CONV_MUM_LOSS) CASE(CONV_MUM_LOSS_EST)
         CASE(CONV_KL_R) CASE(CONV_KL_R_T) CASE(CONV_KL_LOSS) CASE(CONV_KL_LOSS_R)
@@ -1919,13 +1919,10 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
     // select, then the same select on data^2.  Both use the loss partials, one after the other on the stream.
     // Under the KL form with its mask (option "kl_mask") the pair is (sum of the divergence terms, sum of data) over the selected entries.
     const MuForm &f = mu_form(h);
-    h->mask_complement_now = comp ? 1 : 0;
     // Under Itakura-Saito / beta with their mask (option "pq_mask") it is (sum of the divergence terms, number of entries): the observed
     // entries are summed on the sentinel copy like the training loss, the complement on the raw data with the mask tile.
     const bool pqm = conv_pq_masked(f.held_out_family);
-    const int rc = mu_launch_conv(h, f.held_out_family, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy, (pqm && !comp) ? h->Xs : nullptr);
-    h->mask_complement_now = 0;
-    CMFTRY(rc);
+    CMFTRY(mu_launch_conv(h, f.held_out_family, CONV_BASE_LOSS, nullptr, h->d.Tl, h->conv_gy, (pqm && !comp) ? h->Xs : nullptr, comp ? 1 : 0));
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, h->conv_partials, h->d_scalar + 1, (double *)nullptr);
     KCHK("loss_reduce_kernel");
     CMFTRY(read_scalar(h, 1, resid_sumsq));
@@ -1939,25 +1936,41 @@ int cmf_masked_loss(cmf_handle h, int complement, double *resid_sumsq, double *d
     });
 }
 
-int cmf_set_mask(cmf_handle h, const double *mask)
+// MaskedLoss (pgd.jl:58-70) on one shard: the mask is cut like data -- the shard holds its own columns in both layouts and the right
+// lag halo in the transposed one.  m: the shard's first column; NULL: back to the plain loss
+static int shard_set_mask(cmf_handle_s *s, const double *m)
 {
-    if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
-    if (h->group) return group_set_mask(h->group, mask);
-    HIPCHK(hipSetDevice(h->device));
-    if (h->sharded) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
-    const CmfDims &d = h->d;
-    CMFTRY(mu_set_form(h, h->mu_div, h->mu_beta, MU_MASK_RELEASE)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
-    if (!mask) { // back to the plain SquareLoss
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->M) (void)hipFree(h->M);
-        if (h->MT) (void)hipFree(h->MT);
-        h->M = h->MT = nullptr;
+    const CmfDims &d = s->d;
+    set_est(s, EST_NONE);
+    if (!m) {
+        if (s->M) (void)hipFree(s->M);
+        if (s->MT) (void)hipFree(s->MT);
+        s->M = s->MT = nullptr;
         return CMF_OK;
     }
     const size_t TPNp = (size_t)d.TP * d.Np;
-    if (!h->M) CMFTRY(dalloc_zero(&h->M, TPNp));
-    if (!h->MT) CMFTRY(dalloc_zero(&h->MT, TPNp));
-    return upload_cols(h, mask, 0, d.Tl, true, false, h->M, h->MT);
+    if (!s->M) CMFTRY(dalloc_zero(&s->M, TPNp));
+    if (!s->MT) CMFTRY(dalloc_zero(&s->MT, TPNp));
+    CMFTRY(upload_cols(s, m, 0, d.Tl, true, false, s->M, s->MT));
+    return s->halo_r > 0 ? upload_cols(s, m + (size_t)d.Tl * d.N, d.Tl, s->halo_r, false, false, s->M, s->MT) : CMF_OK;
+}
+
+int cmf_set_mask(cmf_handle h, const double *mask)
+{
+    if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
+    if (cmf_group_s *g = h->group) { // one process: `mask` is the whole N x T matrix; one process per shard: the block of data_local
+        CMFTRY(group_sync(g));
+        for (size_t i = 0; i < g->sh.size(); ++i) {
+            CMFTRY(group_use(g->sh[i]));
+            CMFTRY(shard_set_mask(g->sh[i], mask && g->one_process ? mask + (size_t)g->t0[(size_t)g->rank[i]] * g->sh[i]->d.N : mask));
+        }
+        return CMF_OK;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if (h->sharded) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
+    CMFTRY(mu_set_form(h, h->mu_div, h->mu_beta, MU_MASK_RELEASE)); // (the one mask of the handle now belongs to the PGD entries: the MU entries are unmasked again)
+    if (!mask) HIPCHK(hipStreamSynchronize(h->stream)); // (before the free)
+    return shard_set_mask(h, mask);
 }
 
 int cmf_pgd_reset(cmf_handle h)
@@ -1985,11 +1998,11 @@ int cmf_pgd_update_motifs(cmf_handle h, double pen_sq, double pen_abs, int nonne
 {
     if (h && h->group) {
         CMFTRY(group_check_ready(h->group));
-        return group_pgd_w(h, h->group, pen_sq, pen_abs, nonneg);
+        return pgd_w_phase(h, h->group, pen_sq, pen_abs, nonneg);
     }
     CMFTRY(check_ready(h, true));
     CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "PGD"}));
-    return pgd_w_impl(h, pen_sq, pen_abs, nonneg);
+    return pgd_w_phase(h, nullptr, pen_sq, pen_abs, nonneg);
 }
 
 static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_abs, int nonneg, double *loss)
@@ -1998,11 +2011,11 @@ static int pgd_update_feature_maps_body(cmf_handle h, double pen_sq, double pen_
     if (h && h->group) {
         CMFTRY(group_check_ready(h->group));
         CMFTRY(wb_group_post(h)); // (an armed write-back: the helpers wait for every shard's copy of its block of H)
-        return group_pgd_h(h, h->group, pen_sq, pen_abs, nonneg, loss);
+        return pgd_h_phase(h, h->group, pen_sq, pen_abs, nonneg, loss);
     }
     CMFTRY(check_ready(h, true));
     CMFTRY(mu_ask(h, MuAsk{MU_ASK_SQUARE_RULE, 0, 0.0, 0, "PGD"}));
-    return pgd_h_impl(h, pen_sq, pen_abs, nonneg, loss);
+    return pgd_h_phase(h, nullptr, pen_sq, pen_abs, nonneg, loss);
 }
 
 int cmf_pgd_update_feature_maps(cmf_handle h, double pen_sq, double pen_abs, int nonneg, double *loss)

@@ -1,4 +1,4 @@
-// cmf_groups.hip -- T-sharded groups behind the C ABI: transports, the sharded MU / PGD iteration, group construction.
+// cmf_groups.hip -- T-sharded groups behind the C ABI: transports, the sharded MU iteration, group construction, what the PGD rule does between shards.
 #include "cmf_internal.h"
 
 int rccl_load()
@@ -665,7 +665,7 @@ static void build_exchange_halos(cmf_group_s *g, StepList &st)
         return CMF_OK;
     });
 }
-static int group_exchange_halos(cmf_group_s *g)
+int group_exchange_halos(cmf_group_s *g)
 {
     StepList st;
     build_exchange_halos(g, st);
@@ -1307,16 +1307,11 @@ int cmf_shard_bounds(cmf_handle h, int rank, int64_t *t0, int64_t *t1)
     return CMF_OK;
 }
 
-// ---- PGD on T-sharded groups (pgd.jl:158-255 with data / est / H cut along T, W replicated) ------------------------------
-// compute_gradW! (pgd.jl:206-214) is the C2 contraction: every shard contracts its own residual columns and ONE all-reduce
-// sums the K x N x L partial gradients; the penalty, norm(grad) and the step are then identical replicated arithmetic.
-// compute_gradH! (:218-221) is tensor_transconv! on the shard's columns plus its right residual halo (the conv covers
-// Tl + halo_r columns, as in the MU rule); norm(gradH)^2, the per-component norms of UnitNormConstraint and the loss are
-// sums over shards, combined in rank order on the host (exact: doubles travel as two 32-bit words).  The step-size state
-// machine (stepW, stepH, cur_loss; :139-154, :248-253) is replicated: every rank takes the same decisions from the same sums.
+// ---- what the PGD rule (pgd_w_phase / pgd_h_phase, cmf_rules.hip) does between the shards of a group ------------------------------
+// The sums over shards are combined in rank order on the host (exact: doubles travel as two 32-bit words).
 
 // n doubles at device address ptr[i] of every local shard -> their sum over ALL ranks (rank order), written back to every shard
-static int group_sum_doubles(cmf_group_s *g, const std::vector<double *> &ptr, int n, std::vector<double> *host_out = nullptr)
+int group_sum_doubles(cmf_group_s *g, const std::vector<double *> &ptr, int n, std::vector<double> *host_out)
 {
     const size_t nl = g->sh.size();
     std::vector<std::vector<double>> local(nl, std::vector<double>((size_t)n));
@@ -1348,171 +1343,13 @@ static int group_sum_doubles(cmf_group_s *g, const std::vector<double *> &ptr, i
     return CMF_OK;
 }
 
-static bool group_masked(const cmf_group_s *g) { return g->sh[0]->M != nullptr; }
-
-// pgd.jl:245-253 on the group: the residual with the new factors on every shard, loss = sum over shards
-static int group_pgd_finish(cmf_handle_s *st, cmf_group_s *g, double *step)
+// group-only preparation of a PGD phase: the shards take the front handle's loss kind, no deferred loss reduction is pending, H's halos are current
+int group_pgd_prepare(cmf_handle_s *st, cmf_group_s *g)
 {
-    std::vector<double *> ptr;
-    for (cmf_handle_s *s : g->sh) {
-        CMFTRY(group_use(s));
-        CMFTRY(resid_and_loss(s, nullptr, group_masked(g), st->pgd_loss_abs != 0));
-        ptr.push_back(s->d_scalar);
-    }
-    std::vector<double> tot;
-    CMFTRY(group_sum_doubles(g, ptr, 1, &tot));
-    const double loss = tot[0];
-    *step *= (loss < st->pgd_cur_loss) ? 1.05 : 0.70;
-    st->pgd_cur_loss = loss;
-    return CMF_OK;
-}
-
-static int group_pgd_prepare(cmf_handle_s *st, cmf_group_s *g, int nonneg)
-{
-    if (nonneg < 0 || nonneg > 2) return fail(CMF_ERR_ARG, "constraint must be 0 (none), 1 (NonnegConstraint) or 2 (UnitNormConstraint)");
     if (g->gram || g->overlap) return fail(CMF_ERR_STATE, "the PGD rule runs on a group with the options gram and allreduce_overlap off");
-    if (st->pgd_cur_loss < 0.0) st->pgd_cur_loss = g->data_norm; // pgd.jl:151 (the norm, not its square)
     for (cmf_handle_s *s : g->sh) {
         s->pgd_loss_abs = st->pgd_loss_abs;
         s->carry = CmfLossCarry{};
     }
-    if (!g->halos_current) CMFTRY(group_exchange_halos(g));
-    return CMF_OK;
+    return g->halos_current ? CMF_OK : group_exchange_halos(g);
 }
-
-int group_pgd_w(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs, int nonneg)
-{
-    GroupInline scope(g);
-    CMFTRY(scope.rc);
-    CMFTRY(group_pgd_prepare(st, g, nonneg));
-    const CmfDims &d0 = g->sh[0]->d;
-    const float gscale = st->pgd_loss_abs ? 1.f : 2.f; // pgd.jl:31-33 vs :42-44
-    const size_t LKN = (size_t)d0.L * d0.K32 * d0.Np;
-    for (cmf_handle_s *s : g->sh) {
-        CMFTRY(group_use(s));
-        CMFTRY(ensure_resid(s, group_masked(g), st->pgd_loss_abs != 0));                                 // pgd.jl:230 on the shard's columns
-        CMFTRY(hxt_contract(s, s->est, s->est, 1, s->numden)); // pgd.jl:206-214, partial over t
-    }
-    CMFTRY(group_allreduce(g, g->red, 0, LKN)); // the one bulk exchange: K x N x L partial gradients
-    for (cmf_handle_s *s : g->sh) {
-        const CmfDims &d = s->d;
-        CMFTRY(group_use(s));
-        dim3 grid(d.Np / 64, d.KB, d.L);
-        const int nblk = (d.Np / 64) * d.KB * d.L;
-        if ((size_t)nblk > n_partial(s)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
-        hipLaunchKernelGGL(pgd_w_grad_kernel, grid, dim3(256), 0, s->stream, s->Wt, s->numden, s->numden + LKN, s->partial,
-                           d.N, d.K, d.Np, d.K32, (float)pen_sq, (float)pen_abs, gscale);                // pgd.jl:231-234 (replicated)
-        KCHK("pgd_w_grad_kernel");
-        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s->stream, s->partial, nblk, s->d_scalar + 1, (double *)nullptr);
-        KCHK("loss_reduce_kernel");
-        hipLaunchKernelGGL(pgd_w_apply_kernel, grid, dim3(256), 0, s->stream, s->Wt, s->Wn, s->numden + LKN, s->d_scalar + 1,
-                           d.N, d.K, d.Np, d.K32, (float)st->pgd_stepW, nonneg == 1);                    // pgd.jl:237-241
-        KCHK("pgd_w_apply_kernel");
-        if (nonneg == 2) CMFTRY(pgd_unit_norm(s, true));                                                 // pgd.jl:100-110 (W is replicated)
-        set_est(s, EST_NONE);
-    }
-    return group_pgd_finish(st, g, &st->pgd_stepW);
-}
-
-int group_pgd_h(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs, int nonneg, double *loss)
-{
-    GroupInline scope(g);
-    CMFTRY(scope.rc);
-    CMFTRY(group_pgd_prepare(st, g, nonneg));
-    const float gscale = st->pgd_loss_abs ? 1.f : 2.f;
-    std::vector<double *> nrm;
-    for (cmf_handle_s *s : g->sh) {
-        const CmfDims &d = s->d;
-        CMFTRY(group_use(s));
-        if (!s->pgd_gradH) CMFTRY(dalloc_zero(&s->pgd_gradH, (size_t)d.Tl * d.K32));
-        // the transposed residual on the shard's columns AND its right lag halo (transconv reads est[:, t .. t+L-1])
-        if (s->est_kind == pgd_est_kind(s->M != nullptr, st->pgd_loss_abs != 0)) {
-            // the shard's own columns are in est already (the conv that closed the W phase): transposed, not convolved again;
-            // the <= L-1 halo columns are formed directly (resid_halo_kernel)
-            hipLaunchKernelGGL(transpose_rows_kernel, dim3(d.Np / 64, (d.Tl + 63) / 64), dim3(256), 0, s->stream, s->est, s->estT, d.Tl, d.Np, d.TP, d.PADL);
-            KCHK("transpose_rows_kernel");
-            if (s->halo_r > 0) {
-                hipLaunchKernelGGL(resid_halo_kernel, dim3(d.Np / 128, s->halo_r), dim3(128), 0, s->stream, s->Wt, s->H, s->XT, s->MT, s->estT,
-                                   d.Tl, d.K, d.L, d.K32, d.Np, d.TP, d.PADL, st->pgd_loss_abs);
-                KCHK("resid_halo_kernel");
-            }
-        } else {
-            s->pgd_loss_abs_now = st->pgd_loss_abs;
-            int rc_conv = s->MT ? launch_conv<CONV_MASKED_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT)
-                                : launch_conv<CONV_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT);
-            s->pgd_loss_abs_now = 0;
-            CMFTRY(rc_conv);
-        }
-        CMFTRY(launch_transconv(s, 1, s->estT));                                                         // pgd.jl:218-221
-        dim3 grid((d.Tl + 63) / 64, d.KB);
-        const int nblk = ((d.Tl + 63) / 64) * d.KB;
-        if ((size_t)nblk > n_partial(s)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
-        hipLaunchKernelGGL(pgd_h_grad_kernel, grid, dim3(256), 0, s->stream, s->H, s->hslabs, s->tc_S1, s->pgd_gradH, s->partial,
-                           d.Tl, d.K, d.K32, d.PADL, (float)pen_sq, (float)pen_abs, gscale);
-        KCHK("pgd_h_grad_kernel");
-        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s->stream, s->partial, nblk, s->d_scalar + 1, (double *)nullptr);
-        KCHK("loss_reduce_kernel");
-        nrm.push_back(s->d_scalar + 1);
-    }
-    CMFTRY(group_sum_doubles(g, nrm, 1)); // norm(gradH)^2 over all shards (pgd.jl:236)
-    std::vector<double *> kn;
-    for (cmf_handle_s *s : g->sh) {
-        const CmfDims &d = s->d;
-        CMFTRY(group_use(s));
-        dim3 grid((d.Tl + 63) / 64, d.KB);
-        hipLaunchKernelGGL(pgd_h_apply_kernel, grid, dim3(256), 0, s->stream, s->H, s->Ht, s->pgd_gradH, s->d_scalar + 1,
-                           d.Tl, d.K, d.K32, d.PADL, d.TP, (float)st->pgd_stepH, nonneg == 1);
-        KCHK("pgd_h_apply_kernel");
-        if (nonneg == 2) { // pgd.jl:100-110: the norm of a component runs over all of T
-            if (!s->pgd_knorm) CMFTRY(dalloc_zero(&s->pgd_knorm, (size_t)d.K32));
-            hipLaunchKernelGGL(pgd_h_knorm_kernel, dim3(d.K), dim3(256), 0, s->stream, s->Ht, s->pgd_knorm, d.Tl, d.TP, d.PADL);
-            KCHK("pgd_h_knorm_kernel");
-            kn.push_back(s->pgd_knorm);
-        }
-        set_est(s, EST_NONE);
-    }
-    if (nonneg == 2) {
-        CMFTRY(group_sum_doubles(g, kn, g->sh[0]->d.K));
-        for (cmf_handle_s *s : g->sh) {
-            const CmfDims &d = s->d;
-            CMFTRY(group_use(s));
-            hipLaunchKernelGGL(pgd_h_kscale_kernel, dim3(1024), dim3(256), 0, s->stream, s->H, s->Ht, s->pgd_knorm, d.Tl, d.K, d.K32, d.TP, d.PADL);
-            KCHK("pgd_h_kscale_kernel");
-        }
-    }
-    for (cmf_handle_s *s : g->sh) { // (an armed write-back: every shard's block of H is final here)
-        CMFTRY(group_use(s));
-        CMFTRY(wb_after_H(s));
-    }
-    CMFTRY(group_exchange_halos(g));
-    CMFTRY(group_pgd_finish(st, g, &st->pgd_stepH));
-    *loss = std::sqrt(st->pgd_cur_loss / (g->data_norm * g->data_norm)); // pgd.jl:201
-    return CMF_OK;
-}
-
-// MaskedLoss on a group: the mask is cut like data -- shard r holds its own columns in both layouts and the right lag halo
-// in the transposed one.  One process: `mask` is the whole N x T matrix; one process per shard: the block of data_local.
-int group_set_mask(cmf_group_s *g, const double *mask)
-{
-    CMFTRY(group_sync(g));
-    for (size_t i = 0; i < g->sh.size(); ++i) {
-        cmf_handle_s *s = g->sh[i];
-        const CmfDims &d = s->d;
-        CMFTRY(group_use(s));
-        set_est(s, EST_NONE);
-        if (!mask) {
-            if (s->M) (void)hipFree(s->M);
-            if (s->MT) (void)hipFree(s->MT);
-            s->M = s->MT = nullptr;
-            continue;
-        }
-        const size_t TPNp = (size_t)d.TP * d.Np;
-        if (!s->M) CMFTRY(dalloc_zero(&s->M, TPNp));
-        if (!s->MT) CMFTRY(dalloc_zero(&s->MT, TPNp));
-        const double *m = g->one_process ? mask + (size_t)g->t0[(size_t)g->rank[i]] * d.N : mask;
-        CMFTRY(upload_cols(s, m, 0, d.Tl, true, false, s->M, s->MT));
-        if (s->halo_r > 0) CMFTRY(upload_cols(s, m + (size_t)d.Tl * d.N, d.Tl, s->halo_r, false, false, s->M, s->MT));
-    }
-    return CMF_OK;
-}
-

@@ -307,8 +307,6 @@ struct cmf_handle_s {
     // PGD rule state (pgd.jl:139-154)
     double pgd_stepW = 5.0, pgd_stepH = 5.0, pgd_cur_loss = -1.0;
     float *pgd_gradH = nullptr;
-    int mask_complement_now = 0; // cmf_masked_loss: the loss-only masked conv being launched sums over mask == 0
-    int pgd_loss_abs_now = 0;  // loss kind of the residual conv being launched (set by resid_and_loss / the PGD H phase)
     int pgd_loss_abs = 0;      // 0 SquareLoss (pgd.jl:29-36), 1 AbsoluteLoss (pgd.jl:41-47)
     double *pgd_knorm = nullptr; // [K32] per-component sums of squares of UnitNormConstraint (pgd.jl:100-110)
     float *M = nullptr, *MT = nullptr; // mask of MaskedLoss (pgd.jl:58-70) in the layouts of X and XT; null = no mask
@@ -649,15 +647,16 @@ int gram_w_finish(cmf_handle_s *h, const float *HH, double l1W, double l2W, cons
                          int tail_n = 0);
 int gram_h_update(cmf_handle_s *h, double l1H, double l2H);
 int gram_h_impl(cmf_handle_s *h, double l1H, double l2H, double *loss);
-int pgd_w_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg);
-int pgd_h_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg, double *loss);
+// the PGD phases over a set of shards: the shards of g, or (g == NULL) the lone handle st
+int pgd_w_phase(cmf_handle_s *st, struct cmf_group_s *g, double pen_sq, double pen_abs, int nonneg);
+int pgd_h_phase(cmf_handle_s *st, struct cmf_group_s *g, double pen_sq, double pen_abs, int nonneg, double *loss);
 int hals_h_impl(cmf_handle_s *h, double l1H, double l2H);
 int hals_h_rerun(cmf_handle_s *h);
 int gram_denom_h(cmf_handle_s *h, float *out);
 int gram_tables(cmf_handle_s *h);
-int group_pgd_w(cmf_handle_s *st, struct cmf_group_s *g, double pen_sq, double pen_abs, int nonneg);
-int group_pgd_h(cmf_handle_s *st, struct cmf_group_s *g, double pen_sq, double pen_abs, int nonneg, double *loss);
-int group_set_mask(struct cmf_group_s *g, const double *mask);
+int group_pgd_prepare(cmf_handle_s *st, struct cmf_group_s *g);
+int group_sum_doubles(struct cmf_group_s *g, const std::vector<double *> &ptr, int n, std::vector<double> *host_out = nullptr);
+int group_exchange_halos(struct cmf_group_s *g);
 size_t n_partial(const cmf_handle_s *h);
 hipError_t stream_acquire(int device, hipStream_t *s);
 void plan(cmf_handle_s *h, int n_cu);
@@ -693,7 +692,6 @@ double wait_timeout_s();
 int ensure_resid(cmf_handle_s *h, bool masked = false, bool loss_abs = false);
 HalsRowParams hals_row_params(cmf_handle_s *h, double l1H, double l2H);
 int hals_persist_launch(cmf_handle_s *h, const HalsRowParams &q, int debug = 0, bool clear_flags = true);
-int pgd_unit_norm(cmf_handle_s *h, bool is_W);
 int rccl_load();
 int group_use(cmf_handle_s *s);
 int group_join(cmf_group_s *g);
@@ -718,12 +716,12 @@ static inline size_t group_tail_off(const cmf_group_s *g) { return (size_t)(g->g
 static size_t group_stop_workers(cmf_group_s *g) { return cmf_pool_stop(g->pool, g->failed); }
 
 // The entries that are not on the MU hot path (PGD, masks, stand-alone timings, ...) enqueue from the calling thread as they
-// always did: inside this scope the workers are idle and every step list runs in line.
+// always did: inside this scope the workers are idle and every step list runs in line.  g == NULL (a lone handle): nothing to hold.
 struct GroupInline {
     cmf_group_s *g;
     int rc;
-    explicit GroupInline(cmf_group_s *g_) : g(g_), rc(group_join(g_)) { ++g->force_inline; }
-    ~GroupInline() { --g->force_inline; }
+    explicit GroupInline(cmf_group_s *g_) : g(g_), rc(g_ ? group_join(g_) : CMF_OK) { if (g) ++g->force_inline; }
+    ~GroupInline() { if (g) --g->force_inline; }
 };
 
 template <typename T>
@@ -803,8 +801,10 @@ static inline ConvTailCut conv_tail_cut(const cmf_handle_s *h, int tiles, int n_
 }
 
 // data == NULL: the handle's data in the layout the mode reads (the masked rules pass Xm / XmT, cmf_masked_loss the raw data)
+// loss_abs: ConvParams::loss_abs of the modes that read it -- the residual modes' loss kind (1 = AbsoluteLoss), the masked loss-only
+// modes' complement (1 = the sum runs over mask == 0)
 template <int MODE>
-static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr)
+static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const float *data = nullptr, int loss_abs = 0)
 {
     ProfScope prof_(h, conv_pgd(MODE) ? PROF_CONV_RESID : conv_base(MODE) == CONV_BASE_STORE ? PROF_CONV : conv_base(MODE) == CONV_BASE_STORE_T ? PROF_CONV_T
                        : conv_base(MODE) == CONV_BASE_LOSS ? PROF_CONV_LOSS : PROF_CONV_LOSS_STORE);
@@ -822,7 +822,7 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
     p.mask = conv_mask_transposed(MODE) ? h->MT : h->M;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store;
     p.N = d.N; // (n blocks that are all padding are skipped)
-    p.loss_abs = conv_loss_abs_is_absolute_loss(MODE) ? h->pgd_loss_abs_now : (conv_loss_abs_is_complement(MODE) ? h->mask_complement_now : 0);
+    p.loss_abs = (conv_loss_abs_is_absolute_loss(MODE) || conv_loss_abs_is_complement(MODE)) ? loss_abs : 0;
     dim3 grid(h->conv_gx, gy), block(256);
     const int gx3 = d.Np / 64, tiles3 = gx3 * ((T_store + 63) / 64);
     if (h->small_k) { // few components: one-wave tiles over the ceil(K/2) live k pairs per lag (conv_small_kernel)

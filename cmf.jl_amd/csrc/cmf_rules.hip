@@ -1,15 +1,13 @@
-// cmf_rules.hip -- the HALS rule (src/algs/hals.jl), the optional Gram form of the MU iteration and the PGD rule (src/algs/pgd.jl) on one handle.
+// cmf_rules.hip -- the HALS rule (src/algs/hals.jl), the optional Gram form of the MU iteration and the PGD rule (src/algs/pgd.jl).
+// HALS and the Gram form run on one handle; a PGD phase runs over a set of shards: a lone handle, or the shards of a T-sharded group.
 #include "cmf_internal.h"
 
 // est := tensor_conv(W,H) - data (the residual hals.jl / pgd.jl carry), with the loss sum in d_scalar[0]
 int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked, bool loss_abs)
 {
     const CmfDims &d = h->d;
-    h->pgd_loss_abs_now = loss_abs ? 1 : 0;
-    int rc = masked ? launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy) // pgd.jl:64-70
-                    : launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy);
-    h->pgd_loss_abs_now = 0;
-    CMFTRY(rc);
+    CMFTRY(masked ? launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy, nullptr, loss_abs) // pgd.jl:64-70
+                  : launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy, nullptr, loss_abs));
     set_est(h, pgd_est_kind(masked, loss_abs));
     return reduce_partials(h, h->partial, h->conv_partials, 0, sumsq);
 }
@@ -649,103 +647,192 @@ int gram_h_impl(cmf_handle_s *h, double l1H, double l2H, double *loss)
 }
 
 // ---- PGD (src/algs/pgd.jl) ---------------------------------------------------------------------
-static int pgd_check(cmf_handle_s *h)
+// Each phase is stated once and runs over a set of shards: the shards of a T-sharded group (data / est / H cut along T, W
+// replicated), or a lone handle, which is a shard with no halo (halo_r = 0, conv_gy_ext == conv_gy).  The step-size state machine
+// (stepW, stepH, cur_loss; pgd.jl:139-154, :248-253) and the loss kind live on the front handle `st`; on a group they are replicated:
+// every rank takes the same decisions from the same sums.
+//   compute_gradW! (pgd.jl:206-214) is the C2 contraction: every shard contracts its own residual columns and ONE all-reduce sums the
+//     K x N x L partial gradients; the penalty, norm(grad) and the step are then identical replicated arithmetic.
+//   compute_gradH! (:218-221) is tensor_transconv! on the shard's columns plus its right residual halo (the conv covers Tl + halo_r
+//     columns, as in the MU rule); norm(gradH)^2, the per-component norms of UnitNormConstraint and the loss are sums over shards.
+// What happens between shards is PgdShards: nothing on a lone handle (the sums stay on the device, the loss is read through
+// reduce_partials' pinned word), the group's collectives otherwise (a group of one shard included).
+struct PgdShards {
+    cmf_handle_s *st;
+    cmf_group_s *g; // NULL: the lone handle st
+    std::vector<cmf_handle_s *> lone{st};
+    const std::vector<cmf_handle_s *> &sh() const { return g ? g->sh : lone; }
+    int use(cmf_handle_s *s) const { return g ? group_use(s) : CMF_OK; }
+    // n doubles at where(s) of every shard -> their sum over all ranks, on every shard (and the first of them in *host)
+    template <typename F>
+    int sum(F where, int n, double *host = nullptr) const
+    {
+        if (!g) return CMF_OK;
+        std::vector<double *> ptr;
+        for (cmf_handle_s *s : g->sh) ptr.push_back(where(s));
+        std::vector<double> tot;
+        CMFTRY(group_sum_doubles(g, ptr, n, &tot));
+        if (host) *host = tot[0];
+        return CMF_OK;
+    }
+};
+
+static int pgd_begin(const PgdShards &p, int nonneg)
 {
-    if (h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
-    if (h->pgd_cur_loss < 0.0) h->pgd_cur_loss = h->data_norm; // pgd.jl:151 (the norm, not its square)
+    cmf_handle_s *st = p.st;
+    if (!p.g && st->sharded && st->T_global != st->d.Tl) return fail(CMF_ERR_STATE, "sharded handle: attach a communicator first (cmf_comm_init_rccl / cmf_comm_init_callbacks)");
+    if (nonneg < 0 || nonneg > 2) return fail(CMF_ERR_ARG, "constraint must be 0 (none), 1 (NonnegConstraint) or 2 (UnitNormConstraint)");
+    if (p.g) CMFTRY(group_pgd_prepare(st, p.g));
+    if (st->pgd_cur_loss < 0.0) st->pgd_cur_loss = p.g ? p.g->data_norm : st->data_norm; // pgd.jl:151 (the norm, not its square)
     return CMF_OK;
 }
 
-// pgd.jl:245-253: est (here the residual) with the new factors, loss = norm(data - est)^2, step adaptation
-static int pgd_finish(cmf_handle_s *h, double *step)
+// pgd.jl:245-253: est (here the residual) with the new factors on every shard, loss = norm(data - est)^2 over all of them, step adaptation
+static int pgd_finish(const PgdShards &p, double *step)
 {
+    cmf_handle_s *st = p.st;
     double loss = 0.0;
-    CMFTRY(resid_and_loss(h, &loss, h->M != nullptr, h->pgd_loss_abs != 0));
-    *step *= (loss < h->pgd_cur_loss) ? 1.05 : 0.70;
-    h->pgd_cur_loss = loss;
+    for (cmf_handle_s *s : p.sh()) {
+        CMFTRY(p.use(s));
+        CMFTRY(resid_and_loss(s, p.g ? nullptr : &loss, p.sh()[0]->M != nullptr, st->pgd_loss_abs != 0));
+    }
+    CMFTRY(p.sum([](cmf_handle_s *s) { return s->d_scalar; }, 1, &loss));
+    *step *= (loss < st->pgd_cur_loss) ? 1.05 : 0.70;
+    st->pgd_cur_loss = loss;
     return CMF_OK;
 }
 
-// UnitNormConstraint (pgd.jl:100-110) on the freshly stepped factor: per-component norms, then the scaling
-int pgd_unit_norm(cmf_handle_s *h, bool is_W)
+// UnitNormConstraint (pgd.jl:100-110) on the freshly stepped factor in two steps, so that a group can sum H's per-component norms
+// (they run over all of T) between them: the sums of squares, then the scaling
+static int pgd_unit_norm_sums(cmf_handle_s *h, bool is_W)
 {
     const CmfDims &d = h->d;
     if (!h->pgd_knorm) CMFTRY(dalloc_zero(&h->pgd_knorm, (size_t)d.K32));
     if (is_W) {
         hipLaunchKernelGGL(pgd_w_knorm_kernel, dim3(d.K), dim3(256), 0, h->stream, h->Wt, h->pgd_knorm, d.N, d.L, d.Np, d.K32);
         KCHK("pgd_w_knorm_kernel");
-        hipLaunchKernelGGL(pgd_w_kscale_kernel, dim3(1024), dim3(256), 0, h->stream, h->Wt, h->Wn, h->pgd_knorm, d.N, d.K, d.L, d.Np, d.K32);
-        KCHK("pgd_w_kscale_kernel");
     } else {
         hipLaunchKernelGGL(pgd_h_knorm_kernel, dim3(d.K), dim3(256), 0, h->stream, h->Ht, h->pgd_knorm, d.Tl, d.TP, d.PADL);
         KCHK("pgd_h_knorm_kernel");
+    }
+    return CMF_OK;
+}
+
+static int pgd_unit_norm_scale(cmf_handle_s *h, bool is_W)
+{
+    const CmfDims &d = h->d;
+    if (is_W) {
+        hipLaunchKernelGGL(pgd_w_kscale_kernel, dim3(1024), dim3(256), 0, h->stream, h->Wt, h->Wn, h->pgd_knorm, d.N, d.K, d.L, d.Np, d.K32);
+        KCHK("pgd_w_kscale_kernel");
+    } else {
         hipLaunchKernelGGL(pgd_h_kscale_kernel, dim3(1024), dim3(256), 0, h->stream, h->H, h->Ht, h->pgd_knorm, d.Tl, d.K, d.K32, d.TP, d.PADL);
         KCHK("pgd_h_kscale_kernel");
     }
     return CMF_OK;
 }
 
-int pgd_w_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg)
+// update_motifs! (pgd.jl:158-177); g == NULL: on the lone handle st
+int pgd_w_phase(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs, int nonneg)
 {
-    const CmfDims &d = h->d;
-    CMFTRY(pgd_check(h));
-    if (nonneg < 0 || nonneg > 2) return fail(CMF_ERR_ARG, "constraint must be 0 (none), 1 (NonnegConstraint) or 2 (UnitNormConstraint)");
-    const float gscale = h->pgd_loss_abs ? 1.f : 2.f; // pgd.jl:31-33 vs :42-44
-    const size_t LKN = (size_t)d.L * d.K32 * d.Np;
-    CMFTRY(ensure_resid(h, h->M != nullptr, h->pgd_loss_abs != 0));                                                            // pgd.jl:230 (:64-67 with a mask)
-    CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden)); // pgd.jl:206-214
-    dim3 grid(d.Np / 64, d.KB, d.L);
-    const int nblk = (d.Np / 64) * d.KB * d.L;
-    if ((size_t)nblk > n_partial(h)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
-    hipLaunchKernelGGL(pgd_w_grad_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->numden, h->numden + LKN, h->partial,
-                       d.N, d.K, d.Np, d.K32, (float)pen_sq, (float)pen_abs, gscale);                    // pgd.jl:231-234
-    KCHK("pgd_w_grad_kernel");
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, nblk, h->d_scalar + 1, (double *)nullptr);
-    KCHK("loss_reduce_kernel");
-    hipLaunchKernelGGL(pgd_w_apply_kernel, grid, dim3(256), 0, h->stream, h->Wt, h->Wn, h->numden + LKN, h->d_scalar + 1,
-                       d.N, d.K, d.Np, d.K32, (float)h->pgd_stepW, nonneg == 1);                         // pgd.jl:237-241
-    KCHK("pgd_w_apply_kernel");
-    if (nonneg == 2) CMFTRY(pgd_unit_norm(h, true));                                                     // pgd.jl:100-110
-    set_est(h, EST_NONE);
-    return pgd_finish(h, &h->pgd_stepW);
+    GroupInline scope(g);
+    CMFTRY(scope.rc);
+    const PgdShards p{st, g};
+    CMFTRY(pgd_begin(p, nonneg));
+    const bool masked = p.sh()[0]->M != nullptr, loss_abs = st->pgd_loss_abs != 0;
+    const float gscale = loss_abs ? 1.f : 2.f; // pgd.jl:31-33 vs :42-44
+    const CmfDims &d0 = p.sh()[0]->d;
+    const size_t LKN = (size_t)d0.L * d0.K32 * d0.Np;
+    for (cmf_handle_s *s : p.sh()) {
+        CMFTRY(p.use(s));
+        CMFTRY(ensure_resid(s, masked, loss_abs));             // pgd.jl:230 on the shard's columns (:64-67 with a mask)
+        CMFTRY(hxt_contract(s, s->est, s->est, 1, s->numden)); // pgd.jl:206-214, partial over t
+    }
+    if (g) CMFTRY(group_allreduce(g, g->red, 0, LKN)); // the one bulk exchange: K x N x L partial gradients
+    for (cmf_handle_s *s : p.sh()) { // (replicated: W is the same on every shard)
+        const CmfDims &d = s->d;
+        CMFTRY(p.use(s));
+        dim3 grid(d.Np / 64, d.KB, d.L);
+        const int nblk = (d.Np / 64) * d.KB * d.L;
+        if ((size_t)nblk > n_partial(s)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
+        hipLaunchKernelGGL(pgd_w_grad_kernel, grid, dim3(256), 0, s->stream, s->Wt, s->numden, s->numden + LKN, s->partial,
+                           d.N, d.K, d.Np, d.K32, (float)pen_sq, (float)pen_abs, gscale);                // pgd.jl:231-234
+        KCHK("pgd_w_grad_kernel");
+        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s->stream, s->partial, nblk, s->d_scalar + 1, (double *)nullptr);
+        KCHK("loss_reduce_kernel");
+        hipLaunchKernelGGL(pgd_w_apply_kernel, grid, dim3(256), 0, s->stream, s->Wt, s->Wn, s->numden + LKN, s->d_scalar + 1,
+                           d.N, d.K, d.Np, d.K32, (float)st->pgd_stepW, nonneg == 1);                    // pgd.jl:237-241
+        KCHK("pgd_w_apply_kernel");
+        if (nonneg == 2) {                                                                               // pgd.jl:100-110
+            CMFTRY(pgd_unit_norm_sums(s, true));
+            CMFTRY(pgd_unit_norm_scale(s, true));
+        }
+        set_est(s, EST_NONE);
+    }
+    return pgd_finish(p, &st->pgd_stepW);
 }
 
-int pgd_h_impl(cmf_handle_s *h, double pen_sq, double pen_abs, int nonneg, double *loss)
+// update_feature_maps! (pgd.jl:180-202); g == NULL: on the lone handle st
+int pgd_h_phase(cmf_handle_s *st, cmf_group_s *g, double pen_sq, double pen_abs, int nonneg, double *loss)
 {
-    const CmfDims &d = h->d;
-    CMFTRY(pgd_check(h));
-    if (nonneg < 0 || nonneg > 2) return fail(CMF_ERR_ARG, "constraint must be 0 (none), 1 (NonnegConstraint) or 2 (UnitNormConstraint)");
-    const float gscale = h->pgd_loss_abs ? 1.f : 2.f;
-    if (!h->pgd_gradH) CMFTRY(dalloc_zero(&h->pgd_gradH, (size_t)d.Tl * d.K32));
-    if (h->est_kind == pgd_est_kind(h->M != nullptr, h->pgd_loss_abs != 0)) {
-        // est already holds this residual for the resident W, H (stored by the conv that closed the W phase, pgd.jl:245): the
-        // H phase's est of pgd.jl:230 is the same array, only tensor_transconv wants it transposed
-        hipLaunchKernelGGL(transpose_rows_kernel, dim3(d.Np / 64, (d.Tl + 63) / 64), dim3(256), 0, h->stream, h->est, h->estT, d.Tl, d.Np, d.TP, d.PADL);
-        KCHK("transpose_rows_kernel");
-    } else {
-        h->pgd_loss_abs_now = h->pgd_loss_abs;
-        int rc_conv = h->MT ? launch_conv<CONV_MASKED_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT) // (mask .* resid)^T (pgd.jl:64-67)
-                            : launch_conv<CONV_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT); // resid^T (pgd.jl:230), or its sign (pgd.jl:42-44)
-        h->pgd_loss_abs_now = 0;
-        CMFTRY(rc_conv);
+    GroupInline scope(g);
+    CMFTRY(scope.rc);
+    const PgdShards p{st, g};
+    CMFTRY(pgd_begin(p, nonneg));
+    const float gscale = st->pgd_loss_abs ? 1.f : 2.f;
+    for (cmf_handle_s *s : p.sh()) {
+        const CmfDims &d = s->d;
+        CMFTRY(p.use(s));
+        if (!s->pgd_gradH) CMFTRY(dalloc_zero(&s->pgd_gradH, (size_t)d.Tl * d.K32));
+        // the transposed residual on the shard's columns AND its right lag halo (transconv reads est[:, t .. t+L-1])
+        if (s->est_kind == pgd_est_kind(s->M != nullptr, st->pgd_loss_abs != 0)) {
+            // est already holds this residual for the resident W, H (stored by the conv that closed the W phase, pgd.jl:245): the
+            // H phase's est of pgd.jl:230 is the same array, only tensor_transconv wants it transposed, not convolved again;
+            // the <= L-1 halo columns are formed directly (resid_halo_kernel)
+            hipLaunchKernelGGL(transpose_rows_kernel, dim3(d.Np / 64, (d.Tl + 63) / 64), dim3(256), 0, s->stream, s->est, s->estT, d.Tl, d.Np, d.TP, d.PADL);
+            KCHK("transpose_rows_kernel");
+            if (s->halo_r > 0) {
+                hipLaunchKernelGGL(resid_halo_kernel, dim3(d.Np / 128, s->halo_r), dim3(128), 0, s->stream, s->Wt, s->H, s->XT, s->MT, s->estT,
+                                   d.Tl, d.K, d.L, d.K32, d.Np, d.TP, d.PADL, st->pgd_loss_abs);
+                KCHK("resid_halo_kernel");
+            }
+        } else {
+            CMFTRY(s->MT ? launch_conv<CONV_MASKED_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT, st->pgd_loss_abs) // (mask .* resid)^T (pgd.jl:64-67)
+                         : launch_conv<CONV_RESID_T>(s, s->estT, d.Tl + s->halo_r, s->conv_gy_ext, s->XT, st->pgd_loss_abs)); // resid^T (pgd.jl:230), or its sign (pgd.jl:42-44)
+        }
+        CMFTRY(launch_transconv(s, 1, s->estT));                                                         // pgd.jl:218-221
+        const int nblk = ((d.Tl + 63) / 64) * d.KB;
+        if ((size_t)nblk > n_partial(s)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
+        hipLaunchKernelGGL(pgd_h_grad_kernel, dim3((d.Tl + 63) / 64, d.KB), dim3(256), 0, s->stream, s->H, s->hslabs, s->tc_S1, s->pgd_gradH, s->partial,
+                           d.Tl, d.K, d.K32, d.PADL, (float)pen_sq, (float)pen_abs, gscale);
+        KCHK("pgd_h_grad_kernel");
+        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s->stream, s->partial, nblk, s->d_scalar + 1, (double *)nullptr);
+        KCHK("loss_reduce_kernel");
     }
-    CMFTRY(launch_transconv(h, 1, h->estT));                     // pgd.jl:218-221
-    dim3 grid((d.Tl + 63) / 64, d.KB);
-    const int nblk = ((d.Tl + 63) / 64) * d.KB;
-    if ((size_t)nblk > n_partial(h)) return fail(CMF_ERR_UNSUPPORTED, "PGD: partial buffer too small");
-    hipLaunchKernelGGL(pgd_h_grad_kernel, grid, dim3(256), 0, h->stream, h->H, h->hslabs, h->tc_S1, h->pgd_gradH, h->partial,
-                       d.Tl, d.K, d.K32, d.PADL, (float)pen_sq, (float)pen_abs, gscale);
-    KCHK("pgd_h_grad_kernel");
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, h->stream, h->partial, nblk, h->d_scalar + 1, (double *)nullptr);
-    KCHK("loss_reduce_kernel");
-    hipLaunchKernelGGL(pgd_h_apply_kernel, grid, dim3(256), 0, h->stream, h->H, h->Ht, h->pgd_gradH, h->d_scalar + 1,
-                       d.Tl, d.K, d.K32, d.PADL, d.TP, (float)h->pgd_stepH, nonneg == 1);
-    KCHK("pgd_h_apply_kernel");
-    if (nonneg == 2) CMFTRY(pgd_unit_norm(h, false)); // pgd.jl:100-110
-    set_est(h, EST_NONE);
-    CMFTRY(wb_after_H(h));
-    CMFTRY(pgd_finish(h, &h->pgd_stepH));
-    *loss = std::sqrt(h->pgd_cur_loss / (h->data_norm * h->data_norm)); // pgd.jl:201
+    CMFTRY(p.sum([](cmf_handle_s *s) { return s->d_scalar + 1; }, 1)); // norm(gradH)^2 over all shards (pgd.jl:236)
+    for (cmf_handle_s *s : p.sh()) {
+        const CmfDims &d = s->d;
+        CMFTRY(p.use(s));
+        hipLaunchKernelGGL(pgd_h_apply_kernel, dim3((d.Tl + 63) / 64, d.KB), dim3(256), 0, s->stream, s->H, s->Ht, s->pgd_gradH, s->d_scalar + 1,
+                           d.Tl, d.K, d.K32, d.PADL, d.TP, (float)st->pgd_stepH, nonneg == 1);
+        KCHK("pgd_h_apply_kernel");
+        if (nonneg == 2) CMFTRY(pgd_unit_norm_sums(s, false)); // pgd.jl:100-110: the norm of a component runs over all of T
+        set_est(s, EST_NONE);
+    }
+    if (nonneg == 2) {
+        CMFTRY(p.sum([](cmf_handle_s *s) { return s->pgd_knorm; }, p.sh()[0]->d.K));
+        for (cmf_handle_s *s : p.sh()) {
+            CMFTRY(p.use(s));
+            CMFTRY(pgd_unit_norm_scale(s, false));
+        }
+    }
+    for (cmf_handle_s *s : p.sh()) { // (an armed write-back: every shard's block of H is final here)
+        CMFTRY(p.use(s));
+        CMFTRY(wb_after_H(s));
+    }
+    if (g) CMFTRY(group_exchange_halos(g));
+    CMFTRY(pgd_finish(p, &st->pgd_stepH));
+    const double data_norm = g ? g->data_norm : st->data_norm;
+    *loss = std::sqrt(st->pgd_cur_loss / (data_norm * data_norm)); // pgd.jl:201
     return CMF_OK;
 }
 

@@ -117,7 +117,7 @@ class ProtocolShardedGram(ProtocolShardedMultUpdate):
 
 
 class ProtocolShardedPGD(ProtocolShardedMultUpdate):
-    """group_pgd_w / group_pgd_h (pgd.jl:158-255 with T cut into column blocks): one all-reduce of the partial gradW; the
+    """pgd_w_phase / pgd_h_phase on a group (pgd.jl:158-255 with T cut into column blocks): one all-reduce of the partial gradW; the
     squared norm of gradH, the component norms of UnitNormConstraint and the loss are sums over the ranks in rank order; the
     step-size state machine is replicated.  loss: "square" | "abs"; mask: the GLOBAL mask or None."""
 

@@ -48,7 +48,7 @@ def cmf():
 
 def pgd_configs(configs):
     """The configurations of a table row as a PGDUpdate handle takes them.  "gram" and "reuse_est" belong to the MU entries: the PGD
-    entries of a single handle never read them (pgd_w_impl / pgd_h_impl, cmf_rules.hip: est is reused by its kind alone) and a group
+    entries of a single handle never read them (pgd_w_phase / pgd_h_phase, cmf_rules.hip: est is reused by its kind alone) and a group
     refuses the rule under gram (group_pgd_prepare) -- test_options_the_pgd_entries_ignore_or_refuse; they are left out."""
     out = []
     for c in configs:
@@ -193,7 +193,7 @@ def test_exact_pgd_paths(cmf, oracle, N, T, K, L, configs, why):
 
 # No entry leaves est at the residual WITHOUT changing the factors: est_kind becomes a residual kind in resid_and_loss alone, which
 # only the closing step of a half (pgd_finish, the HALS phases) calls, after the factor has moved; cmf_compute_loss is the MU entry and
-# leaves the MU kind.  So the transpose_rows_kernel route of pgd_h_impl always starts from a non-integer factor and has no exact
+# leaves the MU kind.  So the transpose_rows_kernel route of pgd_h_phase always starts from a non-integer factor and has no exact
 # reference.  It is held to the other route instead: after a W half the resident residual is the CONV_RESID / CONV_MASKED_RESID store
 # of (W', H); uploading the very same factors again voids est and sends the H half through CONV_RESID_T / CONV_MASKED_RESID_T.  Both
 # convs form each entry from the same products in the same order (the transposing modes swap the two MFMA operands, cmf_kernels.h), the
@@ -319,7 +319,34 @@ def test_exact_pgd_long_recordings(cmf, oracle, N, T, K, L):
     _done.add(("long", shape))
 
 
-# The paths the PGD entries cannot reach, from pgd_w_impl / pgd_h_impl / group_pgd_* (cmf_rules.hip, cmf_groups.hip) and launch_conv
+@pytest.mark.parametrize("N,T,K,L", [(48, 300, 4, 8), (37, 150, 33, 7)])
+def test_lone_handle_is_a_group_of_one_shard(cmf, N, T, K, L):
+    """A lone PGDUpdate and PGDUpdate(devices=[0]) run the same per-shard code (pgd_w_phase / pgd_h_phase, cmf_rules.hip); between the
+    shards a one-rank all-reduce sums one buffer and group_sum_doubles one double.  From the same non-integer data and factors they give
+    W, H, steps and every loss bit for bit equal over three iterations."""
+    data = cmf.gen_synthetic(N=N, T=T, K=3, L=L, seed=1234 + N)
+    W0, H0 = cmf.init_rand(data, L=L, K=K, seed=T)
+    masked = cmf.MaskedLoss(cmf.SquareLoss(), cmf.holdout_mask(N, T, frac=0.2, block=L, seed=K))
+    for loss_func, constr in ((cmf.SquareLoss(), cmf.NonnegConstraint), (cmf.AbsoluteLoss(), cmf.UnitNormConstraint), (masked, None)):
+        got = []
+        for devices in (None, [0]):
+            rule = cmf.PGDUpdate(data, W0, H0, devices=devices)
+            try:
+                trace = []
+                for _ in range(3):
+                    rule.update_motifs(loss_func=loss_func, constrW=constr)
+                    trace.append(rule.steps)
+                    trace.append((rule.update_feature_maps(loss_func=loss_func, constrH=constr), rule.steps))
+                got.append(rule.download() + (trace,))
+            finally:
+                rule.close()
+        what = f"{type(loss_func).__name__}, {getattr(constr, '__name__', None)}"
+        check_same(got[1][0], got[0][0], "knl", f"W after three iterations, {what}", {"devices": [0]}, "the lone handle", {})
+        check_same(got[1][1], got[0][1], "kt", f"H after three iterations, {what}", {"devices": [0]}, "the lone handle", {})
+        assert got[1][2] == got[0][2], f"{what}: steps and losses {got[1][2]} on the group, {got[0][2]} on the lone handle"
+
+
+# The paths the PGD entries cannot reach, from pgd_w_phase / pgd_h_phase (cmf_rules.hip: one statement for a lone handle and a group) and launch_conv
 # (cmf_internal.h) -- one reason each.  Everything else of LAUNCH_PATHS must be reached by this file.  (conv_small_kernel:pre, the
 # preloaded data tile of the MU loss + store modes, is no PGD path either -- conv_has_pre -- but compute_loss(), the MU entry these
 # handles call for the loss of the integer factors, launches it: it is neither asked for nor forbidden.)

@@ -3,6 +3,7 @@
 
     python tools/device_code_diff.py <checkout A> <checkout B>
     python tools/device_code_diff.py --kernels-of-a <checkout A> <checkout B>
+    python tools/device_code_diff.py --union <checkout A> <checkout B>
 
 Per csrc/*.hip translation unit: the device-only compile line of tools/kernel_resources.py, clang-offload-bundler
 --unbundle, then `llvm-objdump -d` (without its file-name lines) and `llvm-readelf --notes` of both code objects.  Two
@@ -14,6 +15,12 @@ unit, or the first kernel whose instructions or metadata differ; exits 1 if anyt
 A's disassembly is looked up by name in B's and its instructions compared with the addresses taken out (the symbol's own address
 and the `// address:` column; encodings stay), and every kernel of A's metadata note is compared with B's of the same name.  Prints
 per translation unit how many of A's kernels B holds unchanged and how many it adds; exits 1 if one of A's is missing or differs.
+
+--union: for a checkout B that MOVES launch sites between translation units.  The kernels are `static __global__` in a header, so a unit
+holds the code of exactly the kernels it launches and a moved launch site moves the code with it: the per-unit texts cannot be equal.
+Units whose two texts are equal still print `equal`.  Then, over all units together: every symbol and every kernel note of A, in every
+distinct form it has in A, must be in some unit of B under the same name with the same instructions (addresses taken out as above) and
+the same metadata, and B must name nothing that A does not; exits 1 otherwise.
 """
 import os
 import re
@@ -61,7 +68,10 @@ def by_name(text, split, name_of, strip_addresses):
         name = re.search(name_of, blk).group(1)
         if strip_addresses:
             blk = re.sub(r"(?m)^[0-9a-f]+ (<[^>]+>:)", r"\1", re.sub(r"// [0-9A-Fa-f]+:", "//", blk))
-        out[name] = blk.rstrip()
+        # what follows the LAST block of a text belongs to the file, not to the block: objdump's `...` for the padding behind the last
+        # symbol, the note's closing lines (amdhsa.target, amdhsa.version) behind the last kernel
+        blk = re.sub(r"(?m)^amdhsa\.target:(.|\n)*", "", blk).rstrip()
+        out[name] = re.sub(r"\n\s*\.\.\.$", "", blk).rstrip()
     return out
 
 
@@ -82,6 +92,31 @@ def kernels_of_a(src, da, na, db, nb):
     return not bad
 
 
+def union(texts_a, texts_b):
+    """--union.  texts_*: {translation unit: (disassembly, notes)}.  True when every block of A is in some unit of B and B names nothing new."""
+    ok = True
+    for src in sorted(set(texts_a) | set(texts_b)):
+        a, b = texts_a.get(src), texts_b.get(src)
+        n = [len(re.findall(r"\.agpr_count:", t[1])) if t else 0 for t in (a, b)]
+        print(f"{src}: " + (f"equal ({n[0]} kernels)" if a == b else f"{n[0]} kernels in A, {n[1]} in B: compared in the union"))
+    for what, split, name_of, strip, which in (("instructions", SYMBOL, SYMBOL_NAME, True, 0), ("metadata", NOTE, NOTE_NAME, False, 1)):
+        all_a, all_b = {}, {}
+        for texts, out in ((texts_a, all_a), (texts_b, all_b)):
+            for src, t in texts.items():
+                for name, blk in by_name(t[which], split, name_of, strip).items():
+                    out.setdefault(name, {}).setdefault(blk, src)
+        lost = [(k, src) for k, blks in all_a.items() for blk, src in blks.items() if blk not in all_b.get(k, {})]
+        added = [k for k in all_b if k not in all_a]
+        print(f"union, {what}: {sum(len(v) for v in all_a.values())} distinct blocks under {len(all_a)} names in A, "
+              f"{sum(len(v) for v in all_b.values())} under {len(all_b)} in B; {len(lost)} of A's not in B, {len(added)} names added")
+        for k, src in lost[:20]:
+            print(f"  {what} of {demangle(k)} ({src} of A) {'differ' if k in all_b else 'missing'} in B")
+        for k in added[:20]:
+            print(f"  {what} of {demangle(k)} only in B")
+        ok &= not lost and not added
+    return ok
+
+
 def first_difference(a, b, split, name_of):
     """The name of the first block (of `split`) that differs between the two texts."""
     for x, y in zip(re.split(split, a), re.split(split, b)):
@@ -92,14 +127,17 @@ def first_difference(a, b, split, name_of):
 
 
 if __name__ == "__main__":
-    per_kernel = "--kernels-of-a" in sys.argv
-    if per_kernel:
-        sys.argv.remove("--kernels-of-a")
+    per_kernel, over_all = "--kernels-of-a" in sys.argv, "--union" in sys.argv
+    for flag in ("--kernels-of-a", "--union"):
+        if flag in sys.argv:
+            sys.argv.remove(flag)
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     differ = False
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         ja, jb = start(sys.argv[1], ta), start(sys.argv[2], tb)
+        if over_all:
+            sys.exit(0 if union({s: texts(s, *j) for s, j in ja.items()}, {s: texts(s, *j) for s, j in jb.items()}) else 1)
         for src in sorted(set(ja) | set(jb)):
             if src not in ja or src not in jb:
                 print(f"{src}: only in {sys.argv[1] if src in ja else sys.argv[2]}")
