@@ -17,7 +17,9 @@ The shape table SHAPES is shared with tests/test_gpu_divergence_paths.py, which 
 restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below),
 and with tests/test_gpu_exact_masked_mu.py and tests/test_gpu_exact_pgd.py, which hold the MU rule under a 0/1 mask and the PGD rule to
 their references on it (mu_mask, make_pgd_problem, pgd_half, pgd_preconditions).  The last section holds the HALS sweeps' own table
-(HALS_SHAPES), the mirror of their plan, their element-wise check and the mutations of their restatement (tests/test_gpu_exact_hals.py).
+(HALS_SHAPES), the mirror of their plan, their element-wise check and the mutations of their restatement (tests/test_gpu_exact_hals.py),
+and behind it the MU rule under seqNMF's cross-orthogonality penalties on the shape table (xortho_half, xortho_preconditions,
+xortho_mutations: tests/test_gpu_exact_xortho.py).
 """
 import numpy as np
 
@@ -1279,3 +1281,296 @@ def hals_h_mutations(a):
 
                 out[name] = cross
     return out
+
+
+# ---- seqNMF's cross-orthogonality penalties on the MU rule (tests/test_gpu_exact_xortho.py; CPU half in tests/test_exact_problems.py) ----
+# G = off(S(H)), xW = hxt(G, data), xH = off(S(numH)) and oW = off(Wflat) are sums of non-negative integers on the integer problems, so
+# with data % 4 every one of them stays below 2^24 and is exact in fp32 in any order.  The weights are dyadic: lam x, lam2 o, their sum,
+# den + pen, + l1 and + 2 l2 x are multiples of 1/8 below 2^21, exact in fp32 under any association and any fma contraction.  What is
+# left is cmf_mu's one division and one multiply, so the bar is the 2 ulp of tests/test_exact_parity.py (xortho_preconditions asserts
+# all of this from the arrays, and that one unit of every sum moves its element by at least 4 bars).
+XO_WEIGHTS = (0.125, 0.5, 0.5)  # (lambda, lambda_H, lambda_W)
+XO_XMOD = 4.0                    # data = make_problem's X % 4, as in tests/test_gpu_xortho_mu.py
+XO_FOLD_ROW = (1537, 150, 33, 20)  # L K32 Np / 4 = 20 * 64 * 1664 / 4 = 532 480 > 2048 * 256: xo_fold_w_kernel's grid-stride loop comes round again
+XO_FOLD_GRID = 2048 * 256       # threads of the fold launch (cmf_xortho.hip xo_fold_w)
+XO_ULP_PER_REL = 2.0 ** 23      # a relative change r of a float32 number is at least r 2^23 of its ulp
+
+
+def make_xortho_problem(N, T, K, L, family, seed=0):
+    """make_problem with X % 4."""
+    W, H, X = make_problem(N, T, K, L, family, seed)
+    return W, H, np.asfortranarray(X % XO_XMOD)
+
+
+def xo_smooth(A, L):
+    """xortho_mu_restatement.smooth as 2 L - 1 shifted adds: every element receives its terms in ascending t', the restatement's order,
+    so the two agree bit for bit on any input (tests/test_exact_problems.py)."""
+    K, T = A.shape
+    out = np.zeros((K, T), dtype=A.dtype)
+    for d in range(-(L - 1), L):
+        lo, hi = max(0, -d), min(T, T - d)
+        if lo < hi:
+            out[:, lo:hi] += A[:, lo + d:hi + d]
+    return out
+
+
+def xo_weight_sets(weights=XO_WEIGHTS):
+    """All three weights, then each alone."""
+    lam, lamH, lamW = weights
+    return [weights, (lam, 0.0, 0.0), (0.0, lamH, 0.0), (0.0, 0.0, lamW)]
+
+
+def xortho_half(family, X, W, H, weights=XO_WEIGHTS, corrupt=None):
+    """One update_motifs! (family "W") or update_feature_maps! (family "H") under the penalties in fp64, xortho_mu_restatement's operations
+    with the intermediate arrays kept:
+      both      est, num, den, S (the window sum on its way into off: S(H) on the W side, S(numH) on the H side), G = off(S(H)), pen,
+                den_total = ((((den + pen) + l1) + 2 l2 x) + eps), new
+      "W"       xW = hxt(G, data), Wflat, oW = off(Wflat) over every lag
+      "H"       A (the table the window reads: numH), xH = off(S(A)), SH = S(H), loss (after the update)
+    with L1 and L2 as regularisers.  corrupt(stage, arrays) is called after "sums" (num, den, A), "window" (S), "off" (G on the W side,
+    xH on the H side), "contract" (xW), "G" (the H side's G), "oW" and "weights" (a["weights"] is read after it) to damage them in place."""
+    import xortho_mu_restatement as xr
+
+    K, N, L = W.shape
+    a = dict(W=W, H=H, X=X, family=family, weights=tuple(weights))
+
+    def hook(stage):
+        if corrupt:
+            corrupt(stage, a)
+
+    a["est"] = xr.tensor_conv(W, H)
+    if family == "W":
+        a["num"], a["den"] = xr.hxt(H, X, L), xr.hxt(H, a["est"], L)
+        hook("sums")
+        a["S"] = xo_smooth(H, L)
+        hook("window")
+        a["G"] = xr.off(a["S"])
+        hook("off")
+        a["xW"] = xr.hxt(a["G"], X, L)
+        hook("contract")
+        a["Wflat"] = W.sum(axis=2)
+        a["oW"] = np.repeat(xr.off(a["Wflat"])[:, :, None], L, axis=2)
+        hook("oW")
+    else:
+        a["num"], a["den"] = xr.tensor_transconv(W, X), xr.tensor_transconv(W, a["est"])
+        a["A"] = a["num"].copy()
+        hook("sums")
+        a["S"] = xo_smooth(a["A"], L)
+        hook("window")
+        a["xH"] = xr.off(a["S"])
+        hook("off")
+        a["SH"] = xo_smooth(H, L)
+        a["G"] = xr.off(a["SH"])
+        hook("G")
+    hook("weights")
+    return xortho_finish(a, a["weights"])
+
+
+def xortho_finish(a, weights, loss=True):
+    """pen, den_total, new and (family "H", unless loss=False) loss of xortho_half from its tables under the weights given: a new dict that shares the
+    tables (the weights alone change nothing else)."""
+    import xortho_mu_restatement as xr
+
+    a = dict(a, weights=tuple(weights))
+    lam, lamH, lamW = a["weights"]
+    if a["family"] == "W":
+        a["pen"] = lam * a["xW"] + lamW * a["oW"]
+        x = a["W"]
+    else:
+        a["pen"] = lam * a["xH"] + lamH * a["G"]
+        x = a["H"]
+    a["x"] = x
+    a["den_total"] = (((a["den"] + a["pen"]) + L1) + (2.0 * L2) * x) + EPS
+    a["new"] = np.maximum(x * (a["num"] / a["den_total"]), EPS)
+    if a["family"] == "H" and loss:
+        a["loss"] = xr.compute_loss(a["X"], a["W"], a["new"])
+    return a
+
+
+def _f32_exact(v):
+    return np.array_equal(np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64), v)
+
+
+def xortho_preconditions(a, what=""):
+    """Asserted from the arrays of xortho_half, before any GPU call:
+      * every integer table (num, den, est, G, S, xW / A and xH, oW, Wflat) is integral and below 2^24;
+      * every stage of the denominator -- lam x, lam2 o, their sum, den + pen, + l1, + 2 l2 x, in the kernels' order (xo_fold_w_kernel /
+        xo_off_kernel, then cmf_mu) -- survives the round trip through float32: the stages are then the same numbers under any
+        association or fma contraction of them;
+      * the smallest positive term of each sum (a unit of num, of den, of xW and of oW; a unit of G and one entry of numH in a window),
+        weighted, over the largest den_total (for num: the larger of that and the largest num), is at least 8 ulp = 4 bars.
+    Returns {"ulp": {term: ulp}, "weakest": (term, ulp)}."""
+    family = a["family"]
+    lam, lamH, lamW = a["weights"]
+    tables = ["num", "den", "est", "G", "S"] + (["xW", "oW", "Wflat"] if family == "W" else ["A", "xH", "SH"])
+    for name in tables:
+        t = a[name]
+        assert np.all(t == np.rint(t)) and t.min() >= 0 and t.max() < EXACT, f"{what}: {name} is not an integer table below 2^24 (max {t.max()})"
+    x_tab, o_tab, lam2 = (a["xW"], a["oW"], lamW) if family == "W" else (a["xH"], a["G"], lamH)
+    stages = [("lam x", lam * x_tab), ("lam2 o", lam2 * o_tab)]
+    stages.append(("lam x + lam2 o", stages[0][1] + stages[1][1]))
+    stages.append(("den + pen", a["den"] + stages[2][1]))
+    stages.append(("+ l1", stages[3][1] + L1))
+    stages.append(("+ 2 l2 x", stages[4][1] + (2.0 * L2) * a["x"]))
+    for name, v in stages:
+        assert _f32_exact(v), f"{what}: the denominator stage '{name}' rounds in float32"
+    assert np.array_equal(stages[2][1], a["pen"]) and np.array_equal(stages[5][1] + EPS, a["den_total"])
+    top = float(a["den_total"].max())
+    terms = {"num": 1.0 / max(top, float(a["num"].max())), "den": 1.0 / top}
+    data_unit = float(a["X"][a["X"] > 0].min())
+    if family == "W":
+        if lam > 0:
+            terms["xW"] = lam * data_unit / top  # (a unit of G under the smallest positive data entry)
+        if lamW > 0:
+            terms["oW"] = lamW * float(a["W"][a["W"] > 0].min()) / top
+    else:
+        if lam > 0:
+            terms["numH entry"] = lam * float(a["A"][a["A"] > 0].min()) / top
+        if lamH > 0:
+            terms["G"] = lamH * float(a["H"][a["H"] > 0].min()) / top
+    ulp = {k: v * XO_ULP_PER_REL for k, v in terms.items()}
+    weakest = min(ulp.items(), key=lambda kv: kv[1])
+    assert weakest[1] >= 8.0, f"{what}: {weakest[0]} moves an element by {weakest[1]:.1f} ulp only (8 asked: 4 bars of 2 ulp)"
+    return dict(ulp=ulp, weakest=weakest)
+
+
+def xortho_configs(configs):
+    """The configurations of a table row the penalties accept: no Gram form, one device (both are refused); everything else stays."""
+    return [c for c in configs if "gram" not in c and "devices" not in c]
+
+
+def xo_fold_passes(K32, Np, L):
+    """Grid-stride passes of xo_fold_w_kernel over L K32 Np / 4 float4 lanes."""
+    n4 = L * K32 * Np // 4
+    return -(-n4 // XO_FOLD_GRID)
+
+
+def xo_tail_contraction(left, X, L, t0):
+    """sum over data columns t >= t0 of left[k, t - l] X[n, t]: what the rows behind the last whole ring rotation add to a C2 contraction."""
+    K, T = left.shape
+    out = np.zeros((K, X.shape[0], L))
+    for lag in range(min(L, T)):
+        a = max(t0, lag)
+        if a < T:
+            out[:, :, lag] = left[:, a - lag:T - lag] @ X[:, a:].T
+    return out
+
+
+def xortho_mutations(family, a):
+    """name -> corrupt hook for xortho_half: the local errors the penalties' kernels could make, each at one place.  a: the undamaged
+    half (for the sites).  Absent where the row has no such site (a 32-block of components needs K > 32)."""
+    W, H, X = a["W"], a["H"], a["X"]
+    K, N, L = W.shape
+    T = H.shape[1]
+    src = "H" if family == "W" else "A"  # what the window reads
+    b0 = 64 * ((T // 2) // 64)  # one 64-column block of the window kernel, and its seam
+    b1 = min(b0 + 64, T)
+    seam = b0
+    out = {}
+
+    def on(stage, fn):
+        def corrupt(st, x):
+            if st == stage:
+                fn(x)
+        return corrupt
+
+    if L > 1:
+        def short_lo(x):  # the windows of one block one row short at their lower end
+            lo = max(b0, L - 1)
+            x["S"][:, lo:b1] -= x[src][:, lo - (L - 1):b1 - (L - 1)]
+
+        def short_hi(x):
+            hi = min(b1, T - (L - 1))
+            x["S"][:, b0:hi] -= x[src][:, b0 + L - 1:hi + L - 1]
+
+        def seam_cut(x):  # the columns from the seam on never see the rows in front of it
+            for t in range(seam, min(seam + L - 1, T)):
+                x["S"][:, t] -= x[src][:, max(0, t - (L - 1)):seam].sum(axis=1)
+
+        if max(b0, L - 1) < b1:
+            out["window_short_lo"] = on("window", short_lo)
+        if b0 < min(b1, T - (L - 1)):
+            out["window_short_hi"] = on("window", short_hi)
+        if seam > 0:
+            out["window_seam"] = on("window", seam_cut)
+    out["S_first_column"] = on("window", lambda x: x["S"].__setitem__((slice(None), 0), 0.0))
+    out["S_last_column"] = on("window", lambda x: x["S"].__setitem__((slice(None), T - 1), 0.0))
+    tab = "G" if family == "W" else "xH"
+    c0 = 256 * ((T // 2) // 256)  # one 256-column block of the off kernel
+    cols = slice(c0, min(c0 + 256, T))
+    kmiss = K // 2
+
+    def off_one(x):
+        rows = np.arange(K) != kmiss
+        x[tab][rows, cols] -= x["S"][kmiss, cols]
+
+    def off_self(x):
+        x[tab][:, cols] += x["S"][:, cols]
+
+    if K > 1:
+        out["off_one_component"], out["off_with_itself"] = on("off", off_one), on("off", off_self)
+    if K > 32:
+        def off_block(x):  # the k block past 32 never reaches the components of the first
+            x[tab][:32, cols] -= x["S"][32:, cols].sum(axis=0)
+
+        out["off_one_k_block"] = on("off", off_block)
+    if family == "W":
+        def stale_G(x):  # G of the H before: the same factor one column earlier
+            import xortho_mu_restatement as xr
+
+            x["G"][...] = xr.off(xo_smooth(np.roll(x["H"], 1, axis=1), L))
+
+        def tail_from_H(x):  # the rows behind the last whole ring rotation contracted with H in G's place
+            t0 = T - max(1, T % 30 or 30)
+            x["xW"] += xo_tail_contraction(x["H"], X, L, t0) - xo_tail_contraction(x["G"], X, L, t0)
+
+        out["G_of_the_previous_H"] = on("off", stale_G)
+        out["tail_reads_H"] = on("contract", tail_from_H)
+        if L > 1:
+            out["oW_first_lag_only"] = on("oW", lambda x: x["oW"].__setitem__((slice(None), slice(None), slice(1, None)), 0.0))
+    else:
+        def slab_lost(x):  # one C3 slab -- the units of one 8-row chunk on one 128-column block -- never reaches the window's table
+            import xortho_mu_restatement as xr
+
+            t1 = min(c0 + 128, T)
+            Xc = np.zeros_like(X)
+            Xc[:8, c0:min(t1 + L - 1, T)] = X[:8, c0:min(t1 + L - 1, T)]
+            x["A"][:, c0:t1] -= xr.tensor_transconv(W, Xc)[:, c0:t1]
+
+        def stale_G(x):
+            import xortho_mu_restatement as xr
+
+            x["G"][...] = xr.off(xo_smooth(np.roll(x["H"], 1, axis=1), L))
+
+        def swapped(x):
+            lam, lamH, lamW = x["weights"]
+            x["weights"] = (lamH, lam, lamW)
+
+        out["slab_lost_before_the_window"] = on("sums", slab_lost)
+        out["G_of_the_previous_H"] = on("G", stale_G)
+        out["lambda_and_lambda_H_exchanged"] = on("weights", swapped)
+    return out
+
+
+# The penalised rule under plans for fewer compute units (tests/test_gpu_exact_cu_plans.py).  The penalty contraction is a ONE-source C2
+# launch with G as the left operand, chunked by its own plan (hxt_chunks with nsrc = 1): the count's own tail row (CU_SHAPES) leaves tail
+# rows for the rule's two-source launch, which at 128, 64 and 38 CUs the one-source launch does not -- XO_TAIL_T adds the shortest
+# recordings of 130 units (plus 16 columns: a tail of 17 rows, not of one) whose one-source chunks leave a tail too, the rows
+# CmfHxtTail reads out of G.
+XO_TAIL_T = {128: 1937, 64: 977, 32: 497, 38: 587, 1: 448}
+XO_SLAB_ROW_1CU = (130, 700, 32, 20)  # at 1 CU the only row whose C3 launch writes more than one fragment slab
+
+
+def xo_cu_predicates(N, T, K, L, n_cu):
+    """What the plan mirrors say of the general kernels (K > 16) at n_cu: tail / left_tail -- the two-source / the one-source C2 launch
+    leaves rows to the slab sum (the latter reads them out of G) --, slabs: the fragment slabs xo_h_tables sums with stride 2 Tl K32."""
+    return dict(tail=hxt_chunks(N, T, K, L, 2, n_cu)[2] < T, left_tail=hxt_chunks(N, T, K, L, 1, n_cu)[2] < T, slabs=tc_plan(N, T, K, 2, n_cu)[1])
+
+
+def xo_cu_rows(n_cu):
+    """[(N, T, K, L)]: the count's row that names hxt_kernel:tail, the row of XO_TAIL_T, and a row of more than one C3 slab."""
+    rows = [r[:4] for r in CU_SHAPES[n_cu] if "hxt_kernel:tail" in r[5]]
+    rows.append((130, XO_TAIL_T[n_cu], 32, 20))
+    if not any(xo_cu_predicates(*r, n_cu)["slabs"] > 1 for r in rows):
+        rows.append(XO_SLAB_ROW_1CU)
+    return list(dict.fromkeys(rows))

@@ -876,3 +876,109 @@ def test_two_ulp_check_sees_the_errors_a_replanned_chunking_could_make():
     print(f"tail row lost: {u_tail.max():.0f} ulp on {(u_tail > 2).sum()} elements; chunks one rotation short: {u_short.max():.0f} ulp on {(u_short > 2).sum()} elements")
     assert u_tail.max() > 1000 and (u_tail > 2).sum() >= 0.9 * N  # (row 480's component: its lag-0 entry of every unit whose X there is not 0)
     assert u_short.max() > 1000 and (u_short > 2).mean() > 0.9
+
+
+# ---- seqNMF's cross-orthogonality penalties (tests/test_gpu_exact_xortho.py) ---------------------------------------------------------
+XO_SMALL_ROWS = [(70, 600, 20, 10), (90, 610, 5, 7), (30, 24, 32, 12), (37, 150, 33, 7), (17, 150, 16, 64)]
+XO_ROWS = [s[:4] for s in ep.SHAPES] + [ep.XO_FOLD_ROW]
+# the weakest terms of the table under XO_WEIGHTS, as the arrays give them (a unit of G; a unit of xW; an entry of numH in a window)
+XO_WEAKEST = {((2000, 3000, 32, 20), "H"): ("G", 13), ((2000, 6720, 32, 20), "W"): ("xW", 19), ((70, 600, 20, 40), "H"): ("numH entry", 21),
+              (ep.XO_FOLD_ROW, "H"): ("G", 17)}
+
+
+@pytest.mark.parametrize("shape", XO_SMALL_ROWS, ids=str)
+def test_xortho_half_is_the_restatements(shape):
+    """xortho_half (the operations with the intermediate arrays kept) gives the bits of xortho_mu_restatement's update functions under
+    all three weights and under each alone; the vectorised window sum is the restatement's loop bit for bit, on any input."""
+    import xortho_mu_restatement as xr
+
+    L = shape[3]
+    noise = np.random.default_rng(7).random((shape[2], shape[1]))
+    assert np.array_equal(ep.xo_smooth(noise, L), xr.smooth(noise, L))
+    for family in ("W", "H"):
+        W, H, X = ep.make_xortho_problem(*shape, family)
+        assert set(np.unique(X)) == {0.0, 1.0, 2.0, 3.0}
+        assert np.array_equal(ep.xo_smooth(H, L), xr.smooth(H, L))
+        base = ep.xortho_half(family, X, W, H)
+        for weights in ep.xo_weight_sets():
+            a = ep.xortho_half(family, X, W, H, weights)
+            b = ep.xortho_finish(base, weights)
+            Wr, Hr = W.copy(order="F"), H.copy(order="F")
+            if family == "W":
+                xr.update_motifs(X, Wr, Hr, *weights, l1W=ep.L1, l2W=ep.L2)
+                assert np.array_equal(a["new"], Wr) and np.array_equal(b["new"], Wr), (family, weights)
+            else:
+                loss = xr.update_feature_maps(X, Wr, Hr, *weights, l1H=ep.L1, l2H=ep.L2)
+                assert np.array_equal(a["new"], Hr) and np.array_equal(b["new"], Hr) and a["loss"] == loss == b["loss"], (family, weights)
+        xW, xH, G, oW = xr.terms(X, W, H)
+        if family == "W":
+            assert np.array_equal(base["xW"], xW) and np.array_equal(base["oW"], oW) and np.array_equal(base["G"], G)
+        else:
+            assert np.array_equal(base["xH"], xH) and np.array_equal(base["G"], G)
+
+
+@pytest.mark.parametrize("N,T,K,L", XO_ROWS, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in XO_ROWS])
+def test_xortho_preconditions(N, T, K, L):
+    """Every row of the table and XO_FOLD_ROW, both families, all three weights and each alone, from the arrays generated: every table
+    an integer table below 2^24, every stage of the denominator exact in float32, one unit of every sum at least 8 ulp."""
+    shape = (N, T, K, L)
+    for family in ("W", "H"):
+        W, H, X = ep.make_xortho_problem(N, T, K, L, family)
+        base = ep.xortho_half(family, X, W, H)
+        for weights in ep.xo_weight_sets():
+            a = ep.xortho_finish(base, weights, loss=False)
+            p = ep.xortho_preconditions(a, f"{shape} {family} {weights}")
+            if weights == ep.XO_WEIGHTS:
+                assert float(ep.ulps(a["new"].astype(np.float32), a["new"]).max()) <= 0.5
+                print(f"{shape} {family}: weakest {p['weakest'][0]} {p['weakest'][1]:.1f} ulp; " + ", ".join(f"{k} {v:.0f}" for k, v in p["ulp"].items()))
+                if (shape, family) in XO_WEAKEST:
+                    name, ulp = XO_WEAKEST[(shape, family)]
+                    assert p["weakest"][0] == name and round(p["weakest"][1]) == ulp, (shape, family, p["weakest"])
+
+
+def test_xortho_rows_and_configs():
+    """XO_FOLD_ROW is the only row whose fold launch comes round twice (config 2 itself does not); xortho_configs drops exactly the
+    refused configurations; at every CU count the penalised rows hold a tail the penalty contraction leaves and a C3 launch of more
+    than one slab, and the count's own tail row."""
+    passes = {s[:4]: ep.xo_fold_passes(ep.rup(s[2], 32), ep.rup(s[0], 128), s[3]) for s in ep.SHAPES}
+    assert set(passes.values()) == {1} and ep.xo_fold_passes(32, 2048, 20) == 1
+    N, T, K, L = ep.XO_FOLD_ROW
+    assert ep.xo_fold_passes(ep.rup(K, 32), ep.rup(N, 128), L) == 2 and L * ep.rup(K, 32) * ep.rup(N, 128) // 4 == 532480 > ep.XO_FOLD_GRID == 524288
+    for row in ep.SHAPES:
+        kept = ep.xortho_configs(row[4])
+        assert kept and kept[0] == row[4][0] and all("gram" not in c and "devices" not in c for c in kept)
+        assert [c for c in row[4] if c not in kept] == [c for c in row[4] if "gram" in c or "devices" in c]
+    for n in ep.CU_COUNTS:
+        rows = ep.xo_cu_rows(n)
+        ps = [ep.xo_cu_predicates(*row, n) for row in rows]
+        assert any(p["left_tail"] for p in ps) and any(p["slabs"] > 1 for p in ps) and any(p["tail"] for p in ps), (n, ps)
+        assert [r[:4] for r in ep.CU_SHAPES[n] if "hxt_kernel:tail" in r[5]][0] in rows
+        assert all(K > 16 for _, _, K, _ in rows)
+
+
+XO_MUTATIONS = {"W": {"window_short_lo", "window_short_hi", "window_seam", "S_first_column", "S_last_column", "off_one_component", "off_with_itself",
+                      "G_of_the_previous_H", "tail_reads_H", "oW_first_lag_only"},
+                "H": {"window_short_lo", "window_short_hi", "window_seam", "S_first_column", "S_last_column", "off_one_component", "off_with_itself",
+                      "G_of_the_previous_H", "slab_lost_before_the_window", "lambda_and_lambda_H_exchanged"}}
+
+
+@pytest.mark.parametrize("shape", [(70, 600, 20, 10), (90, 610, 5, 7), (37, 150, 33, 7), (1001, 2500, 32, 20)], ids=str)
+def test_two_ulp_check_flags_the_local_errors_of_the_penalties(shape):
+    """Every mutation of xortho_half -- a window one row short at either end, a lost first or last column of S, a window cut at a
+    64-column seam, a component or a 32-block of components missing from off, off with the component itself, G of the previous H, a C3
+    slab that never reached the window's table, a chunk tail contracted with H in G's place, lambda and lambda_H exchanged, oW at the
+    first lag only -- fails the 2 ulp check at some element by at least four bars.  The Frobenius-relative error beside it is printed
+    and not asserted: what a norm-wise 1e-4 would have made of the same fault."""
+    for family, names in (("W", "knl"), ("H", "kt")):
+        W, H, X = ep.make_xortho_problem(*shape, family)
+        a = ep.xortho_half(family, X, W, H)
+        assert ep.ulps(a["new"].astype(np.float32), a["new"]).max() <= 0.5
+        muts = ep.xortho_mutations(family, a)
+        assert set(muts) == XO_MUTATIONS[family] | ({"off_one_k_block"} if shape[2] > 32 else set()), (family, sorted(muts))
+        for name, corrupt in muts.items():
+            bad = ep.xortho_half(family, X, W, H, corrupt=corrupt)
+            got = bad["new"].astype(np.float32)
+            u = ep.ulps(got, a["new"])
+            print(f"{shape} {family} {name}: {u.max():.0f} ulp at {ep.first_bad(u == u.max(), names)}, {int((u > ULP_BAR).sum())} of {u.size} elements over the bar; "
+                  f"Frobenius-relative {_frob(got, a['new']):.2e}")
+            assert u.max() >= 4 * ULP_BAR, (shape, family, name, u.max())

@@ -21,6 +21,9 @@ run_pgd_config, run_divergence_config, run_spotlight, run_hals_row) with every b
 Counts: 128, 64, 32 (the partition sizes: the whole table exact_problems.CU_SHAPES, which reaches every count-dependent path at each of
 them -- the last test); 1 (the degenerate plan: one chunk, whole tiles only, one piece) and 38 (no multiple of 4: no XCD placement, no
 chase) on the small rows.  The conv families' epilogues (masked MU, PGD, Itakura-Saito, masked KL) run at 32 CUs on one row per tile form.
+The MU rule under seqNMF's cross-orthogonality penalties (run_xortho_config of tests/test_gpu_exact_xortho.py) runs on those rows too, and
+at every count on the rows of exact_problems.xo_cu_rows: the penalty contraction is a one-source C2 launch with G as the left operand,
+chunked by its own plan, whose tail rows the slab sum reads out of G, and its H side sums as many C3 slabs as the count's plan makes.
 HALS (exact_problems.CU_HALS_SHAPES): 2, 3 and 4 pullers by the count, the fall to the stage pipeline at K = 32 on 64 CUs, the chased
 form with 32 CUs beside the pipeline (128 CUs, two pullers; the whole chip leaves 128), and 134 CUs, where every condition of the chase
 holds but the count is no multiple of 8 and the chase must be off.
@@ -41,6 +44,7 @@ import test_gpu_divergence_paths as dv
 import test_gpu_exact_hals as hals
 import test_gpu_exact_masked_mu as mm
 import test_gpu_exact_pgd as pgd
+import test_gpu_exact_xortho as xo
 from exact_problems import CU_COUNTS, CU_EPILOGUE_FORMS, CU_EPILOGUE_N_CU, CU_EPILOGUE_ROWS, CU_FULL, CU_HALS_SHAPES, CU_PATHS, CU_SHAPES, L1, L2, LAUNCH_PATHS
 
 pytestmark = pytest.mark.gpu
@@ -241,6 +245,54 @@ def test_divergence_forms_under_cu_plan(cmf, N, T, K, L, configs, why, form):
             dv.check_same(Hg, base[2], "kt", "H half: H", cfg, base[0], c)
     dv.run_spotlight(planned, N, T, K, L, dict(), form, n_cu=n_cu, record=lambda form, c: None)
     assert planned.handles > 0
+
+
+# ---- the MU rule under seqNMF's cross-orthogonality penalties -----------------------------------------------------------------------
+def xortho_under_plan(cmf, n_cu, shape, configs):
+    """run_xortho_config of tests/test_gpu_exact_xortho.py (all three weights; every bar its own) on handles planned for n_cu CUs, the
+    factors bit-identical to the same configuration on the whole-chip plan.  Returns the launch counters per configuration."""
+    refs = cached("xortho", shape, lambda: xo.xortho_references(shape))
+    planned = Planned(cmf, n_cu)
+    worst = {"W": 0.0, "H": 0.0}
+    out = []
+    for cfg in configs:
+        Wg, Hg, c = xo.run_xortho_config(planned, cfg, refs, record=lambda c: None, worst=worst)
+        if ("xortho", shape, key(cfg)) not in _plain:
+            _plain["xortho", shape, key(cfg)] = xo.run_xortho_config(cmf, cfg, refs, record=lambda c: None, worst=worst)[:2]
+        Wp, Hp = _plain["xortho", shape, key(cfg)]
+        same_as_plain(Wg, Wp, "knl", f"{n_cu} CUs: penalised W half: W", cfg, c)
+        same_as_plain(Hg, Hp, "kt", f"{n_cu} CUs: penalised H half: H", cfg, c)
+        out.append((cfg, c))
+    assert planned.handles > 0
+    print(f"penalised MU {shape} at {n_cu} CUs: worst W {worst['W']:.2f} ulp, H {worst['H']:.2f} ulp")
+    return out
+
+
+@pytest.mark.parametrize("N,T,K,L,configs,why", CU_EPILOGUE_ROWS, ids=EPI_IDS)
+def test_xortho_under_cu_plan(cmf, N, T, K, L, configs, why):
+    """One row per conv tile form and two few-component rows at 32 CUs: the conv forms and the few-component plans the replanned
+    handle takes are those the mirrors predict."""
+    n_cu = CU_EPILOGUE_N_CU
+    for cfg, c in xortho_under_plan(cmf, n_cu, (N, T, K, L), epilogue_configs(configs)):
+        plan = {p: v for p, v in ep.cu_plan(N, T, K, L, cfg, n_cu).items() if p.startswith("conv") or p.startswith("g_gemm") or p == "transconv_kernel:xcd"}
+        check_plan(plan, c, f"penalised MU {(N, T, K, L)} {cfg} at {n_cu} CUs")
+
+
+XO_CU_ROWS = [(n,) + row for n in CU_COUNTS for row in ep.xo_cu_rows(n)]
+
+
+@pytest.mark.parametrize("n_cu,N,T,K,L", XO_CU_ROWS, ids=[f"cu{r[0]}-{r[1]}x{r[2]}x{r[3]}x{r[4]}" for r in XO_CU_ROWS])
+def test_xortho_tails_and_slabs_under_cu_plans(cmf, n_cu, N, T, K, L):
+    """The chunk tails of the penalty contraction read G where the rule's read H (CmfHxtTail's left operand), and xo_h_tables sums as many
+    C3 slabs as the plan of the count makes: at every count the count's own tail row, a row whose ONE-source chunks leave a tail as well,
+    and a row of more than one slab -- which row is which is read off the plan mirrors called with that count."""
+    p = ep.xo_cu_predicates(N, T, K, L, n_cu)
+    for cfg, c in xortho_under_plan(cmf, n_cu, (N, T, K, L), [dict()]):
+        what = f"penalised MU {(N, T, K, L)} at {n_cu} CUs"
+        # both launches run in every W phase: the rule's two-source one and the penalty contraction's one-source one
+        assert c["hxt_kernel:nsrc1"] > 0 and c["hxt_kernel:nsrc2"] > 0, f"{what}: launches {mu.reached(c)}"
+        check_plan({"hxt_kernel:tail": p["tail"] or p["left_tail"], "hxt_kernel:no_tail": not (p["tail"] and p["left_tail"])}, c, what)
+    _done.add(("xortho", n_cu, (N, T, K, L)))
 
 
 # ---- HALS -----------------------------------------------------------------------------------------------------------------------------

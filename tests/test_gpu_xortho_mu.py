@@ -9,6 +9,11 @@ project's bars (tests/test_gpu_parity.py):
 How long a fit is compared: the `admit` lines of profiles/mu_xortho_precision.txt (tools/mu_xortho_precision.py).  Every fixture was
 written at a count its line admits -- `load` checks that -- and no fixture is skipped or held to another bar.  The four denominator
 terms and the three costs are compared EXACTLY on integer-valued problems whose every sum stays below 2^24.
+
+The terms entry reaches xH by another route than the update takes (a one-source C3 contraction and an unweighted off), and the norm-wise
+bars above pass a fault confined to one chunk tail, one window seam or one k block.  tests/test_gpu_exact_xortho.py holds the penalised
+UPDATES themselves to fp64 at 2 ulp per element on every kernel path of the shape table, the fold kernel's second pass, and the state
+around G bitwise; tests/test_gpu_exact_cu_plans.py repeats it under plans for fewer compute units.
 """
 import ctypes
 import os
