@@ -222,6 +222,7 @@ static void destroy_impl(cmf_handle_s *h)
     if (h->kl_denH) (void)hipFree(h->kl_denH);
     if (h->kl_sums) (void)hipFree(h->kl_sums);
     xo_free(h);
+    signif_free(h);
     if (h->est2) (void)hipFree(h->est2);
     if (h->est2T) (void)hipFree(h->est2T);
     for (int v = 0; v < 3; ++v)
@@ -1285,6 +1286,7 @@ int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
     if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
     if (std::strcmp(name, "pow_update_launches") == 0) { *value = h->pow_launches; return CMF_OK; }                          // launches of w_update_pow_kernel / h_update_pow_kernel (the beta form outside 1 < beta <= 2)
     if (std::strcmp(name, "xortho_launches") == 0) { *value = h->xo_launches; return CMF_OK; }                               // launches of the kernels of cmf_xortho.h (0 while the weights of cmf_mu_set_xortho are 0 and no cost / terms entry was called)
+    if (std::strcmp(name, "signif_launches") == 0) { *value = h->signif_launches; return CMF_OK; }                           // launches of the kernels of cmf_signif.h (cmf_null_moments: three per batch of draws)
     if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
     if (sep_counter(h, name, value)) return CMF_OK;                                                      // pivoting rounds of the last NNLS step of the separable fit
     if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
@@ -1368,6 +1370,12 @@ static const FlagOption kFlagOptions[] = {
 int cmf_set_option(cmf_handle h, const char *name, int value)
 {
     if (!h || !name) return fail(CMF_ERR_ARG, "NULL argument");
+    if (std::strcmp(name, "signif_batch") == 0) { // draws per batch of cmf_null_moments (0: the default); the result does not depend on it
+        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "signif_batch: cmf_null_moments runs on single-GPU handles only");
+        if (value < 0) return fail(CMF_ERR_ARG, "signif_batch must be at least 0");
+        h->signif_batch = value;
+        return CMF_OK;
+    }
     for (const FlagOption &o : kFlagOptions) {
         if (std::strcmp(name, o.name) != 0) continue;
         if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "%s: %s on single-GPU handles only", name, o.who);
@@ -2463,6 +2471,7 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
     const double S = (double)d.L * d.Tl - 0.5 * (double)d.L * (d.L - 1);
     const double f1 = 2.0 * d.K * d.N * S; // one contraction
     std::string nm(name);
+    if (nm == "signif_draw" || nm == "transconv1_sum") return signif_time(h, nm == "signif_draw", reps, avg_ms, flops); // cmf_signif.hip
     if (nm == "pair_conv_tc" || nm == "seq_conv_tc" || nm == "pair_loss_hxt" || nm == "seq_loss_hxt") {
         // Experiment: two INDEPENDENT contractions of an iteration -- conv_t and numH = transconv(W, data),
         // or the loss conv and numW = hxt(data) -- on two streams at once ("pair_") against one after the other ("seq_"):

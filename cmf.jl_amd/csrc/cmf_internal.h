@@ -379,6 +379,11 @@ struct cmf_handle_s {
     double xo_lam[3] = {0.0, 0.0, 0.0};
     struct XoState *xo = nullptr;
     int64_t xo_launches = 0;
+    // seqNMF's significance test on held-out data (cmf_null_moments; cmf_signif.hip): its scratch (allocated on first use), the draws per
+    // batch (cmf_set_option "signif_batch"; 0: the default of cmf_signif.h) and the launches of its kernels (cmf_get_counter "signif_launches")
+    struct SignifState *signif = nullptr;
+    int signif_batch = 0;
+    int64_t signif_launches = 0;
 };
 static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
 // the refusals of cmf_mu_install.h asked of this handle: CMF_OK, or the code with its text as the thread's last error
@@ -396,6 +401,10 @@ void xo_free(cmf_handle_s *h);
 int xo_fold_w(cmf_handle_s *h);
 void xo_after_w(cmf_handle_s *h);
 int xo_h_tables(cmf_handle_s *h, int nslabs, size_t stride, int num_pos, int den_pos, const float **num, const float **den);
+// cmf_signif.hip: frees the scratch of cmf_null_moments (destroy_impl); the timing pair of cmf_time_kernel ("signif_draw": one batch of null
+// draws, per draw; "transconv1_sum": the rule's one-source C3 contraction plus its slab sum)
+void signif_free(cmf_handle_s *h);
+int signif_time(cmf_handle_s *h, bool draws, int reps, double *avg_ms, double *flops);
 
 // cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)
 void admm_free(cmf_handle_s *h);

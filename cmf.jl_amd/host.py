@@ -422,6 +422,17 @@ class MultUpdate(AbstractCFUpdate):
         check(self._lib.cmf_mu_xortho_terms(self._h, ptr(xW), ptr(xH), ptr(oH), ptr(oW)))
         return xW, xH, oH, oW
 
+    # -- seqNMF's significance test on held-out data (cmf_null_moments) ------------------------
+    def null_moments(self, seed, first_draw, n_draws):
+        """The raw power sums of the overlaps of the null motifs of the resident W with the rule's data, a (3, K, n_draws) array:
+        ``[:, k, j]`` = (sum v, sum v^2, sum v^3) over the columns, v = tensor_transconv(Wnull_d, data)[k, :] of draw
+        d = first_draw + j, whose motif rows are circularly shifted by ``null_shifts``; draw 0 is the resident W itself.
+        Changes nothing the rule calls read (cmf_null_moments)."""
+        n_draws = int(n_draws)
+        sums = np.zeros((3, self.K, max(n_draws, 0)), order="F")
+        check(self._lib.cmf_null_moments(self._h, int(seed) & (2**64 - 1), int(first_draw), n_draws, ptr(sums)))
+        return sums
+
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
         """update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing): src/algs/mult.jl:23-39."""
@@ -1708,6 +1719,100 @@ def evaluate_xortho(r, device=None):
         return rule.xortho_cost()
     finally:
         rule.close()
+
+
+def null_shifts(seed, draws, K, N, L):
+    """The circular shifts of seqNMF's null motifs (cmf_null_shifts): an integer (N, K, len(draws)) array, ``[n, k, j]`` the number
+    of lags row (k, n) of the motif is rotated by in draw ``draws[j]``.  Draw 0 is the identity; every other entry is a pure
+    function of (seed, draw, k, n) in [0, L).  ``draws``: an int (draws 0 .. draws - 1) or a sequence of draw numbers.  No device."""
+    lib = _lib.load()
+    ds = np.arange(int(draws), dtype=np.int64) if np.isscalar(draws) else np.asarray(list(draws), dtype=np.int64)
+    out = np.zeros((int(N), int(K), len(ds)), dtype=np.int32, order="F")
+    p32 = ctypes.POINTER(ctypes.c_int32)
+    consecutive = len(ds) > 0 and bool(np.all(np.diff(ds) == 1))
+    if consecutive:
+        check(lib.cmf_null_shifts(int(seed) & (2**64 - 1), int(ds[0]), len(ds), int(K), int(N), int(L), out.ctypes.data_as(p32)))
+        return out
+    for j, d in enumerate(ds):
+        one = np.zeros((int(N), int(K), 1), dtype=np.int32, order="F")
+        check(lib.cmf_null_shifts(int(seed) & (2**64 - 1), int(d), 1, int(K), int(N), int(L), one.ctypes.data_as(p32)))
+        out[:, :, j] = one[:, :, 0]
+    return out
+
+
+class SignificanceResult:
+    """What ``evaluate_significance`` returns: ``pvals`` (K; inf for an excluded component), ``is_significant`` (K booleans),
+    ``skew`` (K: the skewness of each component's own overlap), ``skewnull`` (K x nnull) and ``excluded`` (K booleans)."""
+
+    def __init__(self, pvals, is_significant, skew, skewnull, excluded, p, nnull):
+        self.pvals, self.is_significant, self.skew, self.skewnull, self.excluded = pvals, is_significant, skew, skewnull, excluded
+        self.p, self.nnull = p, nnull
+
+    def __repr__(self):
+        return f"SignificanceResult(pvals={self.pvals!r}, is_significant={self.is_significant!r})"
+
+
+def _skew_from_sums(sums, T):
+    """MATLAB's biased skewness(., 1, 2) from the raw power sums (S1, S2, S3) along axis 0 over T samples; m2 <= 0 gives NaN."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mu = sums[0] / T
+        m2 = sums[1] / T - mu * mu
+        m3 = sums[2] / T - 3.0 * mu * (sums[1] / T) + 2.0 * mu * mu * mu
+        return np.where(m2 > 0.0, m3 / np.where(m2 > 0.0, m2, 1.0) ** 1.5, np.nan), m2
+
+
+def significance_from_sums(W, sums, T, p=0.05):
+    """The host half of seqNMF's test: ``sums`` is the (3, K, 1 + nnull) array of ``MultUpdate.null_moments(seed, 0, 1 + nnull)``
+    for the K x N x L motifs ``W`` on ``T`` held-out columns.  Excluded before counting (pval = inf): components whose every entry
+    is at or below the MU floor eps(Float64); components with one unit carrying the motif (max_n Wflat^2 > 0.999 sum_n Wflat^2);
+    and -- a deviation from seqNMF, where MATLAB's NaN would count as significant -- components whose own overlap has no variance.
+    pval = (1 + #{null skewness > own}) / nnull (a NaN null compares false); significant where pval <= p / K_kept."""
+    W = np.asarray(W, dtype=np.float64)
+    K = W.shape[0]
+    nnull = sums.shape[2] - 1
+    if nnull < 1:
+        raise ValueError("at least one null draw is needed")
+    sk, m2 = _skew_from_sums(np.asarray(sums, dtype=np.float64), float(T))
+    skew, skewnull = sk[:, 0].copy(), sk[:, 1:].copy()
+    wflat2 = W.sum(axis=2) ** 2
+    excluded = (W.reshape(K, -1).max(axis=1) <= EPSILON) | (wflat2.max(axis=1) > 0.999 * wflat2.sum(axis=1)) | ~(m2[:, 0] > 0.0)
+    kept = int(K - excluded.sum())
+    pvals = np.full(K, np.inf)
+    counts = (skewnull > skew[:, None]).sum(axis=1)
+    pvals[~excluded] = (1.0 + counts[~excluded]) / nnull
+    is_sig = np.zeros(K, dtype=bool)
+    if kept:
+        is_sig[~excluded] = pvals[~excluded] <= p / kept
+    return SignificanceResult(pvals, is_sig, skew, skewnull, excluded, p, nnull)
+
+
+def evaluate_significance(r_or_W, test, p=0.05, nnull=None, seed=0, device=None, options=None):
+    """seqNMF's test_significance on held-out data: which of the K motifs of a fitted model (a ``CNMF_results`` or a K x N x L array)
+    are sequences?  For each component the skewness of its overlap with ``test`` (N x T'), tensor_transconv(W, test)[k, :], is
+    compared with the skewness under ``nnull`` null motifs whose rows are circularly shifted along the lag axis, each
+    (component, unit) by a random amount of its own (``null_shifts``); default nnull = 2 ceil(K / p).  Returns a
+    ``SignificanceResult``.  The overlap drops terms beyond the last column (common.jl:71-81) where seqNMF's helper wraps around;
+    the two agree on ``test`` followed by L zero columns.  ``options``: library options of the handle, e.g. {"signif_batch": 8}."""
+    W = farr(r_or_W.W if hasattr(r_or_W, "W") else r_or_W)
+    if W.ndim != 3:
+        raise ValueError("W must be a K x N x L tensor")
+    test = farr(test)
+    K = W.shape[0]
+    if test.ndim != 2 or test.shape[0] != W.shape[1]:
+        raise ValueError(f"test must be N x T' with N={W.shape[1]}, got {test.shape}")
+    if not (0.0 < p <= 1.0):
+        raise ValueError("p must lie in (0, 1]")
+    nnull = 2 * int(math.ceil(K / p)) if nnull is None else int(nnull)
+    if nnull < 1:
+        raise ValueError("nnull must be at least 1")
+    rule = MultUpdate(test, W, np.zeros((K, test.shape[1]), order="F"), device=device)
+    try:
+        for name, value in (options or {}).items():
+            rule.set_option(name, value)
+        sums = rule.null_moments(seed, 0, 1 + nnull)
+    finally:
+        rule.close()
+    return significance_from_sums(W, sums, test.shape[1], p=p)
 
 
 def xortho_sweep(data, lambdas, L, K, **fit_kw):

@@ -223,6 +223,18 @@ function xortho_terms(rule::HIPMultUpdate, K::Integer, N::Integer, L::Integer, T
     return xW, xH, oH, oW
 end
 
+# null_moments(rule, K, seed, first_draw, n_draws) -> a 3 x K x n_draws array: seqNMF's significance test on held-out data
+# (test_significance.m; cmf_null_moments).  The rule's data are the held-out columns; draw d >= 1 shifts row (k, n) of the resident W
+# circularly along the lag axis by s(d, k, n) (cmf_null_shifts; draw 0 is W itself), and [:, k, j] holds sum v, sum v^2, sum v^3 over t of
+# v = tensor_transconv(Wnull_d, data)[k, :] (common.jl:71-81) for d = first_draw + j - 1.  The skewness of each column of sums,
+# m3 / m2^1.5 with mu = S1/T, m2 = S2/T - mu^2, m3 = S3/T - 3 mu S2/T + 2 mu^3, compared between draw 0 and the others gives the
+# p-values.  Changes nothing the rule calls read.  One GPU; no mask.
+function null_moments(rule::HIPMultUpdate, K::Integer, seed::Integer, first_draw::Integer, n_draws::Integer)
+    sums = zeros(Float64, 3, K, n_draws)
+    check(ccall((:cmf_null_moments, LIBCMF), Cint, (Ptr{Cvoid}, UInt64, Int64, Int64, Ptr{Float64}), rule.handle, UInt64(seed), Int64(first_draw), Int64(n_draws), sums))
+    return sums
+end
+
 # update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
 function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)
     select_mask!(rule, mask)

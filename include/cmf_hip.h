@@ -71,7 +71,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_signif.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, cmf_signif.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -557,6 +557,29 @@ int cmf_mu_xortho_cost(cmf_handle h, double *xortho, double *ortho_H, double *or
  * shape of H (K x T), Julia memory order.  Any pointer may be NULL.  They show which component pairs the penalty acts on (what
  * mult.jl:37 and :51 get added to their denominators is lambda xW + lambda_W oW and lambda xH + lambda_H oH).  Single-GPU handles only. */
 int cmf_mu_xortho_terms(cmf_handle h, double *xW, double *xH, double *oH, double *oW);
+/* ---- seqNMF's significance test of components on held-out data (test_significance.m) ----
+ * The test asks of each component k whether the overlap of its motif with held-out data, tensor_transconv(W, X)[k, :] (common.jl:71-81),
+ * is more right-skewed than the overlaps of null motifs, whose rows are circularly shifted along the lag axis (seqNMF's
+ * circshift(W(n, k, :), s)) by an amount of their own per (draw, component, unit):  draw 0 is the identity, and for d >= 1
+ *   s(d, k, n) = ((bits(base(seed, 0x5157), ((d - 1) K + k) N + n) >> 32) * L) >> 32     in 64-bit integer arithmetic,
+ * base and bits those of the library's counter generator (the one of cmf_init_rand / cmf_gen_synthetic: model.jl:113-125).
+ * cmf_null_shifts writes that table for draws first_draw ... first_draw + n_draws - 1 as an (N, K, n_draws) array, n fastest.  Host only:
+ * no device, no handle.  CMF_ERR_ARG: shifts NULL, n_draws < 1, first_draw < 0, K, N or L < 1, L > 4096. */
+int cmf_null_shifts(uint64_t seed, int64_t first_draw, int64_t n_draws, int64_t K, int64_t N, int64_t L, int32_t *shifts);
+/* The raw power sums of the overlaps of the null motifs of the handle's resident W with the handle's raw data (the held-out columns the
+ * handle was created from):  with Wnull_d[k, n, l] = W[k, n, (l - s(d, k, n)) mod L] and v_d = tensor_transconv(Wnull_d, data)
+ * (common.jl:71-81: terms with t + l > T are dropped; seqNMF's helper wraps circularly instead, which is the same on data followed by L
+ * zero columns),  sums[0..2, k, j] = sum_t v, sum_t v^2, sum_t v^3 of draw first_draw + j, a (3, K, n_draws) column-major array of
+ * doubles.  v is the fp32 contraction, widened to fp64 before it is squared and cubed; the sums are fp64 in a fixed order, so a draw's
+ * result is a function of (W, data, seed, d) alone: bitwise the same whatever the batch size (cmf_set_option "signif_batch": draws per
+ * batch, not listed by cmf_option_names; 0 = the default, the smallest multiple of 32 / gcd(K, 32) draws that fills 8 column blocks of
+ * 32), however a range of draws is cut into calls, and whatever CU count the handle is planned for.  The skewness, the p-values and the
+ * decision are host arithmetic on these sums (host.py: evaluate_significance).  The call reads the data and W and writes scratch of
+ * its own (allocated on first use): est, a speculated contraction, a deferred loss, the slabs and the penalties' tables stay as they
+ * are, and a fit continued after it gives the bits it gives without it.  cmf_get_counter "signif_launches" counts its kernels' launches.
+ * CMF_ERR_ARG: NULL pointers, n_draws < 1, first_draw < 0.  CMF_ERR_STATE: factors not set; a mask installed (cmf_mu_set_mask /
+ * cmf_set_mask: held-out entries of the data may hold NaN).  CMF_ERR_UNSUPPORTED: group and shard handles.  All before any device work. */
+int cmf_null_moments(cmf_handle h, uint64_t seed, int64_t first_draw, int64_t n_draws, double *sums);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
@@ -754,7 +777,8 @@ int cmf_gen_synthetic(int device, int64_t N, int64_t T, int64_t K, int64_t L,
 /* ---- measurement hooks (bench.py) ------------------------------------------
  * Times `reps` launches of one named hot kernel with HIP events on the
  * handle's stream and returns the average duration in milliseconds plus the
- * algorithmic flop count of one launch.  name: "conv", "conv_t", "conv_loss", "conv_loss_store", "hxt", "transconv".
+ * algorithmic flop count of one launch.  name: "conv", "conv_t", "conv_loss", "conv_loss_store", "hxt", "transconv";
+ * "signif_draw" (one default batch of cmf_null_moments, per DRAW) and "transconv1_sum" (the one-source transconv plus its slab sum).
  * On a group handle "allreduce" times the group's bulk exchange alone (the buffer an iteration all-reduces); it is a
  * collective -- every rank of the group makes the call -- and *flops receives the payload in bytes. */
 int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, double *flops);
