@@ -1273,59 +1273,6 @@ int cmf_rccl_version(int *version, char *path, int64_t path_len)
     return CMF_OK;
 }
 
-int cmf_get_counter(cmf_handle h, const char *name, int64_t *value)
-{
-    if (!h || !name || !value) return fail(CMF_ERR_ARG, "NULL argument");
-    if (std::strcmp(name, "hals_pipeline_reruns") == 0) { *value = h->hals_reruns; return CMF_OK; }
-    if (std::strcmp(name, "plan:n_cu") == 0) { // the CU count the plan was dealt for (a group: its shards')
-        *value = (h->root_only && h->group && !h->group->sh.empty()) ? h->group->sh[0]->n_cu : h->n_cu;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "writeback_calls") == 0) { *value = h->wb ? h->wb->armed_calls : 0; return CMF_OK; }            // cmf_arm_writeback calls
-    if (std::strcmp(name, "speculated_contractions") == 0) { *value = h->spec_hits; return CMF_OK; }                         // update_motifs! calls whose C2 contraction was already enqueued
-    if (std::strcmp(name, "liveness_checks") == 0) { *value = g_liveness_checks.load(); return CMF_OK; } // (process-wide) stream queries made while waiting for a loss
-    if (std::strcmp(name, "pow_update_launches") == 0) { *value = h->pow_launches; return CMF_OK; }                          // launches of w_update_pow_kernel / h_update_pow_kernel (the beta form outside 1 < beta <= 2)
-    if (std::strcmp(name, "xortho_launches") == 0) { *value = h->xo_launches; return CMF_OK; }                               // launches of the kernels of cmf_xortho.h (0 while the weights of cmf_mu_set_xortho are 0 and no cost / terms entry was called)
-    if (std::strcmp(name, "signif_launches") == 0) { *value = h->signif_launches; return CMF_OK; }                           // launches of the kernels of cmf_signif.h (cmf_null_moments: three per batch of draws)
-    if (admm_counter(h, name, value)) return CMF_OK;                                                     // reverts of the last ADMM call of each kind
-    if (sep_counter(h, name, value)) return CMF_OK;                                                      // pivoting rounds of the last NNLS step of the separable fit
-    if (anls_counter(h, name, value)) return CMF_OK;                                                     // pivoting rounds, backup-rule and capped problems of the last ANLS call
-    if (std::strcmp(name, "small_k_fused_h_updates") == 0) { // (a group: over its shards)
-        *value = h->sk_fused_h;
-        if (h->group)
-            for (const cmf_handle_s *s : h->group->sh) *value += (s != h) ? s->sk_fused_h : 0;
-        return CMF_OK;
-    }                       // H updates that ran inside the few-component C3 launch
-    if (std::strcmp(name, "writeback_overlapped") == 0) { *value = h->wb ? h->wb->hooked_calls : 0; return CMF_OK; }     // ... served by the copy stream behind the H update
-    if (std::strncmp(name, "launches:", 9) == 0) { // launches of one path (kLaunchNames; a group: over its shards)
-        for (int c = 0; c < LA_NCLS; ++c)
-            if (std::strcmp(name + 9, kLaunchNames[c]) == 0) {
-                *value = h->launches[c];
-                if (h->group)
-                    for (const cmf_handle_s *s : h->group->sh) *value += (s != h) ? s->launches[c] : 0;
-                return CMF_OK;
-            }
-        for (int c = 0; c < HL_NCLS; ++c) // the HALS entries' table (a HALS handle is never a group)
-            if (std::strcmp(name + 9, kHalsLaunchNames[c]) == 0) { *value = h->hals_launches[c]; return CMF_OK; }
-        return fail(CMF_ERR_ARG, "unknown launch path '%s'", name + 9);
-    }
-    if (h->group) { // host cost of the pipelined iterations of a group (reading a counter resets nothing)
-        cmf_group_s *g = h->group;
-        if (std::strcmp(name, "allreduce_calls") == 0) { *value = g->n_allreduce; return CMF_OK; } // collectives this handle has issued since it was made
-        if (std::strcmp(name, "allgather_calls") == 0) { *value = g->n_allgather; return CMF_OK; } // (per shard: every rank makes each of them once)
-        if (std::strcmp(name, "halo_in_allreduce") == 0) { *value = (g->halo_opt && g->halo_can && !g->gram && g->nranks > 1) ? 1 : 0; return CMF_OK; }
-        if (std::strcmp(name, "enqueue_ns") == 0) { *value = g->enqueue_ns; return CMF_OK; }       // calling thread: enqueueing / posting
-        if (std::strcmp(name, "enqueue_iters") == 0) { *value = g->enqueue_iters; return CMF_OK; } // ... over this many iterations
-        if (std::strcmp(name, "worker_ns") == 0) {                                                  // busiest enqueue worker: time inside its jobs
-            int64_t m = 0;
-            for (const auto &w : g->pool.w) m = std::max<int64_t>(m, w->busy_ns.load());
-            *value = m;
-            return CMF_OK;
-        }
-    }
-    return fail(CMF_ERR_ARG, "unknown counter '%s'", name);
-}
-
 int cmf_set_stream(cmf_handle h, void *hip_stream)
 {
     if (!h) return fail(CMF_ERR_ARG, "handle is NULL");
@@ -1340,204 +1287,6 @@ int cmf_set_stream(cmf_handle h, void *hip_stream)
     }
     h->stream = (hipStream_t)hip_stream;
     return CMF_OK;
-}
-
-// every name cmf_set_option knows (cmf_option_names; tests/test_library_abi.py walks the table)
-static const char *const kOptionNames[] = {"reuse_est", "speculate", "gram", "conv_kernel", "conv_split", "small_k", "small_k_fuse", "hals_prepare", "hals_gram",
-                                           "hals_persist", "hals_general", "hals_seg", "hals_lag", "hals_debug", "hals_chase", "profile", "profile_mask",
-                                           "allreduce_overlap", "enqueue_threads", "halo_in_allreduce"};
-int cmf_option_names(char *buf, int64_t len)
-{
-    if (!buf || len < 1) return fail(CMF_ERR_ARG, "bad buffer");
-    std::string all;
-    for (const char *n : kOptionNames) all += (all.empty() ? "" : ",") + std::string(n);
-    if ((int64_t)all.size() + 1 > len) return fail(CMF_ERR_ARG, "buffer too small: %zu bytes needed", all.size() + 1);
-    std::memcpy(buf, all.c_str(), all.size() + 1);
-    return CMF_OK;
-}
-
-// The 0/1 options that cmf_option_names does not list (off by default, see the header; not paths of the listed rules): the field, who
-// may set it, and whether it is a gate of the MU forms -- one that cannot be switched off while what it let in is installed (mu_refusal)
-struct FlagOption { const char *name; int cmf_handle_s::*field; const char *who; bool gate; };
-static const FlagOption kFlagOptions[] = {
-    {"anls_backup_only", &cmf_handle_s::anls_backup_only, "the ANLS rule runs", false}, // plain principal pivoting
-    {"nnls_large", &cmf_handle_s::nnls_large, "the ANLS rule and the separable fit run", false}, // cmf_anls_update_motifs / cmf_sep_nnls: 129 .. 1024 unknowns through global scratch
-    {"kl_mask", &cmf_handle_s::kl_mask, "the mask and the divergence of the MU rule are chosen", true}, // cmf_mu_set_mask + cmf_mu_set_divergence(KL) together
-    {"pq_mask", &cmf_handle_s::pq_mask, "the mask and the divergence of the MU rule are chosen", true}, // cmf_mu_set_mask + the Itakura-Saito / beta form together
-    {"is_div", &cmf_handle_s::is_div, "the divergence of the MU rule is chosen", true}, // lets cmf_mu_set_divergence take CMF_DIV_IS
-};
-
-int cmf_set_option(cmf_handle h, const char *name, int value)
-{
-    if (!h || !name) return fail(CMF_ERR_ARG, "NULL argument");
-    if (std::strcmp(name, "signif_batch") == 0) { // draws per batch of cmf_null_moments (0: the default); the result does not depend on it
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "signif_batch: cmf_null_moments runs on single-GPU handles only");
-        if (value < 0) return fail(CMF_ERR_ARG, "signif_batch must be at least 0");
-        h->signif_batch = value;
-        return CMF_OK;
-    }
-    for (const FlagOption &o : kFlagOptions) {
-        if (std::strcmp(name, o.name) != 0) continue;
-        if (h->group || h->root_only || h->sharded) return fail(CMF_ERR_UNSUPPORTED, "%s: %s on single-GPU handles only", name, o.who);
-        if (value != 0 && value != 1) return fail(CMF_ERR_ARG, "%s must be 0 or 1", name);
-        if (o.gate && !value) CMFTRY(mu_ask(h, MuAsk{MU_ASK_GATE_OFF, 0, 0.0, 0, name}));
-        h->*o.field = value;
-        return CMF_OK;
-    }
-    if (h->group) {
-        cmf_group_s *g = h->group;
-        CMFTRY(group_join(g));
-        if (std::strcmp(name, "allreduce_overlap") == 0) {
-            CMFTRY(group_sync(g));
-            if (value) CMFTRY(group_ensure_lane1(g)); // the communication stream gets a communicator of its own
-            g->overlap = value != 0;
-            g->num_ready = false;
-            return CMF_OK;
-        }
-        if (std::strcmp(name, "halo_in_allreduce") == 0) { // 1 (default): the halo of H travels in the W-phase all-reduce where every shard can (cmf_groups.hip)
-            CMFTRY(group_sync(g));
-            g->halo_opt = value != 0;
-            g->halos_current = false; // (the next phase starts from a whole exchange in the form that is now in force)
-            g->halos_pending = false;
-            g->halo_wide = false;
-            g->num_ready = false;
-            return CMF_OK;
-        }
-        if (std::strcmp(name, "enqueue_threads") == 0) { // 1: an enqueue worker per shard (cmf_group.h), 0: the calling thread enqueues every shard
-            CMFTRY(group_sync(g));
-            if (value) return group_start_workers(g);
-            (void)group_stop_workers(g); // (the group has just been synchronised: nobody is inside a job)
-            return CMF_OK;
-        }
-        if (std::strcmp(name, "gram") == 0) {
-            // Gram form on a T-sharded group: every shard contracts numW and its additive share of HH = H_unfold H_unfold'
-            // from its own columns, the all-reduce carries [numW | HH | tail] (numW + (L*Kpad)^2 floats instead of 2 numW),
-            // denomW = HH * W is formed on every shard; denomH = lag-Gram taps of W applied to H with the H halos.
-            if (value != 0 && value != 1) return fail(CMF_ERR_UNSUPPORTED, "sharded handles take gram = 0 or 1 (the loss of gram = 2 is not exact to 1e-4)");
-            if (value && g->nranks > 1 && g->T < 4 * g->L)
-                return fail(CMF_ERR_UNSUPPORTED, "the Gram form on a sharded handle needs T >= 4 L (got T=%lld, L=%lld)", (long long)g->T, (long long)g->L);
-            CMFTRY(group_sync(g));
-            for (size_t i = 0; i < g->sh.size(); ++i) {
-                cmf_handle_s *s = g->sh[i];
-                CMFTRY(group_use(s));
-                if (value) CMFTRY(gram_ensure(s));
-                // the HH block shares its place with denomW of the default form; hals_hh_kernel writes the first L*K columns
-                // of each 128-padded row only, and the all-reduce sums the whole block in place: whatever the pad columns
-                // held would be multiplied by the rank count every iteration until it overflowed
-                if (value && i < g->red.size() && g->red[i])
-                    HIPCHK(hipMemsetAsync(g->red[i] + g->LKN2 / 2, 0, (size_t)g->HHsz * sizeof(float), s->stream));
-                s->gram = value;
-                set_est(s, EST_NONE);
-                s->carry = CmfLossCarry{};
-            }
-            g->gram = value;
-            g->num_ready = false;
-            return CMF_OK;
-        }
-        for (cmf_handle_s *s : g->sh) {
-            cmf_group_s *keep = s->group;
-            s->group = nullptr;
-            const int rc = cmf_set_option(s, name, value);
-            s->group = keep;
-            if (rc != CMF_OK) return rc;
-        }
-        g->num_ready = false;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "allreduce_overlap") == 0 || std::strcmp(name, "enqueue_threads") == 0 || std::strcmp(name, "halo_in_allreduce") == 0) return CMF_OK; // single GPU: nothing to overlap, nobody else to enqueue
-    if (std::strcmp(name, "gram") == 0) {
-        if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "gram must be 0, 1 or 2");
-        if (value && h->sharded && h->T_global != h->d.Tl) return fail(CMF_ERR_STATE, "the Gram form is not available on sharded handles");
-        CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_GRAM, 0, 0.0, value}));
-        h->gram = value;
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "conv_kernel") == 0) { // K % 32 == 0 only: 0 = chosen per mode (default), 3 = one-wave workgroups, 2 = 128 x 128 tiles
-        if (value != 0 && value != 2 && value != 3) return fail(CMF_ERR_ARG, "conv_kernel must be 0 (per mode), 2 or 3");
-        h->conv_variant = value;
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "hals_gram") == 0) { // HALS projections as differences of the MU quantities: 2 (default) = H phase, 1 = both phases, 0 = neither
-        h->hals_gram = (value == 1 || value == 2) ? value : 0; // 2 = the H phase only
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "hals_persist") == 0 || std::strcmp(name, "hals_general") == 0 || std::strcmp(name, "hals_seg") == 0 ||
-        std::strcmp(name, "hals_lag") == 0 || std::strcmp(name, "hals_debug") == 0 || std::strcmp(name, "hals_chase") == 0) {
-        if (value < 0 && !(name[5] == 'c' && value == -1)) return fail(CMF_ERR_ARG, "%s must be >= 0", name);
-        if (name[5] == 'd') { // "hals_debug": results are wrong by design -- tests of the bounded waits only
-            if (value && !test_hooks_on()) return fail(CMF_ERR_STATE, "hals_debug needs CMF_TEST_HOOKS=1");
-            h->hals_debug = value;
-            return CMF_OK;
-        }
-        if (name[5] == 'c') { // "hals_chase": per cent of the residual conv's tile rows that chase the row pipeline
-            if (value > 100) return fail(CMF_ERR_ARG, "hals_chase is a percentage (0 = off)");
-            h->hals_opt_chase = value;
-            if (h->hals_ready) {
-                HIPCHK(hipSetDevice(h->device));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                hals_plan(h);
-            }
-            return CMF_OK;
-        }
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        (name[5] == 'p' ? h->hals_opt_persist : name[5] == 'g' ? h->hals_opt_general : name[5] == 's' ? h->hals_opt_seg : h->hals_opt_lag) = value;
-        if (h->hals_ready) hals_plan(h);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "hals_prepare") == 0) { // allocate the HALS scratch and check its shape limits now (rule construction)
-        HIPCHK(hipSetDevice(h->device));
-        return hals_ensure(h);
-    }
-    if (std::strcmp(name, "conv_split") == 0) { // 0 = never cut the one-wave conv kernel's last round into quarter tiles
-        h->conv_split = value;
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "small_k_fuse") == 0) { // few components: 1 (default) = the element-wise update of H inside the C3 launch, 0 = a launch of its own
-        if (value < 0 || value > 2) return fail(CMF_ERR_ARG, "small_k_fuse must be 0, 1 or 2");
-        h->sk_fuse = value; // (2: also on one-round launches, where it is slower)
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "small_k") == 0) { // K <= 16: 1 = the few-component kernels (cmf_small_k.h; default), 0 = the general kernels
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->small_k = value != 0 && h->small_k_ok;
-        h->sk_wj_gen = -1;
-        h->sk_tc = h->small_k && (h->sk_tc_ok || value == 2); // (2: the few-component C3 form whatever T is -- tests, measurements)
-        h->tc_S = h->sk_tc ? 2 * h->sk3_NS : h->tc_S_full; // (own block | the spill of the next block, per piece of the reduction: g_gemm_fold_small_kernel)
-        h->tc_S1 = h->sk_tc ? 2 * h->sk3_NS : h->tc_S1_full;
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "reuse_est") == 0) {
-        h->reuse_est = value != 0;
-        set_est(h, EST_NONE);
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "speculate") == 0) { // 1 (default): update_feature_maps! enqueues the next update_motifs!'s contraction behind its loss conv when the caller alternates the two calls
-        h->speculate = value != 0;
-        h->spec_gen = -1;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "profile_mask") == 0) { // which kernel classes "profile" times (bit i: class i of cmf_kernel_times' names in their order; 0 = all)
-        h->prof_mask = (unsigned)value;
-        return CMF_OK;
-    }
-    if (std::strcmp(name, "profile") == 0) { // (re)start or stop the in-loop kernel timing; collected times are dropped
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (auto &r : h->prof_recs) { h->prof_pool.push_back(r.a); h->prof_pool.push_back(r.b); }
-        h->prof_recs.clear();
-        h->prof = value != 0;
-        h->prof_every = value > 1 ? value : 1;
-        for (int &c : h->prof_seen) c = 0;
-        return CMF_OK;
-    }
-    return fail(CMF_ERR_ARG, "unknown option '%s'", name);
 }
 
 int cmf_get_data_sumsq(cmf_handle h, double *sumsq)
@@ -2419,6 +2168,20 @@ int cmf_kernel_times(cmf_handle h, const char *name, double *avg_ms, int64_t *la
     return CMF_OK;
 }
 
+// The plain names of cmf_time_kernel: one contraction launch of an iteration each.  contractions: its flops in units of one contraction
+// (SURVEY.md section 8d); est_after: what est holds afterwards, whatever it held before (a residual on HALS / PGD handles).
+constexpr int EST_AS_BEFORE = -1;
+struct TimedKernel { const char *name; int (*launch)(cmf_handle_s *); double contractions; int est_after; };
+static const TimedKernel kTimedKernels[] = {
+    {"conv", [](cmf_handle_s *h) { return launch_conv<CONV_EST>(h, h->est, h->d.Tl, h->conv_gy); }, 1.0, EST_CONV},
+    {"hxt", [](cmf_handle_s *h) { return h->small_k ? hxt_contract(h, h->X, h->est, 2, h->numden) // (few components: kernel + its slab sum)
+                                                    : launch_hxt_on(h, h->X, h->est, h->d.Np, 2, h->wslabs, h->hxt_nchunks, h->hxt_chunk_len, h->hxt_main); }, 2.0, EST_AS_BEFORE},
+    {"transconv", [](cmf_handle_s *h) { return launch_transconv(h, 2); }, 2.0, EST_AS_BEFORE},
+    {"conv_t", [](cmf_handle_s *h) { return launch_conv<CONV_EST_T>(h, h->estT, h->d.Tl + h->halo_r, h->conv_gy_ext); }, 1.0, EST_AS_BEFORE},
+    {"conv_loss", [](cmf_handle_s *h) { return launch_conv<CONV_LOSS>(h, nullptr, h->d.Tl, h->conv_gy); }, 1.0, EST_AS_BEFORE},
+    {"conv_loss_store", [](cmf_handle_s *h) { return launch_conv<CONV_LOSS_EST>(h, h->est, h->d.Tl, h->conv_gy); }, 1.0, EST_CONV},
+};
+
 int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, double *flops)
 {
     if (!name || !avg_ms || !flops || reps < 1) return fail(CMF_ERR_ARG, "bad argument");
@@ -2444,22 +2207,16 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
             CMFTRY(group_ensure_lane1(g));
         }
         if (halo) count = (size_t)(2 * g->HC);
-        auto once = [&]() -> int { return halo ? group_allgather(g, g->halo_send, g->halo_all, count) : group_allreduce(g, g->red, 0, count, lane1 ? 1 : 0); };
+        auto once = [&]() -> int { // (the events are shard 0's: its device is current around them)
+            CMFTRY(halo ? group_allgather(g, g->halo_send, g->halo_all, count) : group_allreduce(g, g->red, 0, count, lane1 ? 1 : 0));
+            return group_use(s0);
+        };
         for (size_t i = 0; i < g->sh.size() && !halo; ++i) { // finite input: the sums of `reps` all-reduces of zeros stay zeros
             CMFTRY(group_use(g->sh[i]));
             HIPCHK(hipMemsetAsync(g->red[i], 0, count * sizeof(float), lane1 ? g->sh[i]->comm_stream : g->sh[i]->stream));
         }
-        hipStream_t ts = lane1 ? s0->comm_stream : s0->stream;
-        CMFTRY(once()); // warm-up
-        CMFTRY(group_use(s0));
-        HIPCHK(hipEventRecord(s0->ev0, ts));
-        for (int r = 0; r < reps; ++r) CMFTRY(once());
-        CMFTRY(group_use(s0));
-        HIPCHK(hipEventRecord(s0->ev1, ts));
+        CMFTRY(timed_reps(lane1 ? s0->comm_stream : s0->stream, s0->ev0, s0->ev1, reps, once, avg_ms));
         CMFTRY(group_sync(g));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, s0->ev0, s0->ev1));
-        *avg_ms = (double)ms / reps;
         *flops = (double)count * sizeof(float);
         g->num_ready = false;
         g->halos_current = g->halos_pending = g->halo_wide = false; // (the buffers are scratch here: halo slots waiting in the tail are gone -- the next phase exchanges afresh)
@@ -2500,17 +2257,8 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
             }
             return CMF_OK;
         };
-        int rc = once();
-        if (rc == CMF_OK) {
-            HIPCHK(hipEventRecord(h->ev0, keep));
-            for (int r = 0; r < reps && rc == CMF_OK; ++r) rc = once();
-            HIPCHK(hipEventRecord(h->ev1, keep));
-            HIPCHK(hipEventSynchronize(h->ev1));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            *avg_ms = (double)ms / reps;
-            *flops = 2.0 * f1;
-        }
+        const int rc = timed_reps(keep, h->ev0, h->ev1, reps, once, avg_ms);
+        if (rc == CMF_OK) *flops = 2.0 * f1;
         (void)hipStreamSynchronize(aux);
         (void)hipStreamDestroy(aux);
         (void)hipEventDestroy(fork);
@@ -2559,17 +2307,8 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
             if (ra < rows_t) CMFTRY(launch_conv<CONV_RESID>(h, h->est, d.Tl - ra * 64, h->conv_gy));
             return CMF_OK;
         };
-        int rc = once();
-        if (rc == CMF_OK) {
-            HIPCHK(hipEventRecord(h->ev0, keep));
-            for (int r = 0; r < reps && rc == CMF_OK; ++r) rc = once();
-            HIPCHK(hipEventRecord(h->ev1, keep));
-            HIPCHK(hipEventSynchronize(h->ev1));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            *avg_ms = (double)ms / reps;
-            *flops = f1;
-        }
+        const int rc = timed_reps(keep, h->ev0, h->ev1, reps, once, avg_ms);
+        if (rc == CMF_OK) *flops = f1;
         h->stream = keep;
         (void)hipStreamSynchronize(sa);
         (void)hipStreamSynchronize(sb);
@@ -2582,30 +2321,13 @@ int cmf_time_kernel(cmf_handle h, const char *name, int reps, double *avg_ms, do
         set_est(h, EST_NONE);
         return rc;
     }
-    int which = nm == "conv" ? 0 : nm == "hxt" ? 1 : nm == "transconv" ? 2 : nm == "conv_t" ? 3 : nm == "conv_loss" ? 4
-              : nm == "conv_loss_store" ? 5 : -1;
-    if (which < 0) return fail(CMF_ERR_ARG, "unknown kernel '%s'", name);
-    auto run = [&]() -> int {
-        switch (which) {
-        case 0: return launch_conv<CONV_EST>(h, h->est, d.Tl, h->conv_gy);
-        case 1: return h->small_k ? hxt_contract(h, h->X, h->est, 2, h->numden) // (few components: kernel + its slab sum)
-                                : launch_hxt_on(h, h->X, h->est, d.Np, 2, h->wslabs, h->hxt_nchunks, h->hxt_chunk_len, h->hxt_main);
-        case 2: return launch_transconv(h, 2);
-        case 3: return launch_conv<CONV_EST_T>(h, h->estT, d.Tl + h->halo_r, h->conv_gy_ext);
-        case 4: return launch_conv<CONV_LOSS>(h, nullptr, d.Tl, h->conv_gy);
-        default: return launch_conv<CONV_LOSS_EST>(h, h->est, d.Tl, h->conv_gy);
-        }
-    };
-    CMFTRY(run()); // warm-up
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; ++r) CMFTRY(run());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *avg_ms = (double)ms / reps;
-    if (which == 0 || which == 5) set_est(h, EST_CONV); // est now holds plain tensor_conv(W, H), whatever it held before (a residual on HALS / PGD handles)
-    *flops = (which == 1 || which == 2) ? 2.0 * f1 : f1;
-    return CMF_OK;
+    for (const TimedKernel &k : kTimedKernels) {
+        if (nm != k.name) continue;
+        CMFTRY(timed_reps(h->stream, h->ev0, h->ev1, reps, [&]() -> int { return k.launch(h); }, avg_ms));
+        if (k.est_after != EST_AS_BEFORE) set_est(h, k.est_after);
+        *flops = k.contractions * f1;
+        return CMF_OK;
+    }
+    return fail(CMF_ERR_ARG, "unknown kernel '%s'", name);
 }
 

@@ -692,25 +692,20 @@ int cmf_events_set_option(cmf_events h, const char *name, int value)
     return rc;
 }
 
+static const CounterRow<cmf_events_s> kEventCounters[] = {
+    CMF_COUNTER_ROW("device_bytes", h->device_bytes, 0), CMF_COUNTER_ROW("launches", h->launches, 0), CMF_COUNTER_ROW("ratio_passes", h->ratio_passes, 0), CMF_COUNTER_ROW("nnz", h->nnz, 0),
+    CMF_COUNTER_ROW("unit_chunk", h->unit_chunk, 0), CMF_COUNTER_ROW("time_chunk", h->time_chunk, 0), CMF_COUNTER_ROW("keep_ratio", h->keep_ratio, 0),
+    CMF_COUNTER_ROW("unit_items", h->n_u_items, 0), CMF_COUNTER_ROW("time_items", h->n_t_items, 0), CMF_COUNTER_ROW("unit_split", h->n_u_fixes, 0), CMF_COUNTER_ROW("time_split", h->n_t_fixes, 0),
+    CMF_COUNTER_ROW("w_block_units", 64, 0),       // units per workgroup of w_update_kernel
+    CMF_COUNTER_ROW("h_block_columns", HUPD_T, 0), // columns per workgroup of h_update_kernel
+    CMF_COUNTER_ROW("ratio_waves", 4, 0),          // events a workgroup of ev_ratio_kernel has in flight
+};
 int cmf_events_get_counter(cmf_events h, const char *name, int64_t *value)
 {
     if (!h || !name || !value) return fail(CMF_ERR_ARG, "NULL argument");
-    const std::string nm(name);
-    if (nm == "device_bytes") *value = h->device_bytes;
-    else if (nm == "launches") *value = h->launches;
-    else if (nm == "ratio_passes") *value = h->ratio_passes;
-    else if (nm == "nnz") *value = h->nnz;
-    else if (nm == "unit_chunk") *value = h->unit_chunk;
-    else if (nm == "time_chunk") *value = h->time_chunk;
-    else if (nm == "keep_ratio") *value = h->keep_ratio;
-    else if (nm == "unit_items") *value = h->n_u_items;
-    else if (nm == "time_items") *value = h->n_t_items;
-    else if (nm == "unit_split") *value = h->n_u_fixes;
-    else if (nm == "time_split") *value = h->n_t_fixes;
-    else if (nm == "w_block_units") *value = 64;       // units per workgroup of w_update_kernel
-    else if (nm == "h_block_columns") *value = HUPD_T; // columns per workgroup of h_update_kernel
-    else if (nm == "ratio_waves") *value = 4;          // events a workgroup of ev_ratio_kernel has in flight
-    else return fail(CMF_ERR_ARG, "unknown counter \"%s\"", name);
+    const CounterRow<cmf_events_s> *r = row_named(kEventCounters, name);
+    if (!r) return fail(CMF_ERR_ARG, "unknown counter \"%s\"", name);
+    *value = r->get(h);
     return CMF_OK;
 }
 

@@ -77,6 +77,21 @@ static inline long long n_cu_hook() { return test_hook("CMF_TEST_N_CU", kNoCuHoo
 
 static inline int64_t rup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// The timed repetition of cmf_time_kernel: one warm-up call of `once`, then `reps` calls between ev0 and ev1 on `stream`; *avg_ms = the
+// events' span per call.  `once` returns a CMF code and leaves the device of `stream` current; the first failure ends the measurement.
+template <class F> static int timed_reps(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int reps, F once, double *avg_ms)
+{
+    CMFTRY(once()); // warm-up
+    HIPCHK(hipEventRecord(ev0, stream));
+    for (int r = 0; r < reps; ++r) CMFTRY(once());
+    HIPCHK(hipEventRecord(ev1, stream));
+    HIPCHK(hipEventSynchronize(ev1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    *avg_ms = (double)ms / reps;
+    return CMF_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // roctx ranges (tracing)
 // ------------------------------------------------------------------------------------------
@@ -191,6 +206,7 @@ static const char *const kHalsLaunchNames[] = {
 static_assert(sizeof(kHalsLaunchNames) / sizeof(kHalsLaunchNames[0]) == HL_NCLS, "one name per HALS launch path");
 
 #include "cmf_mu_install.h" // CMF_DIV_BETA; what each divergence needs to be installed and when a request is refused (free of HIP)
+#include "cmf_options.h"    // the table of cmf_set_option and the options a handle stores as values (CmfOptionFields; free of HIP)
 
 // What est / estT hold for the resident W, H (cmf_handle_s::est_kind): a reader recomputes on a mismatch, every writer passes through set_est.
 enum EstKind : int {
@@ -212,7 +228,7 @@ enum EstKind : int {
 static inline int pgd_est_kind(bool masked, bool loss_abs) { return EST_RESID + (masked ? 1 : 0) + (loss_abs ? 2 : 0); }
 static_assert(EST_RESID_MASKED == EST_RESID + 1 && EST_SIGN == EST_RESID + 2 && EST_SIGN_MASKED == EST_RESID + 3, "pgd_est_kind");
 
-struct cmf_handle_s {
+struct cmf_handle_s : CmfOptionFields {
     int device = 0;
     CmfDims d{};
     int64_t t_offset = 0, T_global = 0;
@@ -262,15 +278,11 @@ struct cmf_handle_s {
     float *sk_slabs = nullptr, *sk_Wj = nullptr;
     int *sk_cnt = nullptr;                  // ticket counters of the fused few-component launches (one per 128-column block of H; zero between launches)
     int64_t sk_fused_h = 0;                 // cmf_get_counter "small_k_fused_h_updates"
-    int sk_fuse = 1;                        // option "small_k_fuse": 1 = the element-wise update of H runs inside the C3 launch (cmf_small_k.h)
     int64_t sk_wj_gen = -1;                 // est_gen at which sk_Wj was packed from the resident W (w_update_small_kernel, wj_pack_kernel): every writer of W
                                             // passes through set_est, so a stale operand cannot be taken for a fresh one (-1: never packed)
     int tc_S_full = 1, tc_S1_full = 1;      // fragment slabs of the general transconv kernel (tc_S / tc_S1 are 1 while small_k is on)
     int conv_gx = 1, conv_gy = 1, conv_gy_ext = 1;
-    int conv_variant = 0;   // K % 32 == 0: 3 = one-wave workgroups (conv3_kernel), 2 = 128 x 128 tiles (conv2_kernel), 0 = per mode
     int conv_partials = 1;  // loss partials written by the last conv launch
-    int conv_split = 1;     // option "conv_split": 0 = whole tiles only, 1 = quarter / sixteenth tiles for the thin last round of the
-                            // one-wave conv kernel, 4 = quarter tiles only
     int n_cu = 256;
 
     // HALS scratch (allocated on first use)
@@ -280,18 +292,10 @@ struct cmf_handle_s {
     float *hals_HX = nullptr, *hals_cslabs = nullptr, *hals_C = nullptr, *hals_HH = nullptr, *hals_PT = nullptr, *hals_D = nullptr;
     float *hals_PW = nullptr, *hals_GW = nullptr, *hals_GE = nullptr, *hals_GWt = nullptr;
     int hals_seg = 256, hals_nseg = 1;      // column segments of the pipelined H sweep
-    int hals_gram = 2;                      // the sweeps' projections as differences of the MU quantities: 2 = P of the H phase only (default:
-                                            // one conv launch fewer, H within the residual form's bars), 1 = G of the W phase too (~20x the rounding
-                                            // error in W: opt-in), 0 = both contracted from the stored residual
     bool hals_w_general = false, hals_h_general = false; // shapes beyond the on-chip sweeps' limits: the general sweep kernels
-    // options "hals_persist" (1 = the persistent pipeline where it fits, 0 = the stage pipeline, n > 1 = at most n pullers per row),
-    // "hals_general" (bit 0 / 1: the general W / H sweeps at any shape), "hals_seg" / "hals_lag" (the stage pipeline's segment length
-    // and schedule), "hals_debug" (CMF_TEST_HOOKS=1 only: 3 = the pullers leave at once, so that every bounded wait must run out)
-    int hals_opt_persist = 1, hals_opt_general = 0, hals_opt_seg = 384, hals_opt_lag = 2, hals_debug = 0;
     // The residual conv CHASING the row pipeline (option "hals_chase" = per cent of its tile rows, 0 = off): the pipeline runs on a
     // stream masked to the CUs its K + (K-1)P workgroups need, the first tile rows of the conv on a stream masked to the other CUs,
     // each tile waiting for the last row's progress flag (conv3_chase_kernel); the rest of the conv follows on the whole chip.
-    int hals_opt_chase = -1;             // (-1: the share is estimated from the shape, hals_chase_rows)
     hipStream_t hals_sA = nullptr, hals_sB = nullptr; // CU-masked: pipeline | chasing conv (created at the first chased sweep)
     hipEvent_t hals_ev[3] = {nullptr, nullptr, nullptr}; // fork, pipeline done, chasing part done
     int hals_mask_aper = 0;                 // CUs per XCD the pipeline's stream is masked to (the streams are remade when the plan changes)
@@ -321,20 +325,15 @@ struct cmf_handle_s {
     int64_t pow_launches = 0;    // launches of w_update_pow_kernel / h_update_pow_kernel (cmf_get_counter "pow_update_launches")
     float beta_consts[11] = {};  // ... and what its convs read, in the order of ConvParams::beta_m1 .. beta_c
     double data_sum = 0.0;       // what the divergence is divided by: sum(data) (under a mask: sum(Xm)); Itakura-Saito: N * Tl, the mean per entry
-    int kl_mask = 0;             // cmf_set_option "kl_mask": 1 lets the KL form and a mask of cmf_mu_set_mask be installed together
     float *kl_denH = nullptr;    // [Tl][K32]: denomH[k, t] broadcast for h_update_kernel
     double *kl_sums = nullptr;   // [K32 * max(L, KL_HCHUNKS)]: row sums of H in chunks / sums over n of W per (lag, k)
-    int is_div = 0;              // cmf_set_option "is_div": 1 lets cmf_mu_set_divergence take CMF_DIV_IS
-    int pq_mask = 0;             // cmf_set_option "pq_mask": 1 lets the Itakura-Saito / beta forms and a mask of cmf_mu_set_mask be installed together
-    float *Xs = nullptr, *XsT = nullptr; // ... and while both are: data with a negative sentinel at the held-out entries, in the layouts of X and XT
+    float *Xs = nullptr, *XsT = nullptr; // while the Itakura-Saito / beta forms and a mask are both installed (option "pq_mask"): data with a negative sentinel at the held-out entries, in the layouts of X and XT
                                          // (what the masked P, Q convs read: conv_pq_sentinel); data_sum then holds the observed count
     float *est2 = nullptr, *est2T = nullptr; // Q = 1 ./ e of the Itakura-Saito form beside P in est / estT: [TP][Np] / [Np][TP], zero-filled; allocated when the form is first installed, kept until the handle goes
 
     double data_sumsq = 0.0, data_norm = 0.0;
     bool factors_set = false;
     bool have_data = false;
-    bool reuse_est = true;  // option "reuse_est"
-    int gram = 0;           // option "gram": 0 off, 1 Gram-form denominators, 2 also the loss from Gram sums
     float *gram_numden_h = nullptr; // [1][2][Tl][K32]: numH | denomH in the h_update slab layout
     // in-loop kernel timing (option "profile"): HIP event pairs around the contraction launches, on the launch stream
     bool prof = false;
@@ -343,7 +342,6 @@ struct cmf_handle_s {
     int64_t launches[LA_NCLS] = {0}; // cmf_get_counter "launches:<name>" (kLaunchNames)
     int64_t hals_launches[HL_NCLS] = {0}; // ... of the HALS entries (kHalsLaunchNames)
     struct ProfRec { hipEvent_t a, b; int cls; };
-    unsigned prof_mask = 0; // option "profile_mask"
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
     int est_kind = EST_NONE; // what est[t][n] holds for the resident W, H (EstKind)
@@ -353,7 +351,6 @@ struct cmf_handle_s {
     int64_t est_gen = 0;    // counts the assignments of est_kind (set_est): whatever changes H, W or est passes through one
     int64_t spec_gen = -1;  // est_gen for which the C2 contraction of the NEXT update_motifs! has already been enqueued (w_speculate); -1: none
     int last_rule_call = 0; // 1: cmf_update_motifs, 2: cmf_update_feature_maps (MU rule, single handle): speculation follows the alternation only
-    bool speculate = true;  // option "speculate"
     std::function<int()> after_reduce;  // run once by the next reduce_partials between its launch and its wait for the sum (the HALS rule's speculation)
     int64_t hals_spec_gen = -1; // est_gen for which G (the C2 contraction on the residual) and HH of the NEXT HALS update_motifs! have been enqueued; -1: none
     int64_t spec_hits = 0;  // update_motifs! calls that found their contraction done (cmf_get_counter "speculated_contractions")
@@ -371,18 +368,15 @@ struct cmf_handle_s {
     struct AdmmState *admm = nullptr;     // the ADMM rule's fp64 state (cmf_admm_prepare; cmf_admm.hip)
     struct AnlsState *anls = nullptr;     // the ANLS rule's fp64 state (cmf_anls_prepare; cmf_anls.hip)
     struct SepState *sep = nullptr;       // the separable fit's fp64 state (cmf_sep_prepare; cmf_sep.hip)
-    int anls_backup_only = 0;             // cmf_set_option "anls_backup_only": every exchange of the ANLS solver is a backup-rule exchange
-    int nnls_large = 0;                   // cmf_set_option "nnls_large": 129 .. 1024 unknowns run in nnls_large_kernel (cmf_nnls_large.h) instead of being refused
     // seqNMF's cross-orthogonality penalties on the squared-error MU rule (cmf_mu_set_xortho; cmf_xortho.hip): the weights lambda, lambda_H, lambda_W
     // (all 0: today's path, launch for launch), the tables of the penalty terms (allocated with the first non-zero weight or the first
     // cmf_mu_xortho_cost / cmf_mu_xortho_terms) and the launches of the kernels of cmf_xortho.h (cmf_get_counter "xortho_launches")
     double xo_lam[3] = {0.0, 0.0, 0.0};
     struct XoState *xo = nullptr;
     int64_t xo_launches = 0;
-    // seqNMF's significance test on held-out data (cmf_null_moments; cmf_signif.hip): its scratch (allocated on first use), the draws per
-    // batch (cmf_set_option "signif_batch"; 0: the default of cmf_signif.h) and the launches of its kernels (cmf_get_counter "signif_launches")
+    // seqNMF's significance test on held-out data (cmf_null_moments; cmf_signif.hip): its scratch (allocated on first use) and the launches
+    // of its kernels (cmf_get_counter "signif_launches")
     struct SignifState *signif = nullptr;
-    int signif_batch = 0;
     int64_t signif_launches = 0;
 };
 static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
@@ -775,7 +769,7 @@ struct ProfScope {
     ProfScope(cmf_handle_s *h_, int cls) : h(h_)
     {
         if (!h->prof || h->prof_recs.size() >= 8192) return;
-        if (h->prof_mask && !((h->prof_mask >> cls) & 1u)) return;
+        if (h->prof_mask && !(((unsigned)h->prof_mask >> cls) & 1u)) return;
         if ((h->prof_seen[cls]++ % h->prof_every) != 0) return;
         hipEvent_t ev[2] = {nullptr, nullptr};
         for (int q = 0; q < 2; ++q) {

@@ -148,14 +148,8 @@ int signif_time(cmf_handle_s *h, bool draws, int reps, double *avg_ms, double *f
         CMFTRY(launch_transconv(h, 1, h->XT));
         return launch_slab_sum(h, s->tsum, h->hslabs, h->tc_S1, (size_t)d.Tl * d.K32);
     };
-    CMFTRY(run()); // warm-up
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; ++r) CMFTRY(run());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *avg_ms = (double)ms / reps / (draws ? (double)B : 1.0);
+    CMFTRY(timed_reps(h->stream, h->ev0, h->ev1, reps, run, avg_ms));
+    if (draws) *avg_ms /= (double)B;
     const double S = (double)d.L * d.Tl - 0.5 * (double)d.L * (d.L - 1);
     *flops = 2.0 * d.K * d.N * S;
     return CMF_OK;

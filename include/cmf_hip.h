@@ -71,7 +71,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_signif.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, cmf_signif.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_signif.hip, cmf_options.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, cmf_signif.h, cmf_options.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);

@@ -168,8 +168,8 @@ def test_option_is_documented_but_not_listed(cmf):
     assert "pq_mask" not in buf.value.decode().split(",")
     lib.cmf_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
     assert lib.cmf_set_option(None, b"pq_mask", 1) == 1  # CMF_ERR_ARG: a NULL handle
-    src = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_api.hip")).read()
-    assert re.search(r'\{"pq_mask", &cmf_handle_s::pq_mask, [^\n]*, true\}', src)  # (a gate of cmf_set_option's table of 0/1 options)
+    src = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_options.h")).read()
+    assert re.search(r'OPT_FLAG\(pq_mask, "[^\n"]*", FX_MU_GATE\)', src)  # (a gate among the 0/1 rows of cmf_set_option's table)
     assert '"pq_mask"' in open(os.path.join(ROOT, "cmf.jl_amd", "julia", "CMFHip.jl")).read()
     assert "pq_mask" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
     modes = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_conv_modes.h")).read()

@@ -65,8 +65,8 @@ def test_the_option_is_wired_through_every_layer():
     host = __import__("importlib").import_module(cmf.__name__ + ".host")
     assert "nnls_large" in host._KNOWN_KW
     assert "nnls_large" in cmf.separable_fit.__doc__ and "nnls_large" in cmf.ANLSUpdate.__doc__
-    api = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_api.hip")).read()
-    assert re.search(r'\{"nnls_large", &cmf_handle_s::nnls_large, [^\n]*, false\}', api)  # (a row of cmf_set_option's table of 0/1 options)
+    table = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_options.h")).read()
+    assert re.search(r'OPT_FLAG\(nnls_large, "[^\n"]*", 0\)', table)  # (a 0/1 row of cmf_set_option's table: single-GPU handles, not a gate)
     large = open(os.path.join(ROOT, "cmf.jl_amd", "csrc", "cmf_nnls_large.h")).read()
     assert re.search(r"constexpr int WLARGE = 1024;", large) and "nnls_large_kernel" in large
     for unit in ("cmf_anls.hip", "cmf_sep.hip"):
