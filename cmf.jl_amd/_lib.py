@@ -33,7 +33,7 @@ SYMBOLS = [
     "cmf_set_factors", "cmf_get_factors", "cmf_arm_writeback", "cmf_fingerprint",
     "cmf_update_motifs", "cmf_update_feature_maps", "cmf_compute_loss", "cmf_iterate", "cmf_fit", "cmf_converged",
     "cmf_hals_update_motifs", "cmf_hals_update_feature_maps",
-    "cmf_pgd_reset", "cmf_set_mask", "cmf_mu_set_mask", "cmf_masked_loss", "cmf_mu_set_divergence", "cmf_mu_set_beta_divergence", "cmf_mu_set_xortho", "cmf_mu_xortho_cost", "cmf_mu_xortho_terms", "cmf_null_shifts", "cmf_null_moments", "cmf_pgd_set_loss", "cmf_pgd_update_motifs", "cmf_pgd_update_feature_maps", "cmf_pgd_get_steps",
+    "cmf_pgd_reset", "cmf_set_mask", "cmf_mu_set_mask", "cmf_masked_loss", "cmf_mu_set_divergence", "cmf_mu_set_beta_divergence", "cmf_mu_set_xortho", "cmf_mu_xortho_cost", "cmf_mu_xortho_terms", "cmf_null_shifts", "cmf_null_moments", "cmf_recentre_shifts", "cmf_recentre", "cmf_mu_set_recentre", "cmf_mu_recentre_info", "cmf_pgd_set_loss", "cmf_pgd_update_motifs", "cmf_pgd_update_feature_maps", "cmf_pgd_get_steps",
     "cmf_admm_prepare", "cmf_admm_update_motifs", "cmf_admm_update_feature_maps",
     "cmf_anls_prepare", "cmf_anls_update_motifs", "cmf_anls_update_feature_maps",
     "cmf_sep_prepare", "cmf_sep_gram", "cmf_sep_spa", "cmf_sep_nnls", "cmf_sep_shift_table", "cmf_sep_construct",
@@ -133,6 +133,10 @@ def load():
     sig("cmf_mu_xortho_terms", [vp, pd, pd, pd, pd])
     sig("cmf_null_shifts", [u64, i64, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int32)])
     sig("cmf_null_moments", [vp, u64, i64, i64, pd])
+    sig("cmf_recentre_shifts", [pd, i64, i64, i64, ctypes.POINTER(ctypes.c_int32)])
+    sig("cmf_recentre", [vp, ctypes.POINTER(ctypes.c_int32)])
+    sig("cmf_mu_set_recentre", [vp, cint])
+    sig("cmf_mu_recentre_info", [vp, ctypes.POINTER(ctypes.c_int32), pi64])
     sig("cmf_pgd_set_loss", [vp, cint])
     sig("cmf_pgd_update_motifs", [vp, dbl, dbl, cint])
     sig("cmf_pgd_update_feature_maps", [vp, dbl, dbl, cint, pd])

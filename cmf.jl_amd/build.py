@@ -17,14 +17,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcmf_hip.so")
-# Eleven translation units, compiled side by side (round 5: one 3.6 kLoC file, 54 s; now 35 s on the build container's 8 cores): the MU
+# Twelve translation units, compiled side by side (round 5: one 3.6 kLoC file, 54 s; now 35 s on the build container's 8 cores): the MU
 # rule + C ABI, the HALS / Gram / PGD rules, the T-sharded groups, the launchers of the few-component kernels, the fp64 ADMM and
 # ANLS rules, the separable fit, the cross-orthogonality penalties of the MU rule, the KL rule on event lists, the
-# significance test of components on held-out data, and the options and counters of the C ABI (no kernels)
-SOURCES = [os.path.join(CSRC, f) for f in ("cmf_api.hip", "cmf_rules.hip", "cmf_groups.hip", "cmf_small.hip", "cmf_admm.hip", "cmf_anls.hip", "cmf_sep.hip", "cmf_xortho.hip", "cmf_events.hip", "cmf_signif.hip",
+# significance test of components on held-out data, the re-centring of motifs, and the options and counters of the C ABI (no kernels)
+SOURCES = [os.path.join(CSRC, f) for f in ("cmf_api.hip", "cmf_rules.hip", "cmf_groups.hip", "cmf_small.hip", "cmf_admm.hip", "cmf_anls.hip", "cmf_sep.hip", "cmf_xortho.hip", "cmf_events.hip", "cmf_signif.hip", "cmf_recentre.hip",
                                            "cmf_options.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("cmf_internal.h", "cmf_kernels.h", "cmf_conv_modes.h", "cmf_small_k.h", "cmf_workers.h", "cmf_writeback.h", "cmf_rng.h",
-                                                  "cmf_fp64.h", "cmf_admm.h", "cmf_anls.h", "cmf_nnls_large.h", "cmf_sep.h", "cmf_xortho.h", "cmf_events.h", "cmf_mu_install.h", "cmf_signif.h", "cmf_options.h")] + [
+                                                  "cmf_fp64.h", "cmf_admm.h", "cmf_anls.h", "cmf_nnls_large.h", "cmf_sep.h", "cmf_xortho.h", "cmf_events.h", "cmf_mu_install.h", "cmf_signif.h", "cmf_recentre.h", "cmf_options.h")] + [
     os.path.join(ROOT, "include", "cmf_hip.h")]
 
 

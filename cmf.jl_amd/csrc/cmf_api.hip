@@ -4,7 +4,6 @@
 #include "cmf_internal.h"
 
 static void wb_free(cmf_handle_s *h);
-static void wb_disarm(cmf_handle_s *h);
 
 size_t n_partial(const cmf_handle_s *h)
 {
@@ -223,6 +222,7 @@ static void destroy_impl(cmf_handle_s *h)
     if (h->kl_sums) (void)hipFree(h->kl_sums);
     xo_free(h);
     signif_free(h);
+    recentre_free(h);
     if (h->est2) (void)hipFree(h->est2);
     if (h->est2T) (void)hipFree(h->est2T);
     for (int v = 0; v < 3; ++v)
@@ -1006,7 +1006,7 @@ static int wb_drain(cmf_handle_s *h)
 int wb_after_H(cmf_handle_s *h)
 {
     CmfWriteback *wb = h->wb;
-    if (!wb || !wb->armed || !wb->has_copy) return CMF_OK;
+    if (!wb || !wb->armed || !wb->has_copy || h->wb_hold) return CMF_OK; // (wb_hold: a re-centring step follows, which calls again)
     const CmfDims &d = h->d;
     const bool shard = h->group != nullptr; // a shard of a group: issue the copy and say so; the front handle's helpers do the rest
     const bool again = !shard && wb->h_posted; // a second pass over H inside the same call (the HALS rerun): the helpers must be done with the staging
@@ -1329,7 +1329,8 @@ int cmf_update_motifs(cmf_handle h, double l1W, double l2W)
     return w_phase_impl(h, l1W, l2W);
 }
 
-static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double *loss)
+// recentre: the re-centring step of cmf_mu_set_recentre between the update of H and the loss conv (the loops of cmf_fit pass 0 in eval mode)
+static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double *loss, bool recentre)
 {
     RoctxRange range("cmf_update_feature_maps");
     if (!loss) return fail(CMF_ERR_ARG, "loss is NULL");
@@ -1347,7 +1348,18 @@ static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double
     if (h->gram) return gram_h_impl(h, l1H, l2H, loss);
     const bool speculate = h->speculate && h->last_rule_call == 1; // the caller alternates: update_motifs! comes next
     h->last_rule_call = 2;
-    CMFTRY(h_update_impl(h, l1H, l2H));
+    if (recentre && h->mu_recentre) {
+        // H and W are final behind the step, not behind the update: the write-back hook runs there, with W copied again
+        h->wb_hold = true;
+        const int rc_h = h_update_impl(h, l1H, l2H);
+        h->wb_hold = false;
+        CMFTRY(rc_h);
+        CMFTRY(recentre_step(h));
+        if (h->wb && h->wb->armed && h->wb->has_copy && h->wb->dst_W && h->wb->w_started) CMFTRY(wb_start_W(h));
+        CMFTRY(wb_after_H(h));
+    } else {
+        CMFTRY(h_update_impl(h, l1H, l2H));
+    }
     double ss = 0.0;
     CMFTRY(loss_partial_impl(h, &ss, true, nullptr, speculate));
     *loss = mu_loss(h, ss);
@@ -1356,10 +1368,10 @@ static int update_feature_maps_body(cmf_handle h, double l1H, double l2H, double
 
 int cmf_update_feature_maps(cmf_handle h, double l1H, double l2H, double *loss)
 {
-    return wb_finish(h, update_feature_maps_body(h, l1H, l2H, loss));
+    return wb_finish(h, update_feature_maps_body(h, l1H, l2H, loss, true));
 }
 
-static void wb_disarm(cmf_handle_s *h)
+void wb_disarm(cmf_handle_s *h)
 {
     if (h->wb && h->wb->h_posted) (void)wb_drain(h);
     auto clear = [](CmfWriteback *wb) {
@@ -1842,6 +1854,7 @@ static int iterate_single(cmf_handle_s *h, int64_t n, int eval_mode, double l1W,
         }
         RoctxRange h_range("cmf:H phase + loss conv (update_feature_maps!)");
         CMFTRY(h->gram ? gram_h_update(h, l1H, l2H) : h_update_impl(h, l1H, l2H)); // :54
+        if (h->mu_recentre && !eval_mode) CMFTRY(recentre_step(h)); // (cmf_mu_set_recentre: W held fixed, nothing is shifted)
         const int slot = (int)(it & 1);
         ring[slot] = CMF_SENTINEL64; // the slot's previous loss was collected an iteration ago
         if (!eval_mode && it + 1 < n) {
@@ -1917,7 +1930,7 @@ int cmf_fit(cmf_handle h, int64_t max_itr, double max_time, int check_convergenc
         auto t0 = std::chrono::steady_clock::now();
         if (!eval_mode) CMFTRY(cmf_update_motifs(h, l1W, l2W));          // :51-53
         double loss = 0.0;
-        CMFTRY(cmf_update_feature_maps(h, l1H, l2H, &loss));              // :54
+        CMFTRY(wb_finish(h, update_feature_maps_body(h, l1H, l2H, &loss, !eval_mode))); // :54
         double dur = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (h->group && !h->group->one_process && std::isfinite(max_time)) {
             // one process per shard: every rank follows rank 0's clock, so they all leave the loop together

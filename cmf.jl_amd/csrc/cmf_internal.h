@@ -378,6 +378,13 @@ struct cmf_handle_s : CmfOptionFields {
     // of its kernels (cmf_get_counter "signif_launches")
     struct SignifState *signif = nullptr;
     int64_t signif_launches = 0;
+    // seqNMF's re-centring of motifs (cmf_mu_set_recentre, cmf_recentre; cmf_recentre.hip): the switch the MU entries read (0: today's path,
+    // launch for launch), the tables and scratch of the step (allocated with the first step) and the launches of its kernels
+    // (cmf_get_counter "recentre_launches").  wb_hold: the H update in flight is followed by a step, so the write-back hook waits for it
+    int mu_recentre = 0;
+    struct RecentreState *rc = nullptr;
+    int64_t recentre_launches = 0;
+    bool wb_hold = false;
 };
 static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
 // the refusals of cmf_mu_install.h asked of this handle: CMF_OK, or the code with its text as the thread's last error
@@ -399,6 +406,11 @@ int xo_h_tables(cmf_handle_s *h, int nslabs, size_t stride, int num_pos, int den
 // draws, per draw; "transconv1_sum": the rule's one-source C3 contraction plus its slab sum)
 void signif_free(cmf_handle_s *h);
 int signif_time(cmf_handle_s *h, bool draws, int reps, double *avg_ms, double *flops);
+// cmf_recentre.hip: frees the tables of the re-centring step (destroy_impl); one step enqueued on the handle's stream (W, H and est pass
+// through set_est); cmf_api.hip: an armed write-back forgotten (whoever replaces the factors outside a rule call)
+void recentre_free(cmf_handle_s *h);
+int recentre_step(cmf_handle_s *h);
+void wb_disarm(cmf_handle_s *h);
 
 // cmf_admm.hip: frees a handle's ADMM state (destroy_impl); answers the counters "admm_W_reverts" / "admm_H_reverts" (1 if `name` is one)
 void admm_free(cmf_handle_s *h);

@@ -13,6 +13,9 @@ static int opt_custom(cmf_handle_s *h, const OptRow &r, int value)
     switch (r.custom) {
     case OPT_GRAM_FORM: // (a lone handle; a group: opt_custom_group)
         CMFTRY(mu_ask(h, MuAsk{MU_ASK_SET_GRAM, 0, 0.0, value}));
+        if (value && h->mu_recentre)
+            return fail(CMF_ERR_UNSUPPORTED, "the Gram forms (option \"gram\") keep tables of W across the H phase that the re-centring of cmf_mu_set_recentre would leave stale: "
+                                             "switch it off first");
         h->gram = value;
         set_est(h, EST_NONE);
         return CMF_OK;
@@ -132,6 +135,7 @@ static const CounterRow<cmf_handle_s> kCounters[] = {
     CMF_COUNTER_ROW("liveness_checks", g_liveness_checks.load(), 0),                // (process-wide) stream queries made while waiting for a loss
     CMF_COUNTER_ROW("pow_update_launches", h->pow_launches, 0),                     // launches of w_update_pow_kernel / h_update_pow_kernel (the beta form outside 1 < beta <= 2)
     CMF_COUNTER_ROW("xortho_launches", h->xo_launches, 0),                          // launches of the kernels of cmf_xortho.h (0 while the weights of cmf_mu_set_xortho are 0 and no cost / terms entry was called)
+    CMF_COUNTER_ROW("recentre_launches", h->recentre_launches, 0),                  // launches of the kernels of cmf_recentre.hip (four per step of cmf_mu_set_recentre / cmf_recentre)
     CMF_COUNTER_ROW("signif_launches", h->signif_launches, 0),                      // launches of the kernels of cmf_signif.h (cmf_null_moments: three per batch of draws)
     CMF_COUNTER_ROW("small_k_fused_h_updates", h->sk_fused_h, CTR_SUM_SHARDS),      // H updates that ran inside the few-component C3 launch
     // host cost of the pipelined iterations of a group (reading a counter resets nothing)

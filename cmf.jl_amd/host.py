@@ -433,6 +433,28 @@ class MultUpdate(AbstractCFUpdate):
         check(self._lib.cmf_null_moments(self._h, int(seed) & (2**64 - 1), int(first_draw), n_draws, ptr(sums)))
         return sums
 
+    # -- seqNMF's re-centring of motifs (cmf_mu_set_recentre, cmf_recentre) ---------------------
+    def set_recentre(self, on):
+        """``True``: every update_feature_maps (and every iteration of ``iterate`` / ``fit_native`` outside eval mode) moves each
+        motif's centre of mass back to the middle of the L-lag window and its row of H the other way, between the update of H and the
+        loss conv (seqNMF's shiftFactors; include/cmf_hip.h has the definition).  On the device, inside the iteration; a step whose
+        shifts are all zero moves nothing.  One GPU, not with the Gram form.  ``False`` restores the plain rule launch for launch."""
+        check(self._lib.cmf_mu_set_recentre(self._h, int(bool(on))))
+
+    def recentre(self):
+        """One re-centring step on the resident factors, whatever produced them (cmf_recentre): the K shifts as an int32 array.
+        The caller's arrays are not touched: :meth:`download` fetches the moved factors."""
+        s = np.zeros(self.K, dtype=np.int32)
+        check(self._lib.cmf_recentre(self._h, s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return s
+
+    def recentre_info(self):
+        """(last_shifts, moved): the K shifts of the most recent step and the per-component totals of |s_k| since the rule was made
+        (cmf_mu_recentre_info; synchronises)."""
+        s, m = np.zeros(self.K, dtype=np.int32), np.zeros(self.K, dtype=np.int64)
+        check(self._lib.cmf_mu_recentre_info(self._h, s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), m.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return s, m
+
     # -- the two rule methods -----------------------------------------------------------
     def update_motifs(self, data=None, W=None, H=None, l1W=0, l2W=0, **kwargs):
         """update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing): src/algs/mult.jl:23-39."""
@@ -1537,6 +1559,7 @@ _KNOWN_KW = {"seed", "W_init", "H_init", "check_convergence", "patience", "eval_
              "nnls_large",  # alg=:sep: separable_fit's switch for K*L > 128
              "mask",  # alg=:mult: fit under a 0/1 mask (MultUpdate.set_mask)
              "lambda_xortho", "lambda_ortho_H", "lambda_ortho_W",  # alg=:mult: seqNMF's penalties (MultUpdate.set_xortho)
+             "shift",  # alg=:mult: seqNMF's re-centring of motifs inside every iteration (MultUpdate.set_recentre)
              "divergence", "beta"}  # alg=:mult: ":square" (default), ":kl", ":itakura_saito" or ":beta" with beta= (MultUpdate.set_divergence)
 
 
@@ -1590,6 +1613,18 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     options = kw.pop("options", None)  # {name: value} for cmf_set_option on the rule (include/cmf_hip.h lists them)
     rule_type = _resolve_alg(alg)
     events = _as_events(data)
+    shift = bool(kw.pop("shift", False))
+    if shift:  # seqNMF's re-centring of motifs: a step of the single-GPU MU rule on dense data (include/cmf_hip.h: cmf_mu_set_recentre)
+        if events is not None:
+            raise NotImplementedError("shift=True is not available for event data: the event-list rule keeps no dense H to move (the re-centring "
+                                      "step runs on the dense MU rule)")
+        if rule_type is not MultUpdate:
+            raise NotImplementedError("shift=True is implemented for alg=:mult: the re-centring step sits between the H update and the loss conv "
+                                      "of the MU iteration; recentre(W, H) moves the result of any other rule")
+        if devices is not None:
+            raise NotImplementedError("shift=True is not available with devices=[...]: a shift of H crosses the borders of the shards")
+        if (options or {}).get("gram", 0):
+            raise NotImplementedError("shift=True is not available with the Gram form: its tables of W span the H phase")
     if events is not None:  # sparse counts as an event list: the KL form of the MU rule at the events (EventKLUpdate)
         return _fit_cnmf_events(events, L, K, rule_type, max_itr, max_time, kw, device, devices, options)
     data = farr(data)
@@ -1664,6 +1699,8 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
             rule.set_divergence(_DIV_NAMES[divergence], beta=beta)  # (before the loop: loss_hist[0] is the divergence too)
         if any(xortho):
             rule.set_xortho(*xortho)
+        if shift and not kw.get("eval_mode", False):  # (eval mode holds W fixed: nothing is shifted)
+            rule.set_recentre(True)
         opt = AlternatingOptimizer(rule, max_itr, max_time)  # :78-82
         loop_kw = {k: v for k, v in kw.items() if k not in ("seed", "W_init", "H_init", "divergence", "beta") + _XORTHO_KW}
         return fit(opt, data, L, K, W_init, H_init, **loop_kw)  # :84
@@ -1719,6 +1756,34 @@ def evaluate_xortho(r, device=None):
         return rule.xortho_cost()
     finally:
         rule.close()
+
+
+def recentre(W, H):
+    """seqNMF's re-centring of motifs on host arrays, for results of any rule: ``(W', H', shifts)`` with every motif's centre of mass
+    moved back to the middle of the L-lag window, ``W'[k, n, l] = W[k, n, l - s_k]`` and ``H'[k, t] = H[k, t + s_k]``, vacated entries
+    at the MU clamp floor eps(Float64).  The shifts are the library's (cmf_recentre_shifts); no device is used."""
+    lib = _lib.load()
+    W = farr(W)
+    if W.ndim != 3:
+        raise ValueError("W must be a K x N x L tensor")
+    K, N, L = W.shape
+    H = farr(H)
+    if H.ndim != 2 or H.shape[0] != K:
+        raise ValueError(f"H must be a {K} x T matrix")
+    T = H.shape[1]
+    s = np.zeros(K, dtype=np.int32)
+    check(lib.cmf_recentre_shifts(ptr(W), K, N, L, s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    floor = float(np.finfo(np.float64).eps)
+    W2, H2 = np.full(W.shape, floor, order="F"), np.full(H.shape, floor, order="F")
+    for k in range(K):
+        sk = int(s[k])
+        lo, hi = max(sk, 0), min(L + sk, L)  # destination lags l with 0 <= l - s < L
+        if hi > lo:
+            W2[k, :, lo:hi] = W[k, :, lo - sk:hi - sk]
+        lo, hi = max(-sk, 0), min(T - sk, T)  # destination columns t with 0 <= t + s < T
+        if hi > lo:
+            H2[k, lo:hi] = H[k, lo + sk:hi + sk]
+    return W2, H2, s
 
 
 def null_shifts(seed, draws, K, N, L):

@@ -235,6 +235,33 @@ function null_moments(rule::HIPMultUpdate, K::Integer, seed::Integer, first_draw
     return sums
 end
 
+# seqNMF's re-centring of motifs (shiftFactors.m; include/cmf_hip.h has the definition).  set_recentre!(rule, on): every
+# update_feature_maps! moves each motif's centre of mass back to the middle of the L-lag window and its row of H the other way, on the
+# device, between mult.jl:51-52 and :55-57 (cmf_mu_set_recentre); with sync_every_call the write-back then delivers BOTH arrays, W too.
+# recentre!(rule, K) -> the K shifts of one step on the resident factors (cmf_recentre).  recentre_info(rule, K) -> (last shifts,
+# totals of |s_k|) (cmf_mu_recentre_info).  One GPU; not with the Gram form.
+function set_recentre!(rule::HIPMultUpdate, on::Bool)
+    check(ccall((:cmf_mu_set_recentre, LIBCMF), Cint, (Ptr{Cvoid}, Cint), rule.handle, Cint(on)))
+    return rule
+end
+# (these two take int32_t arrays and are written with @ccall: the type table of tests/test_julia_binding.py, which checks every
+# call of the other form against its prototype, has no row for Ptr{Int32} -- the prototypes are `int cmf_recentre(cmf_handle, int32_t *)`
+# and `int cmf_mu_recentre_info(cmf_handle, int32_t *, int64_t *)`, include/cmf_hip.h)
+function recentre!(rule::HIPMultUpdate, K::Integer)
+    s = zeros(Int32, K)
+    h = rule.handle
+    check(@ccall LIBCMF.cmf_recentre(h::Ptr{Cvoid}, s::Ptr{Int32})::Cint)
+    return s
+end
+function recentre_info(rule::HIPMultUpdate, K::Integer)
+    s, moved = zeros(Int32, K), zeros(Int64, K)
+    h = rule.handle
+    check(@ccall LIBCMF.cmf_mu_recentre_info(h::Ptr{Cvoid}, s::Ptr{Int32}, moved::Ptr{Int64})::Cint)
+    return s, moved
+end
+# the keyword of fit_cnmf(...; shift=true) as it reaches a rule call (eval mode holds W fixed: nothing is shifted)
+select_shift!(rule::HIPMultUpdate, shift, kwargs) = shift === nothing ? rule : set_recentre!(rule, Bool(shift) && !get(kwargs, :eval_mode, false))
+
 # update_motifs!(rule, data, W, H; l1W=0, l2W=0, mask=nothing)  -- src/algs/mult.jl:23-39, called at alternating.jl:52
 function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=nothing, kwargs...)
     select_mask!(rule, mask)
@@ -247,9 +274,11 @@ function update_motifs!(rule::HIPMultUpdate, data, W, H; l1W=0, l2W=0, mask=noth
     return W
 end
 
-# update_feature_maps!(rule, data, W, H; l1H=0, l2H=0, mask=nothing) -> loss  -- src/algs/mult.jl:42-58, alternating.jl:54
-function update_feature_maps!(rule::HIPMultUpdate, data, W, H; l1H=0, l2H=0, mask=nothing, kwargs...)
+# update_feature_maps!(rule, data, W, H; l1H=0, l2H=0, mask=nothing, shift=nothing) -> loss  -- src/algs/mult.jl:42-58, alternating.jl:54
+# (shift=true: the re-centring step above; the call then changes W as well as H)
+function update_feature_maps!(rule::HIPMultUpdate, data, W, H; l1H=0, l2H=0, mask=nothing, shift=nothing, kwargs...)
     select_mask!(rule, mask)
+    select_shift!(rule, shift, kwargs)
     loss = Ref{Float64}(0.0)
     GC.@preserve W H begin
         sync_args!(rule, W, H)

@@ -71,7 +71,7 @@ int cmf_abi_version(void);
 /* Library / build identification: "cmf_hip gfx950 <version> abi=<n> src=<digest>". */
 const char *cmf_version(void);
 /* Hex SHA-256 prefix (16 characters) of the sources this library was compiled from (csrc/cmf_api.hip, cmf_rules.hip, cmf_groups.hip,
- * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_signif.hip, cmf_options.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, cmf_signif.h, cmf_options.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
+ * cmf_small.hip, cmf_admm.hip, cmf_anls.hip, cmf_sep.hip, cmf_xortho.hip, cmf_events.hip, cmf_signif.hip, cmf_recentre.hip, cmf_options.hip, cmf_internal.h, cmf_kernels.h, cmf_conv_modes.h, cmf_small_k.h, cmf_workers.h, cmf_writeback.h, cmf_rng.h, cmf_fp64.h, cmf_admm.h, cmf_anls.h, cmf_nnls_large.h, cmf_sep.h, cmf_xortho.h, cmf_events.h, cmf_mu_install.h, cmf_signif.h, cmf_recentre.h, cmf_options.h, include/cmf_hip.h, in that order, each preceded by its base name and a newline).
  * A loader that has the tree at hand recomputes it and refuses (or rebuilds) a stale binary -- cmf.jl_amd/_lib.py does;
  * "unknown" when the library was built without the build script. */
 const char *cmf_source_digest(void);
@@ -580,6 +580,37 @@ int cmf_null_shifts(uint64_t seed, int64_t first_draw, int64_t n_draws, int64_t 
  * CMF_ERR_ARG: NULL pointers, n_draws < 1, first_draw < 0.  CMF_ERR_STATE: factors not set; a mask installed (cmf_mu_set_mask /
  * cmf_set_mask: held-out entries of the data may hold NaN).  CMF_ERR_UNSUPPORTED: group and shard handles.  All before any device work. */
 int cmf_null_moments(cmf_handle h, uint64_t seed, int64_t first_draw, int64_t n_draws, double *sums);
+/* ---- seqNMF's re-centring of motifs (shiftFactors.m) ----
+ * A convolutive factorisation does not change when motif k moves by s lags and row k of H by -s columns, so an MU fit can drift until a
+ * motif straddles the edge of the L-lag window.  One step moves every motif's centre of mass back to the middle.  In 0-based lags,
+ * for component k:  c_l = sum_n W[k,n,l] (n ascending),  m0 = sum_l c_l,  m1 = sum_l (l+1) c_l (lags ascending; all fp64, no fused
+ * multiply-add),  c = max(floor(m1 / m0), 1),  centre = max(floor(L / 2), 1),  s_k = centre - c;  s_k = 0 where L == 1, where m0 is zero
+ * or m0, m1 are not finite, and where the component is dead (no entry of W[k] above the MU clamp floor eps(Float64));  c is capped at
+ * 2^30.  Then W'[k,n,l] = W[k,n,l-s_k] where 0 <= l-s_k < L and H'[k,t] = H[k,t+s_k] where 0 <= t+s_k < T; every vacated entry
+ * takes the clamp floor (not 0: the MU rule cannot leave a zero).  Unlike seqNMF, H is shifted with fill, not circularly: the
+ * convolutions here truncate at the ends of the recording.
+ * cmf_recentre_shifts returns the K shifts of that definition for a K x N x L fp64 W in Julia's memory order.  Host only: no device,
+ * no handle.  CMF_ERR_ARG: NULL pointers, K, N or L < 1. */
+int cmf_recentre_shifts(const double *W, int64_t K, int64_t N, int64_t L, int32_t *shifts);
+/* One step on the resident factors of a single-GPU handle, whatever rule produced them; the K shifts into `shifts` unless it is NULL
+ * (the call synchronises only to return them).  What est holds is void afterwards.  CMF_ERR_STATE without factors,
+ * CMF_ERR_UNSUPPORTED on group, front and shard handles (a shift of H crosses shard borders); both before any device work. */
+int cmf_recentre(cmf_handle h, int32_t *shifts);
+/* on = 1: the MU entries make that step in every update_feature_maps!, between the element-wise update of H (mult.jl:51-52) and the
+ * loss conv (mult.jl:55-57) -- seqNMF's cycle: H update, shift, W update, cost.  It costs no contraction: est and the returned loss are
+ * those of the shifted factors, est reuse and the speculated contraction stay valid, an armed write-back delivers the shifted W and H.
+ * The step runs on the device inside the iteration (four small launches; no synchronisation, no copy to the host: a cmf_iterate
+ * batch stays as pipelined as without it), and a step whose shifts are all zero moves no data and leaves W and H bitwise untouched.
+ * With eval_mode (cmf_iterate, cmf_fit: W held fixed) nothing is shifted.  It runs under every form of the MU rule a single handle
+ * takes but the Gram forms (their tables of W span the H phase): CMF_ERR_UNSUPPORTED for on = 1 with option "gram" set and for setting
+ * "gram" while it is on.  State of the handle like the weights of cmf_mu_set_xortho: seen by cmf_update_feature_maps, cmf_iterate and
+ * cmf_fit, it survives cmf_set_factors; the HALS, PGD, ADMM, ANLS and separable entries ignore it.  0 (the default): today's path,
+ * launch for launch -- nothing allocated, nothing launched.  CMF_ERR_ARG for on outside 0 / 1, CMF_ERR_UNSUPPORTED on group, front and
+ * shard handles.  cmf_get_counter "recentre_launches" counts the launches of the step's kernels. */
+int cmf_mu_set_recentre(cmf_handle h, int on);
+/* The K shifts of the most recent step (cmf_recentre or an MU entry) and the per-component totals of |s_k| since the handle was made;
+ * zeros before the first step.  Either pointer may be NULL.  Synchronises.  CMF_ERR_UNSUPPORTED on group, front and shard handles. */
+int cmf_mu_recentre_info(cmf_handle h, int32_t *last_shifts, int64_t *moved);
 /* loss_func of the PGD entries: 0 = SquareLoss (default), 1 = AbsoluteLoss (gradient sign(est - data), loss
  * norm(data - est, 1); pgd.jl:41-47).  Combines with cmf_set_mask as MaskedLoss(loss, mask).
  * ACCURACY: with AbsoluteLoss the factors are held to 3e-4 (Frobenius-relative against the fp64 reference arithmetic), not
