@@ -14,7 +14,7 @@ Dropping or doubling any time row, column, lag or component block then moves som
 preconditions() bounds every num / den by 2^20, so such an error is at least 8 ulp of fp32.
 
 The shape table SHAPES is shared with tests/test_gpu_divergence_paths.py, which holds the divergence forms of the rule to their fp64
-restatements element by element on the same factors (make_divergence_problem, divergence_half, sensitivity, check_elementwise below),
+restatements element by element on the same factors, the Itakura-Saito and beta forms under a 0/1 mask among them (make_divergence_problem, divergence_half, sensitivity, check_elementwise below),
 and with tests/test_gpu_exact_masked_mu.py and tests/test_gpu_exact_pgd.py, which hold the MU rule under a 0/1 mask and the PGD rule to
 their references on it (mu_mask, make_pgd_problem, pgd_half, pgd_preconditions).  The last section holds the HALS sweeps' own table
 (HALS_SHAPES), the mirror of their plan, their element-wise check and the mutations of their restatement (tests/test_gpu_exact_hals.py),
@@ -398,11 +398,11 @@ def cu_plan(N, T, K, L, cfg=None, n_cu=N_CU):
 
 
 # The storing epilogues and the cut tiles' loss partials differ per conv family: the masked MU rule, the PGD rule and the divergence
-# forms "is" and "kl_mask" run at 32 CUs on one row per conv3 form and two few-component rows (quarter pieces only; whole tiles + tail)
+# forms "is", "kl_mask", "is_mask" and "beta050_mask" run at 32 CUs on one row per conv3 form and two few-component rows (quarter pieces only; whole tiles + tail)
 CU_EPILOGUE_N_CU = 32
 CU_EPILOGUE_ROWS = [r for r in CU_SHAPES[32] if r[:4] in {(130, 448, 32, 20), (130, 700, 32, 20), (250, 3200, 32, 20), (250, 6400, 32, 20),
                                                          (250, 7040, 32, 20), (90, 610, 5, 7), (1000, 572, 8, 10)}]
-CU_EPILOGUE_FORMS = ("is", "kl_mask")
+CU_EPILOGUE_FORMS = ("is", "kl_mask", "is_mask", "beta050_mask")
 
 # The HALS sweeps under fewer CUs: rows of HALS_SHAPES (the bars of profiles/exact_hals.txt are made from them), each with the sweep
 # configurations to run and what hals_plan must say at that count: (cfg, pullers per row -- 0: the stage pipeline --, chased or not).
@@ -435,9 +435,35 @@ EPS = float(np.finfo(np.float64).eps)
 # 1 to its bulk value near 1.5 L, and P = data e^(beta - 2) of the forms with beta < 1 (Itakura-Saito: beta = 0) then spreads over
 # L^2 (L^1.5) inside one sum of the H half: a bulk term of the first columns' numerators is below the bar, whatever range data has.
 # With data / est in the narrow range instead, P spreads like Q does and every row meets the condition sensitivity >= 4 bars.
+# The last three are Itakura-Saito and beta under the MU rule's 0/1 mask (the option pq_mask: the sentinel families of cmf_kernels.h),
+# restated by tests/masked_pq_mu_restatement.py; zeros and relative data follow the unmasked twin.
 FORMS = {"kl": (":kl", None, False, True, False), "kl_mask": (":kl", None, True, True, False),
          "is": (":itakura_saito", None, False, False, True), "beta050": (":beta", 0.5, False, True, True),
-         "beta150": (":beta", 1.5, False, True, False)}
+         "beta150": (":beta", 1.5, False, True, False),
+         "is_mask": (":itakura_saito", None, True, False, True), "beta050_mask": (":beta", 0.5, True, True, True),
+         "beta150_mask": (":beta", 1.5, True, True, False)}
+JUNK = (np.nan, np.inf, -1.0, 0.0)  # what the library is handed under the mask of the last three (junk_under_mask)
+
+
+def pq_masked(form):
+    """Whether the form is one of the masked two-array forms (Itakura-Saito or beta under the mask: the option pq_mask)."""
+    kind, _, masked = FORMS[form][:3]
+    return masked and kind != ":kl"
+
+
+def pq_beta(form):
+    """The beta tests/masked_pq_mu_restatement.py knows the form by (0: Itakura-Saito)."""
+    return FORMS[form][1] or 0.0
+
+
+def junk_under_mask(X, mask, seed=0):
+    """X with NaN, +inf, -1 and 0 in turn (by the entry's hash) wherever mask == 0: what the library is given under a masked two-array
+    form.  The restatement never looks there (the fp64 reference is computed from X itself), so a sentinel copy that lets one raw
+    value through shows as a non-finite or wrong element."""
+    N, T = X.shape
+    nn, tt = np.meshgrid(np.arange(N), np.arange(T), indexing="ij")
+    junk = np.asarray(JUNK)[(_hash(nn, tt, salt=seed * 4 + 7) % np.uint64(len(JUNK))).astype(np.int64)]
+    return np.asfortranarray(np.where(np.asarray(mask) != 0, X, junk))
 
 
 def make_divergence_problem(N, T, K, L, family, zeros=False, seed=0, relative=False):
@@ -476,6 +502,10 @@ def divergence_sources(form, X, mask, W, H, cdtype=np.float64, edtype=np.float64
     kind, beta, masked = FORMS[form][:3]
     if kind == ":kl":
         return (mk.ratio(mk.MaskedKL(X, mask), W, H, cdtype, edtype), mask) if masked else (kr.ratio(X, W, H, cdtype, edtype), None)
+    if masked:  # (select(mask, data, 1), then P and Q with exact 0 where mask == 0)
+        import masked_pq_mu_restatement as pm
+
+        return pm.pq(pm.check_data(X, mask, pq_beta(form))[0], mask, W, H, pq_beta(form), cdtype, edtype)
     if kind == ":itakura_saito":
         return ir.pq(X, W, H, cdtype, edtype)
     return br.pq(X, W, H, beta, cdtype, edtype)
@@ -491,6 +521,11 @@ def divergence_loss(form, X, mask, W, H, cdtype=np.float64, edtype=np.float64):
     kind, beta, masked = FORMS[form][:3]
     if kind == ":kl":
         return mk.masked_kl_loss(mk.MaskedKL(X, mask), W, H, cdtype, edtype) if masked else kr.kl_loss(X, W, H, cdtype, edtype)
+    if masked:
+        import masked_pq_mu_restatement as pm
+
+        xs, count = pm.check_data(X, mask, pq_beta(form))
+        return pm.masked_loss(xs, mask, count, W, H, pq_beta(form), cdtype, edtype)
     if kind == ":itakura_saito":
         return ir.is_loss(X, W, H, cdtype, edtype)
     return br.beta_loss(X, W, H, beta, cdtype, edtype)
@@ -508,7 +543,7 @@ def divergence_half(form, family, X, mask, W, H, cdtype=np.float64, edtype=np.fl
     K, N, L = W.shape
     T = H.shape[1]
     P, Q = divergence_sources(form, X, mask, W, H, cdtype, edtype)
-    a = dict(P=P, Q=Q, W=W, H=H, family=family)
+    a = dict(P=P, Q=Q, W=W, H=H, family=family, form=form, X=X, mask=mask)
     if corrupt:
         corrupt("sources", a)
     if family == "W":

@@ -160,6 +160,7 @@ def test_divergence_half_is_the_restatements(shape):
     import is_mu_restatement as ir
     import kl_mu_restatement as kr
     import masked_kl_mu_restatement as mk
+    import masked_pq_mu_restatement as pm
 
     N, T, K, L = shape
     for family in ("W", "H"):
@@ -174,6 +175,10 @@ def test_divergence_half_is_the_restatements(shape):
                     args, kw, mod = (mk.MaskedKL(data, mask), Wr, Hr), dict(cdtype=dt), mk
                 elif kind == ":kl":
                     args, kw, mod = (data, Wr, Hr), dict(cdtype=dt), kr
+                elif masked:  # (update_feature_maps takes the observed count between the mask and the factors)
+                    xs, count = pm.check_data(data, mask, ep.pq_beta(form))
+                    args = (xs, mask, Wr, Hr, ep.pq_beta(form)) if family == "W" else (xs, mask, count, Wr, Hr, ep.pq_beta(form))
+                    kw, mod = dict(cdtype=dt, edtype=dt), pm
                 elif kind == ":itakura_saito":
                     args, kw, mod = (data, Wr, Hr), dict(cdtype=dt, edtype=dt), ir
                 else:
@@ -233,7 +238,10 @@ def test_sensitivity_from_the_arrays(shape):
     assert np.isclose(ep._min_positive_terms("W", a["P"], W, H)[k, n, lag], terms.min(), rtol=0)
 
 
-def _corruptions(family, has_q):
+SENTINEL = -1.0  # cmf_kernels.h CMF_PQ_HELD_OUT
+
+
+def _corruptions(family, has_q, pq_masked=False):
     """name -> corrupt(stage, arrays) for divergence_half: the damage a seam error in an epilogue or a contraction would do."""
     big = 1.0 / ep.EPS
 
@@ -284,9 +292,43 @@ def _corruptions(family, has_q):
                 n, l = [(n, l) for l in range(a["W"].shape[2]) for n in np.flatnonzero(a["W"][k, :, l] != 0) if a["P"][n, t + l] > 0][0]
                 a["num"][k, t] -= a["P"][n, t + l]
 
+    # What only a sentinel family (Itakura-Saito or beta under the mask) can suffer, inside the strip of strip() above:
+    def unselected(a):
+        """(P, Q) of the form before the select, from the data with the sentinel under the mask (cmf_kernels.h CMF_PQ_HELD_OUT): Q of a
+        held-out entry is 1 / e (e^(beta - 1)), P is the form's product taken on the sentinel, (x q) q or x e^(beta - 2).  (The device's
+        beta P has a select x > 0 of its own, which happens to give 0 for the sentinel; the damage modelled is the product.)"""
+        import kl_mu_restatement as kr
+
+        beta, xs = ep.pq_beta(a["form"]), np.where(a["mask"] != 0, a["X"], SENTINEL)
+        e = kr.tensor_conv(a["W"], a["H"]) + ep.EPS
+        return ((xs / e) / e, 1.0 / e) if beta == 0 else (xs * e ** (beta - 2.0), e ** (beta - 1.0))
+
+    def leak(which):
+        def f(stage, a):  # a select missing in one piece of a cut tile: the held-out entries of the strip keep the unselected value
+            if stage == "sources":
+                held = np.zeros(a["mask"].shape, bool)
+                held[8:12, 192:256] = a["mask"][8:12, 192:256] == 0
+                assert held.any()
+                a[which] = np.where(held, unselected(a)[0 if which == "P" else 1], a[which])
+        return f
+
+    def xst_off(stage, a):  # the [n][t] sentinel copy disagrees with the [t][n] one: its mask lies four columns off inside one 64-column block
+        if stage == "sources":
+            import masked_pq_mu_restatement as pm
+
+            m = a["mask"].copy()
+            m[:, 192:256] = a["mask"][:, 196:260]
+            assert (m != a["mask"]).any()
+            # (make_divergence_problem's data is clean under the mask too: the entries the shifted mask lets through are ordinary terms)
+            a["P"], a["Q"] = pm.pq(a["X"], m, a["W"], a["H"], ep.pq_beta(a["form"]))
+
     out = {"strip_P": strip("P"), "double": double, "term": term, "lag" if family == "W" else "kpair": lag if family == "W" else kpair}
     if has_q:
         out.update(strip_Q=strip("Q"), pad=pad)
+    if pq_masked:
+        out.update(leak_Q=leak("Q"), leak_P=leak("P"))
+        if family == "W":
+            out.update(xst_off=xst_off)
     return out
 
 
@@ -296,7 +338,11 @@ def _corruptions(family, has_q):
 # 4 of 70 ... 130 units); what the norm passes is the single term -- and, at the sizes the GPU test adds, everything confined to one
 # tile: a 4 x 64 strip changes 4 of 2000 units by 2 of 210 terms (4e-4 of the norm at T = 6720, 5e-5 at config 2's T = 50000).  The
 # element-wise check flags every one, at every size, because its bar is per element.
-FROBENIUS_PASSES = {"term"}
+# The three damages of the sentinel families (leak_Q, leak_P, xst_off) touch a quarter of one strip's entries or of one block's columns.
+# The norm passes leak_P even on these small shapes: the sentinel is -1 where observed data is 16 and more, so a P taken on it is a
+# surplus term well below an ordinary term's size, in the sums of four units.  A leaked Q is a whole term and moves the norm by more
+# than 1e-4 here, as xst_off does.
+FROBENIUS_PASSES = {"term", "leak_P"}
 
 
 def test_elementwise_check_flags_what_frobenius_passes():
@@ -308,7 +354,10 @@ def test_elementwise_check_flags_what_frobenius_passes():
                 W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family, relative=ep.FORMS[form][4])
                 ref = ep.divergence_half(form, family, X, mask, W, H)
                 assert ep.check_elementwise(ref["new"].astype(np.float32), ref["new"], bars[form], names) is None
-                for name, corrupt in _corruptions(family, ref["Q"] is not None).items():
+                if ep.pq_masked(form):  # every 4 x 64 strip holds held-out entries, so leak_P and leak_Q damage something wherever the strip lies
+                    strips = (mask[:N // 4 * 4, :T // 64 * 64] == 0).reshape(N // 4, 4, T // 64, 64)
+                    assert strips.any(axis=(1, 3)).all()
+                for name, corrupt in _corruptions(family, ref["Q"] is not None, ep.pq_masked(form)).items():
                     got = ep.divergence_half(form, family, X, mask, W, H, corrupt=corrupt)["new"].astype(np.float32)
                     msg = ep.check_elementwise(got, ref["new"], bars[form], names)
                     assert msg is not None and " at k=" in msg, (name, form, family, (N, T, K, L))

@@ -1,5 +1,6 @@
-"""The divergence forms of the MU rule (KL, KL under a mask, Itakura-Saito, beta = 0.5 and 1.5) ELEMENT BY ELEMENT on every kernel path:
-the shape table of tests/test_exact_parity.py (exact_problems.SHAPES) under every configuration a form accepts.
+"""The divergence forms of the MU rule (KL, KL under a mask, Itakura-Saito, beta = 0.5 and 1.5, and Itakura-Saito, beta = 0.5 and 1.5
+under a 0/1 mask) ELEMENT BY ELEMENT on every kernel path: the shape table of tests/test_exact_parity.py (exact_problems.SHAPES) under
+every configuration a form accepts.
 
 On the integer problems of tests/exact_problems.py est = tensor_conv(W, H) is exact in fp32 on every conv path, so
 
@@ -14,7 +15,13 @@ On the integer problems of tests/exact_problems.py est = tensor_conv(W, H) is ex
 The loss: update_feature_maps! returns the restatement's at the form's loss bar; a spotlight problem (data = est but for 64 entries in
 each of six chosen tiles) holds compute_loss() to 1e-5 where each spotlight is 1e-3 of the sum, so that one lost or doubled partial
 of a cut tile fails by two orders of magnitude.  The launch counters are read per handle, so per form; the last test asserts that
-each form reached every path it can reach."""
+each form reached every path it can reach.
+
+The masked two-array forms (is_mask, beta050_mask, beta150_mask: the option pq_mask) read a sentinel copy of data in two layouts, written
+once at install.  The library is handed NaN, +inf, -1 and 0 under the mask (exact_problems.junk_under_mask) while the fp64 reference is
+computed from the clean array: one raw value let through, one strip of Q = 1 / e kept where 0 belongs, or the two copies disagreeing is a
+surplus or missing term of some sum -- many bars.  The first row installs in the other order too (divergence, then mask), and an
+all-ones mask gives the bits of the unmasked form on the large conv forms (test_all_ones_mask_is_the_unmasked_form_on_the_large_forms)."""
 import os
 import time
 
@@ -47,16 +54,23 @@ def cmf():
     return m
 
 
-def make_rule(cmf, form, cfg, X, mask, W, H):
+def make_rule(cmf, form, cfg, X, mask, W, H, junk=False, divergence_first=False):
+    """A handle in the form.  junk: a masked two-array form is handed exact_problems.junk_under_mask(X, mask) instead of X.
+    divergence_first: the divergence is installed before the mask (on the clean array: the unmasked check runs first)."""
     kind, beta, masked = FORMS[form][:3]
-    rule = cmf.MultUpdate(X, W, H)
+    assert not (junk and divergence_first)
+    rule = cmf.MultUpdate(ep.junk_under_mask(X, mask) if junk and ep.pq_masked(form) else X, W, H)
+    set_divergence = lambda: rule.set_divergence(kind, beta=beta) if beta else rule.set_divergence(kind)  # noqa: E731
     try:
         for name, value in cfg.items():
             rule.set_option(name, value)
         if masked:
-            rule.set_option("kl_mask", 1)
+            rule.set_option("pq_mask" if ep.pq_masked(form) else "kl_mask", 1)
+            if divergence_first:
+                set_divergence()
             rule.set_mask(mask)
-        rule.set_divergence(kind, beta=beta) if beta else rule.set_divergence(kind)
+        if not (masked and divergence_first):
+            set_divergence()
     except Exception:
         rule.close()
         raise
@@ -118,7 +132,7 @@ def run_divergence_config(cmf, form, cfg, K, refs, record=record):
     everything test_divergence_mu_paths asserts per configuration asserted."""
     (Ww, Hw, Xw, mask, aw), (Wh, Hh, Xh, _, ah) = refs
     W_ref, H_ref, lossH_ref = aw["new"], ah["new"], ah["loss"]
-    rule = make_rule(cmf, form, cfg, Xw, mask, Ww, Hw)
+    rule = make_rule(cmf, form, cfg, Xw, mask, Ww, Hw, junk=True)
     try:
         rule.update_motifs(l1W=L1, l2W=L2)
         Wg, _ = rule.download()
@@ -142,7 +156,7 @@ def run_divergence_config(cmf, form, cfg, K, refs, record=record):
     assert np.isfinite(li).all() and np.isfinite(Wi2).all() and np.isfinite(Hi2).all() and min(Wi2.min(), Hi2.min()) >= EPS
     check_same(Wi2, Wc2, "knl", "W after iterate(2)", cfg, "the call-by-call loop", c)
     check_same(Hi2, Hc2, "kt", "H after iterate(2)", cfg, "the call-by-call loop", c)
-    rule = make_rule(cmf, form, cfg, Xh, mask, Wh, Hh)
+    rule = make_rule(cmf, form, cfg, Xh, mask, Wh, Hh, junk=True)
     try:
         lh1 = rule.update_feature_maps(l1H=L1, l2H=L2)
         Wd, Hg = rule.download()
@@ -181,6 +195,17 @@ def test_divergence_mu_paths(cmf, N, T, K, L, configs, why, form, zeros):
         elif set(cfg) <= CONV_ONLY and set(base[0]) <= CONV_ONLY:
             check_same(Wg, base[1], "knl", "W half: W", cfg, base[0], c)
             check_same(Hg, base[2], "kt", "H half: H", cfg, base[0], c)
+    if ep.pq_masked(form) and shape == SHAPES[0][:4]:
+        # The other order of installation: divergence first (on the clean array, which the unmasked check reads), then the mask.  Both end in
+        # the same form, but the sentinel copies are written at another moment: the same bits.
+        for (W0, H0, X, mask, _), half, names in ((refs[0], 0, "knl"), (refs[1], 1, "kt")):
+            rule = make_rule(cmf, form, base[0], X, mask, W0, H0, divergence_first=True)
+            try:
+                rule.update_motifs(l1W=L1, l2W=L2) if half == 0 else rule.update_feature_maps(l1H=L1, l2H=L2)
+                got, c = rule.download()[half], counters(rule)
+            finally:
+                rule.close()
+            check_same(got, base[1 + half], names, "divergence installed before the mask: " + "WH"[half], base[0], "mask first", c)
     _done.add((shape, form, zeros))
     print(f"{form}{'+zeros' if zeros else ''} {shape} {why}: reference {t_ref:.2f} s, total {time.perf_counter() - t0:.2f} s; "
           f"worst so far {_worst[form][0]:.2e} (bar {BARS['bar'][form]:g}), loss {_worst[form][1]:.2e} (bar {BARS['lossbar'][form]:g})")
@@ -260,14 +285,16 @@ def run_spotlight(cmf, N, T, K, L, cfg, form, n_cu=ep.N_CU, record=record):
     background = IS_BACKGROUND * N * T if FORMS[form][0] == ":itakura_saito" else 0.0
     assert background <= 0.1 * SPOT_BAR * total
     want = ep.divergence_loss(form, X, mask, W, H)
-    norm = (X[mask != 0].sum() if masked else X.sum()) if FORMS[form][0] == ":kl" else float(N * T)
+    # (what the loss is divided by: the data's sum under KL, the number of entries -- observed entries under a mask -- otherwise)
+    norm = (X[mask != 0].sum() if masked else X.sum()) if FORMS[form][0] == ":kl" else float((mask != 0).sum()) if masked else float(N * T)
+    out = X[mask == 0].sum() if FORMS[form][0] == ":kl" else float((mask == 0).sum())  # cmf_masked_loss's second return over the held-out entries
     assert abs(want * norm - total) <= 1e-9 * total  # (the restatement's loss is the spotlights' terms: the background is 0 in fp64)
     rule = make_rule(cmf, form, cfg, X, mask, W, H)
     try:
         got = rule.compute_loss()
         if masked:  # the complement score counts the held-out spotlights and only them
             d, s = rule.masked_loss(complement=True)
-            assert abs(d - terms[held].sum()) <= SPOT_BAR * terms[held].sum() and abs(s - X[mask == 0].sum()) <= 1e-6 * s, (d, terms[held].sum(), s)
+            assert abs(d - terms[held].sum()) <= SPOT_BAR * terms[held].sum() and abs(s - out) <= 1e-6 * s, (d, terms[held].sum(), s, out)
             d1, s1 = rule.masked_loss(complement=False)
             assert abs(d1 - total) <= SPOT_BAR * total and abs(s1 - norm) <= 1e-6 * norm
         c = counters(rule)
@@ -283,6 +310,38 @@ def run_spotlight(cmf, N, T, K, L, cfg, form, n_cu=ep.N_CU, record=record):
 def test_spotlight_loss(cmf, N, T, K, L, cfg, form):
     run_spotlight(cmf, N, T, K, L, cfg, form)
     _done.add(("spot", (N, T, K, L), form))
+
+
+# ---- an all-ones mask is the unmasked form, on the table's large conv forms -------------------------------------------------------
+# tests/test_gpu_masked_pq_mu.py holds this on seven small shapes; here the shapes of exact_problems.CU_EPILOGUE_ROWS (one per conv3 form
+# at 32 CUs, two few-component rows) under the default configuration at the chip's own CU count.  With nothing held out the sentinel
+# copies are the data, so the masked families' epilogues must store the bits of the unmasked ones: W after the W half, H after the H half.
+ONES_SHAPES = [r[:4] for r in ep.CU_EPILOGUE_ROWS]
+ONES_FORMS = {"is": "is_mask", "beta050": "beta050_mask"}
+assert len(ONES_SHAPES) == 7
+
+
+@pytest.mark.parametrize("form", list(ONES_FORMS))
+@pytest.mark.parametrize("N,T,K,L", ONES_SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}x{s[3]}" for s in ONES_SHAPES])
+def test_all_ones_mask_is_the_unmasked_form_on_the_large_forms(cmf, N, T, K, L, form):
+    conv = [p for p in LAUNCH_PATHS if p.startswith("conv")]
+    for family, half, names in (("W", 0, "knl"), ("H", 1, "kt")):
+        W, H, X, mask = ep.make_divergence_problem(N, T, K, L, family, relative=FORMS[form][4])
+        got = []
+        for f, m in ((form, mask), (ONES_FORMS[form], np.ones_like(mask))):
+            rule = make_rule(cmf, f, dict(), X, m, W, H)
+            try:
+                rule.update_motifs(l1W=L1, l2W=L2) if half == 0 else rule.update_feature_maps(l1H=L1, l2H=L2)
+                got.append((rule.download()[half], counters(rule)))
+            finally:
+                rule.close()
+        (plain, cp), (ones, c) = got
+        assert np.isfinite(plain).all() and plain.min() >= EPS
+        check_same(ones, plain, names, f"{ONES_FORMS[form]} under an all-ones mask: " + "WH"[half], dict(), f"the unmasked {form}", c)
+        assert {p for p in conv if c[p]} == {p for p in conv if cp[p]}, (reached(c), reached(cp))
+        # (which conv forms the chip's own plan gave this shape: several of these rows share one at the full CU count)
+        print(f"all-ones {form} {(N, T, K, L)} {family} half: conv forms reached {sorted(p for p in conv if c[p])}")
+    _done.add(("ones", (N, T, K, L), form))
 
 
 # ---- coverage -------------------------------------------------------------------------------------------------------------------
@@ -303,8 +362,10 @@ NOT_FOR_DIVERGENCES = {
 # ... and per form: KL contracts one source in C2 (its denominators are sums), every other form two; the masked KL terms have no
 # 128 x 128 tiles (conv_on_tiles128: family KL_MASKED is not on them; the other forms reach conv2_kernel through the loss-only base alone,
 # which is what the spotlight handle with conv_kernel = 2 and reuse_est = 0 runs)
+# The masked two-array families are on the 128 x 128 tiles in their loss-only mode alone as well (conv_on_tiles128), the held-out score included.
 NOT_FOR_FORM = {"kl": {"hxt_kernel:nsrc2"}, "kl_mask": {"hxt_kernel:nsrc1", "conv2_kernel"}, "is": {"hxt_kernel:nsrc1"},
-                "beta050": {"hxt_kernel:nsrc1"}, "beta150": {"hxt_kernel:nsrc1"}}
+                "beta050": {"hxt_kernel:nsrc1"}, "beta150": {"hxt_kernel:nsrc1"}, "is_mask": {"hxt_kernel:nsrc1"},
+                "beta050_mask": {"hxt_kernel:nsrc1"}, "beta150_mask": {"hxt_kernel:nsrc1"}}
 
 
 def expected_paths(form):
@@ -317,7 +378,7 @@ def test_every_form_reached_every_path_it_can():
     profiles/mu_divergence_elementwise.txt)."""
     for form in FORMS:
         print(f"gpu {form} {_worst[form][0]:.3g}\ngpuloss {form} {_worst[form][1]:.3g}")
-    want = len(SHAPES) * len(VARIANTS) + len(SPOT_SHAPES) * len(FORMS)
+    want = len(SHAPES) * len(VARIANTS) + len(SPOT_SHAPES) * len(FORMS) + len(ONES_SHAPES) * len(ONES_FORMS)
     if len(_done) < want:
         pytest.skip("runs after the whole table (the file as a whole)")
     for form in FORMS:

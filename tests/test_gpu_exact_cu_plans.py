@@ -20,7 +20,8 @@ run_pgd_config, run_divergence_config, run_spotlight, run_hals_row) with every b
 
 Counts: 128, 64, 32 (the partition sizes: the whole table exact_problems.CU_SHAPES, which reaches every count-dependent path at each of
 them -- the last test); 1 (the degenerate plan: one chunk, whole tiles only, one piece) and 38 (no multiple of 4: no XCD placement, no
-chase) on the small rows.  The conv families' epilogues (masked MU, PGD, Itakura-Saito, masked KL) run at 32 CUs on one row per tile form.
+chase) on the small rows.  The conv families' epilogues (masked MU, PGD, Itakura-Saito, masked KL, and Itakura-Saito and beta = 0.5
+under the mask -- the sentinel families, handed junk under the mask) run at 32 CUs on one row per tile form.
 The MU rule under seqNMF's cross-orthogonality penalties (run_xortho_config of tests/test_gpu_exact_xortho.py) runs on those rows too, and
 at every count on the rows of exact_problems.xo_cu_rows: the penalty contraction is a one-source C2 launch with G as the left operand,
 chunked by its own plan, whose tail rows the slab sum reads out of G, and its H side sums as many C3 slabs as the count's plan makes.
@@ -245,6 +246,7 @@ def test_divergence_forms_under_cu_plan(cmf, N, T, K, L, configs, why, form):
             dv.check_same(Hg, base[2], "kt", "H half: H", cfg, base[0], c)
     dv.run_spotlight(planned, N, T, K, L, dict(), form, n_cu=n_cu, record=lambda form, c: None)
     assert planned.handles > 0
+    _done.add(("divergence", form, shape))
 
 
 # ---- the MU rule under seqNMF's cross-orthogonality penalties -----------------------------------------------------------------------
@@ -388,6 +390,7 @@ def test_every_count_dependent_path_reached_at_every_partition_size():
     for n in CU_FULL:
         print(n, {p: _seen[n].get(p, 0) for p in LAUNCH_PATHS if _seen[n].get(p)})
     want = {(n, row[:4]) for n in CU_COUNTS for row in CU_SHAPES[n]} | {("hals", n, row[:4]) for n in CU_HALS_SHAPES for row in CU_HALS_SHAPES[n]}
+    want |= {("divergence", form, row[:4]) for form in CU_EPILOGUE_FORMS for row in CU_EPILOGUE_ROWS}  # every epilogue form on every epilogue row
     if not want <= _done:
         pytest.skip("runs after the whole table (the file as a whole)")
     for n in CU_FULL:

@@ -5,7 +5,8 @@ On the integer problems of tests/exact_problems.py est = tensor_conv(W, H) is ex
 fp64 restatement in ONE update of a divergence form is the fp32 epilogue that forms R / P / Q, the fp32 contraction of those with the
 other factor, and the element-wise step.  For every (form, shape, family) of the shared table (exact_problems.SHAPES; family "W": one
 update_motifs!, family "H": one update_feature_maps! and its loss; KL, masked KL and the beta forms a second time with zeros in the
-data; Itakura-Saito and beta = 0.5 on data relative to est: exact_problems.FORMS) the restatement is run with cdtype = edtype = float32 against its fp64 run, and a `row` line records
+data; Itakura-Saito and beta = 0.5 on data relative to est; Itakura-Saito, beta = 0.5 and beta = 1.5 once more under the 0/1 mask, by
+tests/masked_pq_mu_restatement.py: exact_problems.FORMS) the restatement is run with cdtype = edtype = float32 against its fp64 run, and a `row` line records
 
     err          the largest element-wise relative error of the updated factor
     loss_err     the relative error of the loss (family "H")
