@@ -1475,8 +1475,8 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
     for (int attempt = 0; attempt < 2; ++attempt) {
         // ... whose contraction on the residual and lag correlations (they need H and the residual only; l1W, l2W enter in the sweep) go
         // out behind the loss reduction, so that the device works while the loss travels and the caller's loop comes round
-        if (speculate && attempt == 0 && h->hals_gram != 1) h->after_reduce = [h]() { return hals_w_speculate(h); };
-        if (h->hals_gram == 1) { // hals.jl:41: norm(resids)/data_norm -- the conv with the loss fused in its epilogue, nothing stored
+        if (speculate && attempt == 0 && hals_gram_form(h) != 1) h->after_reduce = [h]() { return hals_w_speculate(h); };
+        if (hals_gram_form(h) == 1) { // hals.jl:41: norm(resids)/data_norm -- the conv with the loss fused in its epilogue, nothing stored
             CMFTRY(launch_conv<CONV_LOSS>(h, nullptr, h->d.Tl, h->conv_gy));
             CMFTRY(reduce_partials(h, h->partial, h->conv_partials, 0, &ss));
             set_est(h, EST_NONE);
@@ -1489,7 +1489,8 @@ static int hals_update_feature_maps_body(cmf_handle h, double l1H, double l2H, d
         if (attempt == 0 && h->hals_status && *h->hals_status) CMFTRY(hals_h_rerun(h));
         else break;
     }
-    *loss = std::sqrt(ss) / h->data_norm;
+    // (under a mask, option "hals_mask": norm(mask .* resid) / norm(mask .* data), the masked MU rule's loss)
+    *loss = std::sqrt(ss) / (hals_masked(h) ? h->xm_norm : h->data_norm);
     return CMF_OK;
 }
 

@@ -307,6 +307,9 @@ struct cmf_handle_s : CmfOptionFields {
     float *hals_snap = nullptr;             // [2][TP][K32]: H and Ht as they were when the persistent sweep started
     double hals_l1 = 0.0, hals_l2 = 0.0;    // regularisers of the sweep in flight (for a rerun)
     int64_t hals_reruns = 0;                // H sweeps redone on the stage pipeline after such an expiry (cmf_get_counter)
+    int64_t hals_masked_convs = 0;          // mode-6 / mode-7 conv launches of the HALS entries under a mask (cmf_get_counter "hals_masked_convs")
+    int64_t hals_resid_gen = -1;            // est_gen at which the HALS entries stored mask .* (est - Xm): the PGD rule's masked residual has the same kind
+                                            // but reads the raw data, whose held-out entries may hold anything, so only this one is taken as current
 
     // PGD rule state (pgd.jl:139-154)
     double pgd_stepW = 5.0, pgd_stepH = 5.0, pgd_cur_loss = -1.0;
@@ -386,11 +389,17 @@ struct cmf_handle_s : CmfOptionFields {
     int64_t recentre_launches = 0;
     bool wb_hold = false;
 };
+// The HALS entries under a mask of cmf_mu_set_mask (option "hals_mask"): HALS on the data with its held-out entries imputed by the current
+// estimate.  est - imputed data = mask .* (est - data), so both projections are contracted from the masked residual (conv modes 6 / 7 on Xm /
+// XmT), whatever "hals_gram" says: its difference forms would read the imputed data itself, which is never formed.
+static inline bool hals_masked(const cmf_handle_s *h) { return h->mu_mask && h->hals_mask != 0; }
+static inline int hals_gram_form(const cmf_handle_s *h) { return hals_masked(h) ? 0 : h->hals_gram; }
 static inline bool xo_active(const cmf_handle_s *h) { return h->xo_lam[0] > 0.0 || h->xo_lam[1] > 0.0 || h->xo_lam[2] > 0.0; }
 // the refusals of cmf_mu_install.h asked of this handle: CMF_OK, or the code with its text as the thread's last error
 static inline int mu_ask(const cmf_handle_s *h, const MuAsk &q)
 {
-    const MuFacts f{h->mu_div, h->mu_beta, h->mu_mask, h->kl_mask, h->pq_mask, h->is_div, h->gram, xo_active(h), h->group || h->root_only || h->sharded, h->have_data};
+    const MuFacts f{h->mu_div, h->mu_beta, h->mu_mask, h->kl_mask, h->pq_mask, h->is_div, h->gram, xo_active(h), h->group || h->root_only || h->sharded, h->have_data,
+                    h->hals_mask};
     std::string msg;
     const int rc = mu_refusal(f, q, &msg);
     return rc == CMF_OK ? rc : fail(rc, "%s", msg.c_str());
@@ -654,7 +663,7 @@ int wb_after_H(cmf_handle_s *h); // hook: the kernels that make H final have bee
 int gram_ensure(cmf_handle_s *h);
 int hals_w_impl(cmf_handle_s *h, double l1W, double l2W);
 int hals_w_speculate(cmf_handle_s *h);
-int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked = false, bool loss_abs = false);
+int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked = false, bool loss_abs = false, const float *data = nullptr); // (data == NULL: the handle's raw data)
 int hals_resid_and_loss(cmf_handle_s *h, double *sumsq);
 int gram_w_impl(cmf_handle_s *h, double l1W, double l2W);
 int gram_w_partial(cmf_handle_s *h, float *hh_out);
@@ -891,14 +900,16 @@ static int launch_conv(cmf_handle_s *h, float *out, int T_store, int gy, const f
 // The one-wave conv tiles of tile rows [row0, row0 + nrows) on h->stream (conv3_chase_kernel; K a multiple of 32): the tail of the
 // grid is cut into pieces for a chip of n_cu CUs like launch_conv does.  gate != NULL: every tile waits for *gate >= its row + 1 (the
 // HALS row pipeline's last progress flag) and reads H with agent-scope loads.  Loss partials pidx0 ... pidx0 + *npartials - 1.
+// data == NULL: the handle's raw data in the layout the mode reads (the masked residual of the HALS rule passes Xm); the mask is the handle's.
 template <int MODE>
 static int launch_conv_rows(cmf_handle_s *h, float *out, int row0, int nrows, int pidx0, int n_cu, const int *gate, int *abort_word,
-                            int *host_status, int *npartials, int T_store = -1)
+                            int *host_status, int *npartials, int T_store = -1, const float *data = nullptr)
 {
     ProfScope prof_(h, MODE == CONV_EST_T ? PROF_CONV_T : MODE == CONV_LOSS_EST ? PROF_CONV_LOSS_STORE : PROF_CONV_RESID);
     const CmfDims &d = h->d;
     ConvParams p;
-    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = conv_data_transposed(MODE) ? h->XT : h->X; p.partial = h->partial; p.mask = h->M;
+    if (conv_reads_mask(MODE) && !h->M) return fail(CMF_ERR_STATE, "internal: a masked conv without a mask");
+    p.Ht = h->Ht; p.Wt = h->Wt; p.out = out; p.data = data ? data : (conv_data_transposed(MODE) ? h->XT : h->X); p.partial = h->partial; p.mask = h->M;
     p.out2 = nullptr;
     p.Np = d.Np; p.TP = d.TP; p.PADL = d.PADL; p.K = d.K; p.KB = d.KB; p.L = d.L; p.T_store = T_store >= 0 ? T_store : d.Tl;
     p.N = d.N;

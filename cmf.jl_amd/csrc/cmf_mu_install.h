@@ -41,13 +41,14 @@ struct MuFacts {
     int div; double beta; bool mask;     // the installed form
     int kl_mask, pq_mask, is_div;        // the gate options
     int gram; bool xortho, group, have_data; // option "gram", active weights of cmf_mu_set_xortho, a group / sharded handle, data on the device
+    int hals_mask = 0;                   // option "hals_mask": the HALS entries run their imputed form under a mask (last: aggregates that end at have_data leave it 0)
     bool gate(const char *name) const { return !name || (name[0] == 'k' ? kl_mask : name[0] == 'p' ? pq_mask : is_div) != 0; }
 };
 enum MuAskKind {
     MU_ASK_SET_MASK, MU_ASK_CLEAR_MASK, // cmf_mu_set_mask(mask) / (NULL); value != 0: cmf_set_mask takes the mask for the PGD entries, which has made its own checks
     MU_ASK_SET_KIND, MU_ASK_SET_BETA,   // cmf_mu_set_divergence(kind), cmf_mu_set_beta_divergence(beta)
     MU_ASK_SET_GRAM, MU_ASK_GATE_OFF,   // cmf_set_option("gram", value), cmf_set_option(name, 0) of a gate
-    MU_ASK_SQUARE_RULE,                 // a rule that minimises the squared error only is about to run (name: "HALS" has no masked form either, "PGD" brings its own mask)
+    MU_ASK_SQUARE_RULE,                 // a rule that minimises the squared error only is about to run (name: "HALS" has no masked form without option "hals_mask", "PGD" brings its own mask)
     MU_ASK_SET_XORTHO                   // cmf_mu_set_xortho with a weight > 0
 };
 struct MuAsk { int what; int kind = 0; double beta = 0.0; int value = 0; const char *name = nullptr; };
@@ -129,7 +130,7 @@ static inline int mu_refusal(const MuFacts &f, const MuAsk &q, std::string *msg)
         if (cur.gate && !std::strcmp(q.name, cur.gate)) return mu_refuse(msg, CMF_ERR_STATE, "%s: the %s is installed; %s", q.name, cur.noun, way_square);
         return CMF_OK;
     case MU_ASK_SQUARE_RULE:
-        if (f.mask && !std::strcmp(q.name, "HALS"))
+        if (f.mask && !f.hals_mask && !std::strcmp(q.name, "HALS"))
             return mu_refuse(msg, CMF_ERR_STATE, "a mask of cmf_mu_set_mask is installed: the HALS rule has no masked form (its denominators become per-entry masked norms); clear it first");
         if (f.div != CMF_DIV_SQUARE)
             return mu_refuse(msg, CMF_ERR_STATE, "the %s is installed (%s): this rule minimises the squared error only; restore CMF_DIV_SQUARE first", cur.noun, cur.setter);

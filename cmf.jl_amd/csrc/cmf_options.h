@@ -39,6 +39,8 @@ struct CmfOptionFields {
     // the gates of the MU forms: "kl_mask" = 1 lets the KL form, "pq_mask" = 1 the Itakura-Saito / beta forms and a mask of cmf_mu_set_mask be
     // installed together; "is_div" = 1 lets cmf_mu_set_divergence take CMF_DIV_IS
     int kl_mask = 0, pq_mask = 0, is_div = 0;
+    int hals_mask = 0;        // "hals_mask": under a mask of cmf_mu_set_mask the HALS entries run on the data with its held-out entries imputed by the
+                              // current estimate (the residual is the masked one; cmf_rules.hip) instead of being refused
 };
 
 enum OptScope {
@@ -109,6 +111,7 @@ static const OptRow kOptions[] = {
     OPT_FLAG(kl_mask, "the mask and the divergence of the MU rule are chosen", FX_MU_GATE), // cmf_mu_set_mask + cmf_mu_set_divergence(KL) together
     OPT_FLAG(pq_mask, "the mask and the divergence of the MU rule are chosen", FX_MU_GATE), // cmf_mu_set_mask + the Itakura-Saito / beta form together
     OPT_FLAG(is_div, "the divergence of the MU rule is chosen", FX_MU_GATE),                // lets cmf_mu_set_divergence take CMF_DIV_IS
+    OPT_FLAG(hals_mask, "the HALS rule runs", FX_DROP_EST | FX_DROP_SPEC),                  // cmf_mu_set_mask + cmf_hals_update_*: the imputed form (switchable at any time)
 };
 #undef OPT_ANY_VALUE
 #undef OPT_FLAG

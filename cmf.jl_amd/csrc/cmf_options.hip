@@ -137,6 +137,7 @@ static const CounterRow<cmf_handle_s> kCounters[] = {
     CMF_COUNTER_ROW("xortho_launches", h->xo_launches, 0),                          // launches of the kernels of cmf_xortho.h (0 while the weights of cmf_mu_set_xortho are 0 and no cost / terms entry was called)
     CMF_COUNTER_ROW("recentre_launches", h->recentre_launches, 0),                  // launches of the kernels of cmf_recentre.hip (four per step of cmf_mu_set_recentre / cmf_recentre)
     CMF_COUNTER_ROW("signif_launches", h->signif_launches, 0),                      // launches of the kernels of cmf_signif.h (cmf_null_moments: three per batch of draws)
+    CMF_COUNTER_ROW("hals_masked_convs", h->hals_masked_convs, 0),                  // conv launches with the masked residual epilogue (modes 6 and 7) made by the HALS entries (option "hals_mask")
     CMF_COUNTER_ROW("small_k_fused_h_updates", h->sk_fused_h, CTR_SUM_SHARDS),      // H updates that ran inside the few-component C3 launch
     // host cost of the pipelined iterations of a group (reading a counter resets nothing)
     CMF_COUNTER_ROW("allreduce_calls", h->group->n_allreduce, CTR_GROUP_ONLY),      // collectives this handle has issued since it was made

@@ -3,11 +3,11 @@
 #include "cmf_internal.h"
 
 // est := tensor_conv(W,H) - data (the residual hals.jl / pgd.jl carry), with the loss sum in d_scalar[0]
-int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked, bool loss_abs)
+int resid_and_loss(cmf_handle_s *h, double *sumsq, bool masked, bool loss_abs, const float *data)
 {
     const CmfDims &d = h->d;
-    CMFTRY(masked ? launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy, nullptr, loss_abs) // pgd.jl:64-70
-                  : launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy, nullptr, loss_abs));
+    CMFTRY(masked ? launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy, data, loss_abs) // pgd.jl:64-70
+                  : launch_conv<CONV_RESID>(h, h->est, d.Tl, h->conv_gy, data, loss_abs));
     set_est(h, pgd_est_kind(masked, loss_abs));
     return reduce_partials(h, h->partial, h->conv_partials, 0, sumsq);
 }
@@ -163,9 +163,27 @@ static int compute_hh(cmf_handle_s *h, float *out = nullptr)
 
 // Behind the loss reduction of update_feature_maps! (the residual is current, H final): G = resid * H_unfold' and HH of the NEXT
 // update_motifs! (hals.jl:56-60, 104-110), like the MU rule's w_speculate.  Taken by hals_w_impl if nothing has passed set_est since.
+// The residual the HALS entries contract from, and whether est holds it for the resident W, H.  Under a mask (option "hals_mask") it is
+// mask .* (est - Xm): the residual against the data with its held-out entries imputed by est, stored by conv mode 6 ON Xm -- the epilogue
+// multiplies by the mask, and Xm holds 0 where data may hold anything, so a held-out entry stores an exact 0.
+static int hals_est_kind(const cmf_handle_s *h) { return hals_masked(h) ? EST_RESID_MASKED : EST_RESID; }
+static bool hals_resid_current(const cmf_handle_s *h)
+{
+    return h->est_kind == hals_est_kind(h) && (!hals_masked(h) || h->hals_resid_gen == h->est_gen);
+}
+static int hals_ensure_resid(cmf_handle_s *h)
+{
+    if (hals_resid_current(h)) return CMF_OK;
+    if (!hals_masked(h)) return resid_and_loss(h, nullptr);
+    CMFTRY(resid_and_loss(h, nullptr, true, false, h->Xm));
+    h->hals_masked_convs += 1;
+    h->hals_resid_gen = h->est_gen;
+    return CMF_OK;
+}
+
 int hals_w_speculate(cmf_handle_s *h)
 {
-    if (h->est_kind != EST_RESID || h->hals_gram == 1 || h->group) return CMF_OK;
+    if (!hals_resid_current(h) || hals_gram_form(h) == 1 || h->group) return CMF_OK;
     CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden));
     CMFTRY(compute_hh(h));
     h->hals_launches[HL_W_SPECULATE] += 1;
@@ -184,7 +202,7 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
     // is opt-in (hals_gram = 1) and the default contracts G from the residual the loss conv stores anyway.
     const size_t LKN = (size_t)d.L * d.K32 * d.Np;
     const float *G = h->numden, *Gsub = nullptr;
-    if (h->hals_gram == 1) {
+    if (hals_gram_form(h) == 1) {
         CMFTRY(hxt_contract(h, h->X, h->X, 1, h->numden));
         CMFTRY(compute_hh(h));
         CMFTRY(launch_gram_w(h, h->hals_HH, h->numden + LKN));
@@ -193,11 +211,11 @@ int hals_w_impl(cmf_handle_s *h, double l1W, double l2W)
         h->hals_launches[HL_G_DIFF] += 1;
     } else {
         // (both already enqueued behind the loss of the update_feature_maps! before, for exactly this state: hals_w_speculate)
-        const bool spec = h->hals_spec_gen >= 0 && h->hals_spec_gen == h->est_gen && h->est_kind == EST_RESID;
+        const bool spec = h->hals_spec_gen >= 0 && h->hals_spec_gen == h->est_gen && hals_resid_current(h); // (one notion of "current": hals_w_speculate asked the same)
         h->hals_spec_gen = -1;
         if (spec) h->spec_hits += 1;
         else {
-            CMFTRY(ensure_resid(h));
+            CMFTRY(hals_ensure_resid(h)); // (under a mask: the masked residual, so G is the contraction against the imputed data)
             CMFTRY(hxt_contract(h, h->est, h->est, 1, h->numden));
             CMFTRY(compute_hh(h));
         }
@@ -260,7 +278,9 @@ static int hals_h_project(cmf_handle_s *h, bool contract, bool snapshot = false)
         flags = h->hals_flags;
         nflags = (int)((size_t)(d.K + d.K * h->hals_pullers + 1) * HALS_FLAG_STRIDE);
     }
-    const bool gram = h->hals_gram && (size_t)d.K32 * (64 + 2 * (d.L - 1)) * sizeof(float) <= 96 * 1024; // (gram_denom_h's LDS window)
+    // (under a mask the difference form would contract the imputed data, which is never formed: the residual form, from mode 7 on XmT / MT)
+    const bool masked = hals_masked(h);
+    const bool gram = hals_gram_form(h) && (size_t)d.K32 * (64 + 2 * (d.L - 1)) * sizeof(float) <= 96 * 1024; // (gram_denom_h's LDS window)
     if (gram) {
         if (!h->gram_numden_h) CMFTRY(dalloc_zero(&h->gram_numden_h, 2 * TK));
         if (contract) {
@@ -271,7 +291,9 @@ static int hals_h_project(cmf_handle_s *h, bool contract, bool snapshot = false)
                            h->tc_S1, d.Tl, d.K32, h->hals_TPp, h->H, h->Ht, snap, d.TP, d.PADL, flags, nflags);
     } else {
         if (contract) {
-            CMFTRY(launch_conv<CONV_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT));
+            CMFTRY(masked ? launch_conv<CONV_MASKED_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XmT)
+                          : launch_conv<CONV_RESID_T>(h, h->estT, d.Tl, h->conv_gy, h->XT));
+            if (masked) h->hals_masked_convs += 1;
             CMFTRY(launch_transconv(h, 1, h->estT));
         }
         hipLaunchKernelGGL(hals_p_init_kernel, dim3((d.Tl + 63) / 64, d.KB), dim3(256), 0, h->stream, h->hals_PT, h->hslabs, (const float *)nullptr,
@@ -372,7 +394,7 @@ int hals_persist_launch(cmf_handle_s *h, const HalsRowParams &q, int debug, bool
 static int hals_chase_rows(cmf_handle_s *h)
 {
     const CmfDims &d = h->d;
-    if (h->hals_opt_chase == 0 || h->hals_pullers <= 0 || d.K % 32 != 0 || h->small_k || h->hals_gram == 1 || h->hals_debug == 1 || h->hals_debug == 2) return 0;
+    if (h->hals_opt_chase == 0 || h->hals_pullers <= 0 || d.K % 32 != 0 || h->small_k || hals_gram_form(h) == 1 || h->hals_debug == 1 || h->hals_debug == 2) return 0;
     if (h->n_cu % 8 != 0 || h->n_cu > 256) return 0;
     const int per_xcd = h->n_cu / 8, need = (d.K + (d.K - 1) * h->hals_pullers + 7) / 8;
     if (per_xcd - need < 4) return 0;
@@ -426,9 +448,13 @@ static int hals_persist_chased(cmf_handle_s *h, const HalsRowParams &q, int ra)
     int rc = hals_persist_launch(h, q, h->hals_debug, false);
     h->stream = h->hals_sB;
     int nA = 0;
-    if (rc == CMF_OK) rc = launch_conv_rows<CONV_RESID>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA);
+    const bool masked = hals_masked(h); // the same tiles with the masked residual's epilogue (mode 6 on Xm and the mask) behind the gate poll
+    if (rc == CMF_OK)
+        rc = masked ? launch_conv_rows<CONV_MASKED_RESID>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA, -1, h->Xm)
+                    : launch_conv_rows<CONV_RESID>(h, h->est, 0, ra, 0, h->hals_cuB, prog_last, abort_word, h->hals_status, &nA);
     h->stream = keep;
     CMFTRY(rc);
+    if (masked) h->hals_masked_convs += 1;
     h->hals_launches[HL_PERSIST_CHASED] += 1;
     h->hals_launches[HL_CHASE] += 1;
     HIPCHK(hipEventRecord(h->hals_ev[1], h->hals_sA));
@@ -447,15 +473,24 @@ int hals_resid_and_loss(cmf_handle_s *h, double *sumsq)
     const CmfDims &d = h->d;
     const int ra = h->hals_chased_rows, nA = h->hals_chased_partials, rows_t = (d.Tl + 63) / 64;
     h->hals_chased_rows = h->hals_chased_partials = 0;
-    if (ra <= 0) return resid_and_loss(h, sumsq);
-    int nB = 0;
-    if (ra < rows_t) {
-        CMFTRY(launch_conv_rows<CONV_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
-        h->hals_launches[HL_CHASE_REST] += 1;
+    const bool masked = hals_masked(h); // under a mask: mode 6 on Xm / M in place of mode 4, launch for launch
+    if (ra <= 0) {
+        if (!masked) return resid_and_loss(h, sumsq);
+        CMFTRY(launch_conv<CONV_MASKED_RESID>(h, h->est, d.Tl, h->conv_gy, h->Xm));
+        h->hals_masked_convs += 1;
+    } else {
+        int nB = 0;
+        if (ra < rows_t) {
+            CMFTRY(masked ? launch_conv_rows<CONV_MASKED_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB, -1, h->Xm)
+                          : launch_conv_rows<CONV_RESID>(h, h->est, ra, rows_t - ra, nA, h->n_cu, nullptr, nullptr, nullptr, &nB));
+            h->hals_launches[HL_CHASE_REST] += 1;
+            if (masked) h->hals_masked_convs += 1;
+        }
+        HIPCHK(hipStreamWaitEvent(h->stream, h->hals_ev[2], 0));
+        h->conv_partials = nA + nB;
     }
-    HIPCHK(hipStreamWaitEvent(h->stream, h->hals_ev[2], 0));
-    h->conv_partials = nA + nB;
-    set_est(h, EST_RESID);
+    set_est(h, hals_est_kind(h));
+    h->hals_resid_gen = h->est_gen;
     return reduce_partials(h, h->partial, h->conv_partials, 0, sumsq);
 }
 

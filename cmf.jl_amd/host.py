@@ -1488,6 +1488,13 @@ def _resolve_alg(alg):
     raise TypeError(f"alg must be an update-rule type or a name like ':mult', got {alg!r}")
 
 
+def _is_hals(alg):
+    try:
+        return _resolve_alg(alg) is HALSUpdate
+    except (TypeError, ValueError, NotImplementedError):
+        return False
+
+
 # --------------------------------------------------------------------------------------
 # driver (src/algs/alternating.jl)
 # --------------------------------------------------------------------------------------
@@ -1632,9 +1639,11 @@ def fit_cnmf(data, L=10, K=5, alg=MultUpdate, max_itr=100, max_time=math.inf, **
     if mask is not None:
         if rule_type is PGDUpdate:
             raise ValueError("alg=:pgd takes its mask through the loss: loss_func=MaskedLoss(SquareLoss(), mask) (pgd.jl:58-70)")
-        if rule_type is not MultUpdate:
+        # (HALS under a mask: the imputed form behind the library option "hals_mask", include/cmf_hip.h)
+        if rule_type is not MultUpdate and not (rule_type is HALSUpdate and (options or {}).get("hals_mask", 0)):
             raise NotImplementedError("mask= is implemented for alg=:mult (and, as loss_func=MaskedLoss(...), for :pgd); the HALS, ADMM, "
-                                      "ANLS and separable fits have no masked form")
+                                      "ANLS and separable fits have no masked form unless options={'hals_mask': 1} (alg=:hals: HALS on "
+                                      "the data with its held-out entries imputed by the current estimate)")
         if devices is not None:
             raise NotImplementedError("mask= is not available with devices=[...]: the masked MU rule runs on one GPU")
         mask = kw["mask"] = farr(mask, data.shape)  # (one object from here on: the rule methods compare by identity)
@@ -2001,6 +2010,8 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
     ``divergence=":kl"`` (for counts) fits the KL form under the mask -- the library option "kl_mask" is set here, beside whatever
     ``options=`` holds -- and scores with the same divergence.  ``divergence=":itakura_saito"`` or ``":beta"`` (for power
     spectrograms) proceed when ``options`` carries ``pq_mask=1`` and score by the mean divergence per entry.
+    ``alg=":hals"`` with ``options={"hals_mask": 1}`` fits with the HALS rule under the mask (HALS on the data with its held-out
+    entries imputed by the current estimate) and scores the same way; any other ``alg`` raises TypeError.
     Returns ``{(L, K): {"train": array(repeats), "test": array(repeats)}}``.  ``block`` defaults to the combination's L.
     seed' = seed + index of the (combination, repeat) pair (fresh draws when ``seed`` is None), so that a result can be redone
     by hand.  Under an initialised torch.distributed process group the pairs are dealt to the ranks like parameter_sweep's
@@ -2014,8 +2025,11 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
                                   "has no masked form, so nothing can be held out (unless options={'pq_mask': 1})")
     data = farr(data)
     N, T = data.shape
-    if "mask" in fit_kw or "alg" in fit_kw:
-        raise TypeError("cross_validate draws its own masks and fits with alg=':mult'")
+    # (the one other rule with a masked form: HALS behind the library option "hals_mask")
+    hals = "alg" in fit_kw and (fit_kw.get("options") or {}).get("hals_mask", 0) and _is_hals(fit_kw["alg"])
+    if "mask" in fit_kw or ("alg" in fit_kw and not hals):
+        raise TypeError("cross_validate draws its own masks and fits with alg=':mult' (or alg=':hals' with options={'hals_mask': 1})")
+    alg = fit_kw.pop("alg", ":mult")
     combos = [(L, K) for L in L_vals for K in K_vals]
     jobs = [(c, rep) for c in combos for rep in range(int(repeats))]
     dist, rank, world = _process_group(group)
@@ -2029,7 +2043,7 @@ def cross_validate(data, L_vals, K_vals, frac=0.1, block=None, repeats=1, seed=N
             continue
         s = None if seed is None else int(seed) + idx
         mask = holdout_mask(N, T, frac=frac, block=L if block is None else block, seed=s)
-        r = fit_cnmf(data, L=L, K=K, alg=":mult", mask=mask, seed=s, **fit_kw)
+        r = fit_cnmf(data, L=L, K=K, alg=alg, mask=mask, seed=s, **fit_kw)
         mine[idx] = evaluate_heldout(r, mask, device=device, divergence=divergence, beta=fit_kw.get("beta", None),
                                      options={"pq_mask": 1} if pq_mask else None)
     if world > 1:

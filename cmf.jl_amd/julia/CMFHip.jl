@@ -567,7 +567,7 @@ function iterate!(rule::HIPMultUpdate, n::Integer; l1W=0, l2W=0, l1H=0, l2H=0, e
     return losses
 end
 
-"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", \"kl_mask\" (set_divergence!(rule, :kl) together with a mask), \"pq_mask\" (set_divergence!(rule, :itakura_saito) / set_beta_divergence! together with a mask), ..."
+"Library option (include/cmf_hip.h, cmf_set_option): \"reuse_est\", \"speculate\", \"gram\", \"small_k\", \"allreduce_overlap\", \"enqueue_threads\", \"kl_mask\" (set_divergence!(rule, :kl) together with a mask), \"pq_mask\" (set_divergence!(rule, :itakura_saito) / set_beta_divergence! together with a mask), \"hals_mask\" (the HALS rule under a mask: HALS on the data imputed by the current estimate), ..."
 set_option!(rule::HIPMultUpdate, name::AbstractString, value::Integer) =
     check(ccall((:cmf_set_option, LIBCMF), Cint, (Ptr{Cvoid}, Cstring, Cint), rule.handle, name, value))
 "The ANLS rule's options: \"anls_backup_only\", \"nnls_large\" (include/cmf_hip.h, the ANLS rule)."

@@ -480,6 +480,25 @@ int cmf_mu_set_divergence(cmf_handle h, int kind);
  * an all-ones mask W and H are those of the unmasked form.  Every switch voids est, the speculated contraction and a deferred loss.
  * Off (the default), every call answers as documented: CMF_ERR_UNSUPPORTED for the combination.  Groups, the Gram forms and the
  * HALS and PGD entries stay refused. */
+/* The HALS rule under a mask: cmf_set_option(h, "hals_mask", 1) (default 0; values other than 0 and 1: CMF_ERR_ARG; single-GPU
+ * handles only; cmf_option_names does not list it, like "kl_mask" above).  With it on, and a 0/1 mask of cmf_mu_set_mask installed
+ * under CMF_DIV_SQUARE, cmf_hals_update_motifs and cmf_hals_update_feature_maps run HALS BY IMPUTATION, the form seqNMF uses for
+ * missing data: before each half-update the held-out entries of data are replaced by the current estimate,
+ *   X~ = select(M, data, tensor_conv(W, H)),
+ * and the ordinary half-update (src/algs/hals.jl) runs on X~.  X~ is never formed: the rule reads the residual only, and
+ * est - X~ = M .* (est - data).  The convs store (est - Xm) .* M with Xm = select(M, data, 0), an exact 0 at a held-out entry whatever
+ * data holds there (NaN and Inf included); G of the W half and P of the H half are contracted from it, the sweeps are unchanged.
+ * Every step of a half-update minimises a block of norm(X~ - est)^2 exactly, and that majorises norm(M .* (data - est))^2 with
+ * equality at the current point: with l1 = l2 = 0 the loss does not increase, and the fixed points are those of the masked objective.
+ * LOSS: norm(M .* (est - data)) / norm(Xm), the masked MU rule's (cmf_mu_set_mask above), so the two rules' loss_hist compare.
+ * "hals_gram": its difference forms (2, the default, and 1) would contract X~ itself; while this form runs both projections come
+ * from the stored residual as under hals_gram = 0.  The stored value is kept and applies again when the mask or the option goes.
+ * Every other HALS option is honoured ("hals_chase" included: the chasing tiles carry the masked epilogue).  With an all-ones mask W
+ * and H are those of the plain rule under hals_gram = 0, bit for bit.  The option can be switched at any time; a switch voids est
+ * and the speculated contraction.  Off (the default), the HALS entries answer CMF_ERR_STATE while the mask is installed, as
+ * documented above.  Real-valued weights and the mask of cmf_set_mask stay the PGD rule's (the HALS entries ignore them); groups
+ * and a divergence other than CMF_DIV_SQUARE stay refused.  cmf_get_counter "hals_masked_convs": conv launches with the masked
+ * residual epilogue made by the HALS entries (0 while the form has not run). */
 /* CMF_DIV_IS: the multiplicative update of the Itakura-Saito divergence (beta = 0; beta_loss="itakura-saito" elsewhere), the
  * scale-invariant objective for POWER spectrograms: a quiet harmonic weighs as much as a loud one.  It is taken by
  * cmf_mu_set_divergence only after cmf_set_option(h, "is_div", 1) (default 0; values other than 0 and 1: CMF_ERR_ARG; single-GPU
